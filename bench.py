@@ -6,8 +6,15 @@ loss heads, grad all-reduce, AdamW + weight refresh) and, on every 10th iteratio
 fwd as one 2B batch, student fwd+bwd, negative-guidance loss, all-reduce, upper AdamW).  Synthetic (latent, noise,
 timestep, prompt-embed) inputs are resident in HBM before the timed region; weights are random-init SD-2.1 shapes.
 
-Prints ONE JSON line (rank 0).  Extra keys: roofline (dominant kernel, HIP-event timed), cpu_baseline (oracle on host
-cores, N=1 only), breakdown.
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times --steps iterations, writes --dump-outputs and prints the
+line; `roofline` and `cpu_baseline` are null there.  --full adds everything that takes runs of its own: per-phase and eager
+step times, the VAE / text-encode extras, roofline (dominant kernel, HIP-event timed), the B=16 point and cpu_baseline (oracle
+on host cores, N=1 only); the --no_* switches thin a --full run out.
+
+--dump-outputs DIR: what the last timed iteration handed its caller, written right after the timed loop (float64 / float32
+.npy, ~32 MB at SD-2.1 size): losses.npy = the step's loss accumulators (diff, distill, block, unused: what Trainer returns),
+student_weights_sample.npy = the student's fp32 master weights after it, student_weights_update_sample.npy = what that
+iteration changed in them; the two weight arrays sample the same fixed, seeded positions of the parameter arena.
 """
 import argparse
 import json
@@ -41,7 +48,28 @@ def parse():
     p.add_argument("--no_roofline", action="store_true")
     p.add_argument("--no_vae", action="store_true", help="skip the (untimed) VAE-encode extra")
     p.add_argument("--no_graph", action="store_true", help="eager Python launches instead of hipGraph replay")
-    return p.parse_args()
+    p.add_argument("--full", action="store_true",
+                   help="also measure what the headline figure does not need (extras, roofline, B=16 point, CPU baseline)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the losses and a seeded sample of the weights of the last timed iteration to DIR/<name>.npy")
+    a = p.parse_args()
+    if a.steps < 1:
+        p.error("--steps must be at least 1")
+    return a
+
+
+DUMP_SAMPLE = 1 << 22      # weight positions sampled by --dump-outputs: 2 arrays x 16 MB
+
+
+def dump_outputs(path, arrays):
+    """Writes {name: tensor} as path/<name>.npy in float32 / float64 (the --dump-outputs contract: 64 MB at most)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    out = {n: t.detach().cpu().numpy() for n, t in arrays.items()}
+    assert all(v.dtype in (np.float32, np.float64) for v in out.values())
+    assert sum(v.nbytes for v in out.values()) <= 64 << 20
+    for n, v in out.items():
+        np.save(os.path.join(path, n + ".npy"), v)
 
 
 def cpu_baseline(budget, latent, tiny, full=False):
@@ -294,6 +322,13 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
+    master = student.store.master
+    dump_idx = w_before = None
+    if a.dump_outputs and rank == 0:
+        n = min(DUMP_SAMPLE, master.numel())
+        dump_idx = (torch.arange(n) if n == master.numel() else
+                    torch.randint(0, master.numel(), (n,), generator=torch.Generator().manual_seed(0)).sort().values).to(dev)
+
     for i in range(a.warmup):
         bilevel_iter(i) if graphs is not None else main_iter(i)
     if a.warmup > 0 and graphs is None:
@@ -301,6 +336,8 @@ def main():
     sync()
     t0 = time.perf_counter()
     for i in range(a.steps):
+        if dump_idx is not None and i == a.steps - 1:
+            w_before = master.index_select(0, dump_idx)       # queued in stream order: the weights the last iteration starts from
         bilevel_iter(i, a.warmup)
     sync()
     el = time.perf_counter() - t0
@@ -309,8 +346,13 @@ def main():
         tt = torch.tensor([el], device=dev, dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         el = float(tt.item())
+    if dump_idx is not None:         # before anything below runs more steps
+        w_after = master.index_select(0, dump_idx)
+        dump_outputs(a.dump_outputs, {"losses": st.losses, "student_weights_sample": w_after,
+                                      "student_weights_update_sample": w_after - w_before})
+        del w_before, w_after
 
-    # ---- untimed extras on rank 0: per-phase times, roofline of the dominant kernel
+    # ---- untimed extras on rank 0 (--full: per-phase times, roofline of the dominant kernel)
     extras = {}
     if rank == 0:
         def timed(fn, n):
@@ -320,7 +362,7 @@ def main():
                 fn(j)
             torch.cuda.synchronize()
             return (time.perf_counter() - s) / n
-        if world == 1:
+        if world == 1 and a.full:
             if graphs is not None:
                 d0 = data[0]
                 # (steady state of the main step alone: every call finds the teacher pass its predecessor queued and queues the next one -
@@ -340,7 +382,7 @@ def main():
         if graphs is not None:
             extras["graphs_per_main_step"] = len(graphs.g_main.all())
         extras["lockstep_forward"] = bool(st.lockstep)
-        if world == 1 and not a.no_vae and not a.tiny:
+        if world == 1 and a.full and not a.no_vae and not a.tiny:
             # SURVEY 8f N1, NOT part of `value` (SURVEY 8d keeps the VAE off the timed path): what a pixel_values batch adds
             # in front of every step - vae.encode(pixels).latent_dist.sample() * 0.18215 (trainer.py:2405-2406)
             from pdm.models.vae.autoencoder_kl import AutoencoderKL
@@ -363,7 +405,7 @@ def main():
         flop_upper = 2.0 * (2 * Tm + 3 * Sm) * B
         extras["model_tflops_per_gpu"] = round((a.steps * flop_main + n_upper * flop_upper) / el / 1e12, 2)
     roof = None
-    if rank == 0 and not a.no_roofline and world == 1:
+    if rank == 0 and a.full and not a.no_roofline and world == 1:
         # Dominant kernel: one eager main step with every GEMM launch bracketed by HIP events on its launch stream
         # (pdm._pdmk.PROFILE) and labelled with the candidate kernel the library's plan cache picked; the teacher runs
         # in line here (no second stream) so that an event pair times one kernel, not two overlapped ones.
@@ -500,7 +542,7 @@ def main():
                 "top_kernels": {sym(kd) + " | " + class_names[kd[1:3]]: {"tflops": round(v[0] / (v[1] * 1e-3) / 1e12, 2),
                                                                         "ms": round(v[1], 2), "launches": v[2]}
                                 for kd, v in top}}
-    if rank == 0 and world == 1 and not a.no_b16 and not a.tiny and B != 16 and graphs is not None:
+    if rank == 0 and world == 1 and a.full and not a.no_b16 and not a.tiny and B != 16 and graphs is not None:
         # the shipped bilevel YAML's per-GPU batch (configs/baselines/sd-2-1_coco_aptp_both_512_bilevel.yaml:48), same cadence,
         # same protocol, NOT the bench value (configs[1] is quoted at B = 8)
         graphs.close()
@@ -537,7 +579,7 @@ def main():
                          "steps": 10, "warmup": 2}
         del g2, d2
     cpu = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if rank == 0 and world == 1 and a.full and not a.no_cpu_baseline:
         del data
         torch.cuda.empty_cache()
         cpu = cpu_baseline(a.budget, a.latent, a.tiny, full=a.cpu_baseline_full)

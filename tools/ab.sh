@@ -7,7 +7,7 @@ for r in $(seq 1 $R); do
   if [ $((r % 2)) = 1 ]; then ORDER="A B"; else ORDER="B A"; fi
   for v in $ORDER; do
     if [ $v = A ]; then E="$A"; else E="$B"; fi
-    out=$(env $E timeout -k 10 200 python bench.py --steps 20 --warmup 5 --no_cpu_baseline --no_b16 --no_vae --no_roofline 2>/dev/null | tail -1)
+    out=$(env $E timeout -k 10 200 python bench.py --full --steps 20 --warmup 5 --no_cpu_baseline --no_b16 --no_vae --no_roofline 2>/dev/null | tail -1)
     python - "$v" "$E" "$out" <<'PY'
 import json, sys
 d = json.loads(sys.argv[3])
