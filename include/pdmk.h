@@ -428,6 +428,28 @@ int pdmk_attn_fwd_causal(const void* q, const void* k, const void* v, void* o, f
 int pdmk_gelu_fwd(const void* x, void* y, int64_t n, int dtype, pdmk_stream stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Image preprocessing in front of the VAE encoder (pdm/utils/data.py): the reference's torchvision training transform
+ * (pdm/utils/data_utils.py:68-97: Resize(R, BILINEAR), CenterCrop(R) / RandomCrop(R), RandomHorizontalFlip, ToTensor,
+ * Normalize(0.5, 0.5)) over a ragged batch of decoded 8-bit RGB images, bit-exact with Pillow's 8-bpc bilinear resample
+ * (horizontal pass rounded and clipped to uint8, then the vertical pass; triangle-filter coefficients in double, normalised
+ * to 22-bit fixed point).
+ * src: the images packed back to back as HWC uint8 (src_bytes long, 4-byte aligned); image i starts at desc[i].offset and is
+ *   resized to (rh, rw), cropped at (top, left) to R x R, mirrored when flip = 1.  Only the crop window is computed.
+ * desc: the B descriptors in HOST memory (validated here); desc_dev: the same descriptors on the device (8-byte aligned),
+ *   read by the kernel.  out: fp32 NCHW [B, 3, R, R] in [-1, 1].
+ * -1 on a null / misaligned pointer, B or R out of range (1 <= R <= 1024), a zero size, a crop outside the resized image,
+ *   an image outside src (its last 4-byte word included) or a downscale above 127x. */
+typedef struct {
+    int64_t offset;           /* byte offset of the image in src */
+    int64_t h, w;             /* decoded size */
+    int64_t rh, rw;           /* resized size */
+    int64_t top, left;        /* crop origin in the resized image */
+    int64_t flip;             /* 1: horizontal flip after the crop */
+} pdmk_image_desc;
+int pdmk_image_prep(const uint8_t* src, int64_t src_bytes, const pdmk_image_desc* desc, const pdmk_image_desc* desc_dev,
+                    int B, int R, float* out, pdmk_stream stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Data-parallel gradient exchange: DDP's all-reduce inside accelerator.backward
  * (pdm/training/trainer.py:117-129, 2782, 2808) as RCCL all-reduces over xGMI behind an explicit communicator handle.
  * pdmk_comm_unique_id: rank 0 fills 128 bytes (ncclUniqueId) and hands them to the other ranks out of band (the Python

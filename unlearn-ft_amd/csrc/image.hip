@@ -1,0 +1,226 @@
+// pdmk_image_prep: the training transform of the image-caption loader (Resize(R, BILINEAR) -> CenterCrop / RandomCrop ->
+// optional horizontal flip -> ToTensor -> Normalize(0.5, 0.5)) over a ragged batch of decoded 8-bit RGB images, bit-exact
+// with Pillow's 8-bpc two-pass resample (libImaging/Resample.c, Pillow >= 7):
+//   * per output coordinate: scale = in / out, filterscale = max(scale, 1), support = filterscale (triangle filter),
+//     center = (xx + 0.5) * scale, taps [int(center - support + 0.5), int(center + support + 0.5)) clipped to the input,
+//     w_i = tri((i + xmin - center + 0.5) * (1 / filterscale)), normalised by their sequential double sum, then
+//     k_i = int(0.5 + w_i * 2^22);
+//   * horizontal pass: (2^21 + sum_i px * k_i) >> 22, clipped to [0, 255] (uint8 intermediate); vertical pass likewise
+//     over the intermediate rows;
+//   * x / 255 then (x - 0.5) / 0.5 in fp32.
+// Every double / float operation above is written out in the order Pillow / torch perform it; FP contraction is off for this
+// file (an FMA would change the rounding of `center` or of the fixed-point coefficients, and with it the output bits).
+//
+// One workgroup per (output row band of BAND rows, image).  Only the crop window is computed: the band's output rows need
+// source rows [ymin(first row), ymax(last row)); their horizontal pass (only the R columns of the crop) goes to LDS as uint8,
+// in chunks of STAGE_BYTES when a large downscale needs more rows than fit, and each thread accumulates the vertical sums of
+// its (row, column) outputs in registers across the chunks.  Source reads are aligned 4-byte loads; neighbouring threads
+// read neighbouring words of the same row.
+#include "common.h"
+
+#pragma clang fp contract(off)
+
+namespace {
+
+constexpr int NT = 256;
+constexpr int BAND = 4;                 // output rows per workgroup
+constexpr int RMAX = 1024;              // largest output side
+constexpr int KVMAX = 256;              // vertical taps per output row: downscale <= 127x
+constexpr int STAGE_BYTES = 24 * 1024;  // horizontal-pass rows staged in LDS (uint8, [row][channel][column])
+constexpr int PB = 22;                  // PRECISION_BITS
+
+__device__ __forceinline__ double tri(double x) {
+    if (x < 0.0) x = -x;
+    return x < 1.0 ? 1.0 - x : 0.0;
+}
+
+// Pillow's precompute_coeffs for one output coordinate xx: first tap, tap count, the filter centre and the weight sum
+struct Axis {
+    double scale, fs, support, ss;
+};
+__device__ __forceinline__ Axis make_axis(int in, int out) {
+    Axis a;
+    a.scale = (double)in / (double)out;
+    a.fs = a.scale < 1.0 ? 1.0 : a.scale;
+    a.support = 1.0 * a.fs;
+    a.ss = 1.0 / a.fs;
+    return a;
+}
+__device__ __forceinline__ void tap_range(const Axis& a, int in, int xx, double& center, int& xmin, int& cnt) {
+    center = 0.0 + ((double)xx + 0.5) * a.scale;
+    xmin = (int)(center - a.support + 0.5);
+    if (xmin < 0) xmin = 0;
+    int xmax = (int)(center + a.support + 0.5);
+    if (xmax > in) xmax = in;
+    cnt = xmax - xmin;
+}
+__device__ __forceinline__ double weight(const Axis& a, int i, int xmin, double center) {
+    return tri(((double)(i + xmin) - center + 0.5) * a.ss);
+}
+// normalize_coeffs_8bpc (bilinear weights are never negative)
+__device__ __forceinline__ int fixed_coeff(double w, double ww) {
+    if (ww != 0.0) w = w / ww;
+    return (int)(0.5 + w * (double)(1 << PB));
+}
+__device__ __forceinline__ int clip8(int v) {
+    v >>= PB;
+    return v < 0 ? 0 : (v > 255 ? 255 : v);
+}
+
+// sequential byte reader over one source row: each aligned word is loaded once
+struct Bytes {
+    const uint32_t* w;
+    long cur;
+    uint32_t val;
+    __device__ __forceinline__ int at(long q) {
+        const long d = q >> 2;
+        if (d != cur) {
+            cur = d;
+            val = w[d];
+        }
+        return (int)((val >> (8 * (int)(q & 3))) & 255u);
+    }
+};
+
+template <int PER>
+__global__ __launch_bounds__(NT) void image_prep_kernel(const uint8_t* __restrict__ src, const pdmk_image_desc* __restrict__ descs,
+                                                        int R, float* __restrict__ out) {
+    __shared__ double h_center[RMAX], h_ww[RMAX];
+    __shared__ int h_min[RMAX], h_cnt[RMAX];
+    __shared__ int v_k[BAND][KVMAX];
+    __shared__ int v_min[BAND], v_cnt[BAND];
+    __shared__ uint8_t stage[STAGE_BYTES];
+
+    const int img = blockIdx.y;
+    const int y0 = blockIdx.x * BAND;
+    const int nb = R - y0 < BAND ? R - y0 : BAND;            // output rows of this band
+    const pdmk_image_desc d = descs[img];
+    const int H = (int)d.h, W = (int)d.w, RH = (int)d.rh, RW = (int)d.rw, top = (int)d.top, left = (int)d.left;
+    const Axis ax = make_axis(W, RW), ay = make_axis(H, RH);
+
+    // horizontal coefficients of the R crop columns: the weight sum is a sequential double sum, one thread per column
+    for (int x = threadIdx.x; x < R; x += NT) {
+        double c;
+        int m, n;
+        tap_range(ax, W, left + x, c, m, n);
+        double ww = 0.0;
+        for (int i = 0; i < n; ++i) ww += weight(ax, i, m, c);
+        h_center[x] = c;
+        h_ww[x] = ww;
+        h_min[x] = m;
+        h_cnt[x] = n;
+    }
+    // vertical coefficients of the band's rows, one thread per row
+    if (threadIdx.x < nb) {
+        const int y = threadIdx.x;
+        double c;
+        int m, n;
+        tap_range(ay, H, top + y0 + y, c, m, n);
+        double ww = 0.0;
+        for (int i = 0; i < n; ++i) ww += weight(ay, i, m, c);
+        for (int i = 0; i < n; ++i) v_k[y][i] = fixed_coeff(weight(ay, i, m, c), ww);
+        v_min[y] = m;
+        v_cnt[y] = n;
+    }
+    __syncthreads();
+
+    int s0 = v_min[0], s1 = 0;
+    for (int y = 0; y < nb; ++y) s1 = max(s1, v_min[y] + v_cnt[y]);
+    const int rows_per_chunk = STAGE_BYTES / (3 * R);
+    const long row_bytes = 3L * W;
+    Bytes rd{reinterpret_cast<const uint32_t*>(src), -1, 0u};
+
+    int acc[PER][3];
+#pragma unroll
+    for (int j = 0; j < PER; ++j) acc[j][0] = acc[j][1] = acc[j][2] = 1 << (PB - 1);
+
+    for (int c0 = s0; c0 < s1; c0 += rows_per_chunk) {
+        const int c1 = min(c0 + rows_per_chunk, s1);
+        // horizontal pass of source rows [c0, c1) over the crop columns -> stage[row][channel][x]
+        for (int p = threadIdx.x; p < (c1 - c0) * R; p += NT) {
+            const int r = p / R, x = p - r * R;
+            const int m = h_min[x], n = h_cnt[x];
+            const double c = h_center[x], ww = h_ww[x];
+            long q = d.offset + (long)(c0 + r) * row_bytes + 3L * m;
+            int s[3] = {1 << (PB - 1), 1 << (PB - 1), 1 << (PB - 1)};
+            for (int i = 0; i < n; ++i, q += 3) {
+                const int k = fixed_coeff(weight(ax, i, m, c), ww);
+                s[0] += rd.at(q) * k;
+                s[1] += rd.at(q + 1) * k;
+                s[2] += rd.at(q + 2) * k;
+            }
+            uint8_t* st = stage + (long)r * 3 * R + x;
+            st[0] = (uint8_t)clip8(s[0]);
+            st[R] = (uint8_t)clip8(s[1]);
+            st[2 * R] = (uint8_t)clip8(s[2]);
+        }
+        __syncthreads();
+        // vertical accumulation of the staged rows into this thread's outputs
+#pragma unroll
+        for (int j = 0; j < PER; ++j) {
+            const int p = threadIdx.x + j * NT;
+            const int y = p / R, x = p - y * R;
+            if (y < nb) {
+                const int m = v_min[y];
+                const int lo = max(c0, m), hi = min(c1, m + v_cnt[y]);
+                for (int sr = lo; sr < hi; ++sr) {
+                    const int k = v_k[y][sr - m];
+                    const uint8_t* st = stage + (long)(sr - c0) * 3 * R + x;
+                    acc[j][0] += (int)st[0] * k;
+                    acc[j][1] += (int)st[R] * k;
+                    acc[j][2] += (int)st[2 * R] * k;
+                }
+            }
+        }
+        __syncthreads();
+    }
+
+    // ToTensor + Normalize, NCHW fp32; the flip mirrors the crop's columns
+    const long plane = (long)R * R;
+    float* o = out + (long)img * 3 * plane;
+#pragma unroll
+    for (int j = 0; j < PER; ++j) {
+        const int p = threadIdx.x + j * NT;
+        const int y = p / R, x = p - y * R;
+        if (y < nb) {
+            const long at = (long)(y0 + y) * R + (d.flip ? R - 1 - x : x);
+#pragma unroll
+            for (int ch = 0; ch < 3; ++ch) {
+                const float v = __fdiv_rn((float)clip8(acc[j][ch]), 255.0f);
+                o[ch * plane + at] = __fdiv_rn(__fsub_rn(v, 0.5f), 0.5f);
+            }
+        }
+    }
+}
+
+bool desc_ok(const pdmk_image_desc& d, int R, int64_t src_bytes) {
+    const int64_t lim = 1 << 20;
+    if (d.h < 1 || d.w < 1 || d.rh < 1 || d.rw < 1 || d.h > lim || d.w > lim || d.rh > lim || d.rw > lim) return false;
+    if (d.top < 0 || d.left < 0 || d.top + R > d.rh || d.left + R > d.rw) return false;
+    if (d.flip != 0 && d.flip != 1) return false;
+    if ((d.h + d.rh - 1) / d.rh > (KVMAX - 1) / 2) return false;          // vertical taps of one output row fit v_k
+    if (d.offset < 0 || d.h * d.w * 3 > src_bytes) return false;
+    const int64_t end = d.offset + d.h * d.w * 3;
+    return end <= src_bytes && ((end + 3) & ~int64_t(3)) <= src_bytes;   // the last aligned word is inside the buffer
+}
+
+}  // namespace
+
+extern "C" int pdmk_image_prep(const uint8_t* src, int64_t src_bytes, const pdmk_image_desc* desc,
+                               const pdmk_image_desc* desc_dev, int B, int R, float* out, pdmk_stream stream) {
+    if (!src || !desc || !desc_dev || !out || B < 1 || B > 65535 || R < 1 || R > RMAX || src_bytes < 1 ||
+        ((uintptr_t)src & 3) || ((uintptr_t)desc_dev & 7) || ((uintptr_t)out & 3))
+        return -1;
+    for (int i = 0; i < B; ++i)
+        if (!desc_ok(desc[i], R, src_bytes)) return -1;
+    const int per = (BAND * R + NT - 1) / NT;
+    dim3 grid((unsigned)((R + BAND - 1) / BAND), (unsigned)B);
+    hipStream_t st = (hipStream_t)stream;
+    if (per <= 1) hipLaunchKernelGGL(image_prep_kernel<1>, grid, dim3(NT), 0, st, src, desc_dev, R, out);
+    else if (per <= 2) hipLaunchKernelGGL(image_prep_kernel<2>, grid, dim3(NT), 0, st, src, desc_dev, R, out);
+    else if (per <= 4) hipLaunchKernelGGL(image_prep_kernel<4>, grid, dim3(NT), 0, st, src, desc_dev, R, out);
+    else if (per <= 8) hipLaunchKernelGGL(image_prep_kernel<8>, grid, dim3(NT), 0, st, src, desc_dev, R, out);
+    else hipLaunchKernelGGL(image_prep_kernel<16>, grid, dim3(NT), 0, st, src, desc_dev, R, out);
+    PDMK_CHECK_LAUNCH();
+    return 0;
+}

@@ -99,6 +99,7 @@ _SIGS = {
     "pdmk_embed_tokens": ([vp, vp, vp, vp, i64, i32, i32, i32, i32, i32, i32, i32, vp], i32),
     "pdmk_attn_fwd_causal": ([vp, vp, vp, vp, vp, i32, i32, i32, i64, i32, i64, i32, i64, i32, i64, i32, f32, i32, vp], i32),
     "pdmk_gelu_fwd": ([vp, vp, i64, i32, vp], i32),
+    "pdmk_image_prep": ([vp, i64, vp, vp, i32, i32, vp, vp], i32),
     "pdmk_gemm_splitk_workspace_bytes": ([i64, i32, i32], i64),
     "pdmk_groupnorm_workspace_bytes": ([i32, i32], i64),
     "pdmk_groupnorm_bwd_part_workspace_bytes": ([i32, i32], i64),
@@ -895,6 +896,19 @@ def attn_fwd_causal(q, kk, v, o, lse, B, H, N, qs, ks, vs, os_, scale):
 
 def gelu_fwd(x, y):
     _chk(_lib.pdmk_gelu_fwd(_p(x), _p(y), x.numel(), dt(x), _st()), "pdmk_gelu_fwd")
+
+
+def image_prep(src, desc, desc_dev, out):
+    """Resize / crop / flip / normalise a packed batch of uint8 RGB images into out ([B, 3, R, R] fp32 on the device).
+    src: uint8 device tensor holding the images back to back (offsets in desc); desc: int64 [B, 8] HOST tensor
+    (offset, h, w, rh, rw, top, left, flip); desc_dev: the same descriptors on the device (what the kernel reads)."""
+    B, R = out.shape[0], out.shape[-1]
+    if (desc.device.type != "cpu" or desc.dtype != torch.int64 or tuple(desc.shape) != (B, 8) or not desc.is_contiguous()
+            or desc_dev.dtype != torch.int64 or desc_dev.numel() != 8 * B or not desc_dev.is_contiguous()
+            or src.dtype != torch.uint8 or out.dtype != torch.float32 or tuple(out.shape) != (B, 3, R, R)
+            or not out.is_contiguous()):
+        raise PdmkError("image_prep: src uint8, desc int64 [B, 8] on the host, desc_dev its device copy, out fp32 [B, 3, R, R]")
+    _chk(_lib.pdmk_image_prep(_p(src), src.numel(), _p(desc), _p(desc_dev), B, R, _p(out), _st()), "pdmk_image_prep")
 
 
 def softmax_rows(s, p, rows, cols, lds, ldp):

@@ -259,16 +259,63 @@ class Trainer:
     def init_dataloader(self, upper):
         c = self.config
         if not _cfg(c, "synthetic", False):
-            raise NotImplementedError(
-                "image datasets and tokenisation are host-side data loading (not built): pass a dataloader yielding "
-                "{'pixel_values' | 'latents', 'prompt_embeds' | 'input_ids', 'empty_prompt_embeds' | 'empty_input_ids'} "
-                "or run with --synthetic")
+            return self._data_loader(upper)
         bs = int(_cfg(c, "data.dataloader.train_batch_size", 8))
         res = int(_cfg(c, "model.prediction_model.resolution", 512)) // 8
         seed = int(_cfg(c, "seed", 43)) + self.rank + (7919 if upper else 0)
         T = 13 if _cfg(c, "tiny", False) else 77
         return SyntheticBatches(bs, res, T, self.unet_config.cross_attention_dim, seed, self.device,
                                 pixels=bool(_cfg(c, "synthetic_pixels", False)), vae_factor=self.vae_factor)
+
+    # ---- image-caption data (trainer.py:87-98, 160-263, 2262-2268, 2634-2662; pdm/utils/data.py)
+    def _data_loader(self, upper):
+        """The training (upper=False: also the validation and prompt loaders) or upper loader over local data.  Images are
+        transformed to `resolution // 8 * vae_factor` pixels, so the latents are resolution // 8 wide as with --synthetic."""
+        from ..utils import data as D
+        c = self.config
+        if getattr(self, "tokenizer", None) is None:
+            self.tokenizer = D.load_tokenizer(_cfg(c, "pretrained_model_name_or_path"))
+        dl = lambda key, d=None: _cfg(c, "data.dataloader." + key, d)
+        res = int(_cfg(c, "model.prediction_model.resolution", 512)) // 8 * self.vae_factor
+        bs = int(dl("train_batch_size", 8))
+        kw = dict(resolution=res, tokenizer=self.tokenizer, num_workers=int(dl("dataloader_num_workers", 0) or 0),
+                  rank=self.rank, world=self.world, center_crop=bool(dl("center_crop", False)), device=self.device)
+        seed = int(_cfg(c, "seed", 43))
+        if upper:
+            name = _cfg(c, "upper_data.dataset_name")
+            ds = self.init_upper_dataset(D.load_local_dataset(name, _cfg(c, "upper_data.data_files"))["train"])
+            return D.ImageCaptionLoader(ds, batch_size=bs, seed=seed + 1, train=True, random_flip=bool(dl("random_flip", False)),
+                                        image_column=_cfg(c, "upper_data.image_column", "image"),
+                                        caption_column=_cfg(c, "upper_data.caption_column", "caption"), **kw)
+        data = _cfg(c, "data", {})
+        splits = D.get_dataset(data)
+        cols = dict(image_column=_cfg(c, "data.image_column", "image"), caption_column=_cfg(c, "data.caption_column", "caption"))
+        for name, split in splits.items():
+            if split is not None and cols["caption_column"] not in split.column_names:
+                raise ValueError(f"--caption_column '{cols['caption_column']}' needs to be one of: {', '.join(split.column_names)}")
+        ckpt, name = _cfg(c, "pruning_ckpt_dir"), _cfg(c, "data.dataset_name")
+        if _cfg(c, "data.filter_dataset", True) and ckpt and os.path.exists(os.path.join(ckpt, f"{name}_train_mapped_indices.pt")):
+            # trainer.py:2211-2230: the rows the hypernetwork routed to this expert (the reference's file names, the second
+            # without its underscore); without the files every row is used - routing them needs the hypernetwork, not built here
+            expert = int(_cfg(c, "expert_id", 0))
+            for key, fname in (("train", f"{name}_train_mapped_indices.pt"), ("validation", f"{name}validation_mapped_indices.pt")):
+                f = os.path.join(ckpt, fname)
+                if splits[key] is not None and os.path.exists(f):
+                    routed = torch.load(f, map_location="cpu")
+                    splits[key] = splits[key].select(torch.where(routed == expert)[0].tolist())
+        train = D.limit(splits["train"], _cfg(c, "data.max_train_samples"))
+        val = D.limit(splits["validation"], _cfg(c, "data.max_validation_samples"))
+        if val is not None and len(val):           # the validation transform: no flip (data_utils.py:84-95)
+            self.eval_dataloader = D.ImageCaptionLoader(val, batch_size=int(dl("validation_batch_size", bs)), seed=seed,
+                                                        train=False, shuffle=False, **cols, **kw)
+        prompts = _cfg(c, "data.prompts")
+        if prompts is None and val is not None:    # trainer.py:92-94: the validation captions
+            prompts = [D.pick_caption(x, False, None) for x in val[cols["caption_column"]]]
+        if prompts and self.prompt_dataloader is None:
+            prompts = D.read_prompts(prompts, _cfg(c, "data.max_generated_samples"))
+            self.prompt_dataloader = D.PromptBatches(prompts, self.tokenizer, dl("image_generation_batch_size", 1), self.device)
+        return D.ImageCaptionLoader(train, batch_size=bs, seed=seed, train=True, random_flip=bool(dl("random_flip", False)),
+                                    **cols, **kw)
 
     # ---- sampling prologue shared by step/upper_step (trainer.py:2405-2423)
     def _sample(self, batch):
@@ -620,8 +667,8 @@ class BilevelUnetFineTuner(UnetFineTuner):
 
     def init_upper_dataset(self, dataset, preprocess_train=None):
         """trainer.py:2634-2650: the upper (concept) dataset is the rows whose `style` column is in `upper_data.style`.
-        Dataset loading itself is host-side I/O outside this build: `dataset` is anything with
-        `column_names`, `filter` and `with_transform` (a `datasets.Dataset`), handed in by the caller."""
+        `dataset` is anything with `column_names`, `filter` and `with_transform` (a `datasets.Dataset`): the train split of
+        `upper_data.dataset_name` when the trainer builds its own loaders (_data_loader)."""
         caption_column = _cfg(self.config, "upper_data.caption_column", "caption")
         if caption_column not in dataset.column_names:
             raise ValueError(f"--caption_column '{caption_column}' needs to be one of: {', '.join(dataset.column_names)}")
