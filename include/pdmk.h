@@ -450,6 +450,44 @@ int pdmk_image_prep(const uint8_t* src, int64_t src_bytes, const pdmk_image_desc
                     int B, int R, float* out, pdmk_stream stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Sampler (csrc/sampler.hip): what the eager denoising loop of StableDiffusionPruningPipeline.generate_samples does
+ * between two U-Net calls, in one launch (reference: pruning_pipelines.py:955-980 - the `torch.cat([latents] * 2)`,
+ * `noise_pred_uncond + guidance_scale * (noise_pred_text - noise_pred_uncond)` and diffusers PNDMScheduler.step_plms
+ * with skip_prk_steps, as generate_fid_images.py:113-153 drives it).
+ *
+ * One row of the host-built step table (per-step scalars: float64 on the host, then cast to fp32 exactly as the eager
+ * path passes them to pdmk_axpby).  "form(a, x, b, y)" below is pdmk_axpby's fp32 arithmetic, fma(a, x, b * y). */
+typedef struct {
+    int64_t t;                /* U-Net timestep of this step */
+    int32_t mode;             /* 0: counter 0 (keeps the base sample), 1: counter 1 (averages with ets[-1]), 2: multistep */
+    int32_t nterms;           /* mode 2: terms of the combination, 2..4 */
+    int32_t wslot;            /* history slot this step's guided prediction is stored in (-1: none, mode 1) */
+    int32_t rslot[3];         /* history slots of ets[-2], ets[-3], ets[-4] (mode 1: rslot[0] is ets[-1]) */
+    float coef[4];            /* mode 2: eps = form(coef[1], ets[-2], coef[0], ets[-1]), then form(coef[i], ets[-1-i], 1, eps) */
+    float v_x, v_v;           /* vpred: eps = form(v_x, base, v_v, eps)  (sqrt(1 - a_t), sqrt(a_t)) */
+    float eps_scale, x_scale; /* prev = form(eps_scale, eps, x_scale, base)  (-(a_prev - a_t) / denom, sqrt(a_prev / a_t)) */
+    int32_t vpred;            /* 1: v_prediction (the conversion follows the combination, on this step's base sample) */
+    int32_t pad_;
+} pdmk_plms_row;
+
+/* Guidance + PLMS step + next U-Net input.  pred: the engine's output, NHWC rows [(cfg ? 2B : B) * HW, ld] in dtype
+ * (CFG: the unconditional half first); guided = form(g_u, uncond, g_t, text) (g_u = 1 - guidance_scale, g_t =
+ * guidance_scale), or pred itself without CFG.  State (fp32, NCHW [B, C, HW] each): sample (the latents, updated in place
+ * to the previous sample), cur (the counter-0 base sample), ets (4 history slots).  state[0] is the step counter: the
+ * launch uses table[state[0]] and advances it (the last workgroup to finish; state[1] is its ticket, kept 0 between
+ * launches); with state[0] >= nsteps it does nothing.  t_out (int64 [cfg ? 2B : B]) receives table[step + 1].t, x_next
+ * ([(cfg ? 2B : B) * HW, cpad] in dtype) the new sample for both halves, padding channels 0 - as pdmk_nchw_to_nhwc
+ * writes them.  No host synchronisation: capturable and replayable nsteps times. */
+int pdmk_plms_step(const void* pred, int ld, float g_u, float g_t, int cfg, float* sample, float* cur, float* ets,
+                   const pdmk_plms_row* table, int nsteps, int32_t* state, int64_t* t_out, void* x_next, int cpad,
+                   int B, int C, int HW, int dtype, pdmk_stream stream);
+
+/* Image epilogue of generate_fid_images.py:141-151 (`(image / 2 + 0.5).clamp(0, 1)` of the diffusers image processor, then
+ * `.permute(0, 2, 3, 1).cpu().numpy()`, `img * 255`, `img.astype(np.uint8)`): fp32 NCHW [B, C, HW] in, uint8 NHWC out,
+ * truncated (not rounded); NaN gives 0. */
+int pdmk_image_to_u8(const float* src, uint8_t* dst, int B, int C, int HW, pdmk_stream stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Data-parallel gradient exchange: DDP's all-reduce inside accelerator.backward
  * (pdm/training/trainer.py:117-129, 2782, 2808) as RCCL all-reduces over xGMI behind an explicit communicator handle.
  * pdmk_comm_unique_id: rank 0 fills 128 bytes (ncclUniqueId) and hands them to the other ranks out of band (the Python

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Time the image-logging / FID sampler on one MI355X: B prompts, PNDM, CFG 7.5, 512 x 512, bf16, pruned
-student (MAC budget 0.55) + VAE decode.  Reports s / batch, images/s and the U-Net forward rate."""
+student (MAC budget 0.55) + VAE decode.  Reports s / batch, images/s and the U-Net forward rate.  --graph: the denoising
+loop as replays of the captured step (pdmk_plms_step), else the eager loop."""
 import argparse
 import os
 import sys
@@ -22,6 +23,8 @@ def main():
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--budget", type=float, default=0.55)
+    ap.add_argument("--graph", action="store_true", help="captured denoising loop (the capture happens in the warm-up)")
+    ap.add_argument("--reps", type=int, default=1, help="timed batches (the mean is reported)")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     cfg = UNetConfig.sd21()
@@ -33,15 +36,18 @@ def main():
     ids = torch.randint(0, 49408, (a.batch, 77), device=dev)
     empty = torch.zeros(a.batch, 77, dtype=torch.int64, device=dev)
     gen = torch.Generator(device=dev).manual_seed(0)
-    pipe(prompt_ids=ids, negative_prompt_ids=empty, num_inference_steps=2, generator=gen)          # warm-up: GEMM plans
+    pipe(prompt_ids=ids, negative_prompt_ids=empty, num_inference_steps=a.steps if a.graph else 2, generator=gen,
+         graph=a.graph)                                                       # warm-up: GEMM plans (and the capture)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    img = pipe(prompt_ids=ids, negative_prompt_ids=empty, num_inference_steps=a.steps, generator=gen, output_type="pt").images
+    for _ in range(a.reps):
+        img = pipe(prompt_ids=ids, negative_prompt_ids=empty, num_inference_steps=a.steps, generator=gen, output_type="pt",
+                   graph=a.graph).images
     torch.cuda.synchronize()
-    el = time.perf_counter() - t0
+    el = (time.perf_counter() - t0) / a.reps
     macs = plan_macs(cfg, unet.blocks, 64, 77)[0]
     calls = a.steps + 1
-    print(f"sampler B={a.batch} {a.steps} PNDM steps ({calls} U-Net calls on 2B), CFG 7.5, 512x512, bf16, budget {ratio:.3f}: "
+    print(f"sampler {'captured' if a.graph else 'eager'} B={a.batch} {a.steps} PNDM steps ({calls} U-Net calls on 2B), CFG 7.5, 512x512, bf16, budget {ratio:.3f}: "
           f"{el:.2f} s/batch = {a.batch / el:.2f} img/s; U-Net {2 * macs * 2 * a.batch * calls / el / 1e12:.0f} TFLOP/s incl. "
           f"text encode + VAE decode; image range [{img.min().item():.2f}, {img.max().item():.2f}]")
 

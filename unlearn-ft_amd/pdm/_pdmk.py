@@ -46,6 +46,12 @@ class GemmArgs(C.Structure):
                 ("ln_gamma", vp), ("ln_beta", vp), ("ln_stats", vp), ("ln_out", vp), ("ld_ln_out", i32), ("ln_eps", f32)]
 
 
+class PlmsRow(C.Structure):
+    """pdmk_plms_row (include/pdmk.h): one step of the fused guidance + PLMS update."""
+    _fields_ = [("t", i64), ("mode", i32), ("nterms", i32), ("wslot", i32), ("rslot", i32 * 3), ("coef", f32 * 4),
+                ("v_x", f32), ("v_v", f32), ("eps_scale", f32), ("x_scale", f32), ("vpred", i32), ("pad_", i32)]
+
+
 _SIGS = {
     "pdmk_version": ([], i32),
     "pdmk_gemm": ([C.POINTER(GemmArgs), vp], i32),
@@ -100,6 +106,8 @@ _SIGS = {
     "pdmk_attn_fwd_causal": ([vp, vp, vp, vp, vp, i32, i32, i32, i64, i32, i64, i32, i64, i32, i64, i32, f32, i32, vp], i32),
     "pdmk_gelu_fwd": ([vp, vp, i64, i32, vp], i32),
     "pdmk_image_prep": ([vp, i64, vp, vp, i32, i32, vp, vp], i32),
+    "pdmk_plms_step": ([vp, i32, f32, f32, i32, vp, vp, vp, vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, vp], i32),
+    "pdmk_image_to_u8": ([vp, vp, i32, i32, i32, vp], i32),
     "pdmk_gemm_splitk_workspace_bytes": ([i64, i32, i32], i64),
     "pdmk_groupnorm_workspace_bytes": ([i32, i32], i64),
     "pdmk_groupnorm_bwd_part_workspace_bytes": ([i32, i32], i64),
@@ -909,6 +917,37 @@ def image_prep(src, desc, desc_dev, out):
             or not out.is_contiguous()):
         raise PdmkError("image_prep: src uint8, desc int64 [B, 8] on the host, desc_dev its device copy, out fp32 [B, 3, R, R]")
     _chk(_lib.pdmk_image_prep(_p(src), src.numel(), _p(desc), _p(desc_dev), B, R, _p(out), _st()), "pdmk_image_prep")
+
+
+def plms_table(rows, device):
+    """A list of PlmsRow -> the uint8 device tensor pdmk_plms_step reads (one host-to-device copy)."""
+    arr = (PlmsRow * len(rows))(*rows)
+    return torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(device)
+
+
+def plms_step(pred, ld, g_u, g_t, cfg, sample, cur, ets, table, nsteps, state, t_out, x_next, cpad, B, Cc, HW):
+    """One fused guidance + PLMS step (include/pdmk.h pdmk_plms_step).  pred / x_next in the engine dtype; sample, cur
+    fp32 [B*Cc*HW]; ets fp32 [4, B*Cc*HW]; table from plms_table() with nsteps rows; state int32 [2]; t_out int64."""
+    n = B * Cc * HW
+    rows = (2 * B if cfg else B) * HW
+    avail = pred.untyped_storage().nbytes() // pred.element_size() - pred.storage_offset()     # (pred may be a strided view)
+    if (pred.dtype != x_next.dtype or avail < (rows - 1) * ld + Cc or x_next.numel() < rows * cpad
+            or any(t.dtype != torch.float32 or not t.is_contiguous() for t in (sample, cur, ets))
+            or sample.numel() != n or cur.numel() != n or ets.numel() != 4 * n or table.dtype != torch.uint8
+            or table.numel() != nsteps * C.sizeof(PlmsRow) or state.dtype != torch.int32 or state.numel() != 2
+            or t_out.dtype != torch.int64 or t_out.numel() < (2 * B if cfg else B)):
+        raise PdmkError("plms_step: inconsistent buffers")
+    _chk(_lib.pdmk_plms_step(_p(pred), ld, float(g_u), float(g_t), int(bool(cfg)), _p(sample), _p(cur), _p(ets), _p(table),
+                             nsteps, _p(state), _p(t_out), _p(x_next), cpad, B, Cc, HW, dt(pred), _st()), "pdmk_plms_step")
+
+
+def image_to_u8(src, dst):
+    """uint8 NHWC dst [B, H, W, C] = trunc(255 * clamp(src / 2 + 0.5, 0, 1)) of the fp32 NCHW decoder output src."""
+    B, Cc, H, W = src.shape
+    if (src.dtype != torch.float32 or not src.is_contiguous() or dst.dtype != torch.uint8 or not dst.is_contiguous()
+            or tuple(dst.shape) != (B, H, W, Cc)):
+        raise PdmkError("image_to_u8: src fp32 contiguous [B, C, H, W], dst uint8 contiguous [B, H, W, C]")
+    _chk(_lib.pdmk_image_to_u8(_p(src), _p(dst), B, Cc, H * W, _st()), "pdmk_image_to_u8")
 
 
 def softmax_rows(s, p, rows, cols, lds, ldp):

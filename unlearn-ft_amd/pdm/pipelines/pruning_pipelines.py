@@ -4,15 +4,26 @@ Mirror of pdm/pipelines/pruning_pipelines.py:867-1010 as scripts/metrics/generat
 PNDM (PLMS, skip_prk_steps) scheduler, classifier-free guidance on a doubled batch, `vae.decode(latents /
 scaling_factor)`, `image / 2 + 0.5` clamped to [0, 1].  Models are this package's `UNet2DConditionModelPruned`,
 `AutoencoderKL`, `CLIPTextModel`; the scheduler's per-step latent arithmetic runs in `pdmk_axpby` (fp32), its scalar
-coefficients on the host in float64 like diffusers.  Prompts come as token ids or embeddings (tokenisation is host-side
-data preparation).  The safety checker of the diffusers base class is not reproduced (the reference's FID script keeps
-every image).  Scheduler parity is "unpinned" (diffusers absent, no vendored twin): see oracle/pdm_ref/sampler.py.
+coefficients on the host in float64 like diffusers.  Prompts come as token ids, embeddings or - with a tokenizer - strings.
+The safety checker of the diffusers base class is not reproduced (the reference's FID script keeps every image).
+Scheduler parity is "unpinned" (diffusers absent, no vendored twin): see oracle/pdm_ref/sampler.py.
+
+The denoising loop runs as replays of a captured graph (`_CapturedLoop`) when it can: one U-Net forward on static buffers
+followed by pdmk_plms_step, which does the guidance, the PLMS update and the next U-Net input in one launch, advances a
+device-side step counter and refreshes the U-Net's timestep buffer from a step table - so one capture serves every step.
+It is bit-identical to the eager loop (the kernel repeats pdmk_axpby's fp32 arithmetic operation by operation; DESIGN.md
+9.1).  `callback=`, block hooks, another scheduler class or PDMK_SAMPLER_GRAPH=0 select the eager loop.
 """
+import ctypes
+import gc
+import json
+import os
 from types import SimpleNamespace
 
 import torch
 
 from .. import _pdmk as k
+from ..models.unet.spec import padc
 
 
 class PNDMScheduler:
@@ -20,6 +31,10 @@ class PNDMScheduler:
     set_alpha_to_one False, scaled_linear betas)."""
     order = 1
     init_noise_sigma = 1.0
+    # scheduler_config.json keys whose value this class does not implement otherwise: the value it implements
+    _FIXED = {"beta_schedule": "scaled_linear", "skip_prk_steps": True, "set_alpha_to_one": False, "trained_betas": None,
+              "clip_sample": False, "timestep_spacing": "leading"}
+    _FREE = ("num_train_timesteps", "beta_start", "beta_end", "steps_offset", "prediction_type")
 
     def __init__(self, num_train_timesteps=1000, beta_start=0.00085, beta_end=0.012, steps_offset=1,
                  prediction_type="epsilon"):
@@ -29,6 +44,28 @@ class PNDMScheduler:
         self.config = SimpleNamespace(num_train_timesteps=num_train_timesteps, steps_offset=steps_offset,
                                       prediction_type=prediction_type, skip_prk_steps=True)
         self.timesteps = None
+
+    @classmethod
+    def from_config(cls, config):
+        """From a diffusers scheduler_config.json dict (or its path).  Keys starting with "_" are ignored; a value this
+        class does not implement (PRK steps, another beta schedule, set_alpha_to_one, ...) or an unknown key raises."""
+        if isinstance(config, str):
+            with open(config) as f:
+                config = json.load(f)
+        kw = {}
+        for key, v in config.items():
+            if key.startswith("_"):
+                continue
+            if key in cls._FIXED:
+                if v != cls._FIXED[key]:
+                    raise ValueError(f"PNDMScheduler: {key}={v!r} is not implemented (only {cls._FIXED[key]!r})")
+            elif key in cls._FREE:
+                kw[key] = v
+            else:
+                raise ValueError(f"PNDMScheduler: config key {key!r} is not implemented")
+        if kw.get("prediction_type", "epsilon") not in ("epsilon", "v_prediction"):
+            raise ValueError(f"PNDMScheduler: prediction_type={kw['prediction_type']!r} is not implemented")
+        return cls(**kw)
 
     def set_timesteps(self, num_inference_steps, device=None):
         self.num_inference_steps = num_inference_steps
@@ -63,26 +100,157 @@ class PNDMScheduler:
             for i in range(2, len(e)):
                 k.axpby(e[-1 - i], mo, coef[i], 1.0)
         self.counter += 1
+        v_x, v_v, eps_scale, x_scale = self._scalars(t, prev_t)
+        if self.config.prediction_type == "v_prediction":
+            k.axpby(sample, mo, v_x, v_v)                                  # eps = sqrt(a) v + sqrt(1 - a) x
+        prev = sample.clone()
+        k.axpby(mo, prev, eps_scale, x_scale)                              # coeff * sample - (a_prev - a_t) eps / denom
+        return SimpleNamespace(prev_sample=prev) if return_dict else (prev,)
+
+    def _scalars(self, t, prev_t):
+        """The step's coefficients (float64, then Python floats; fp32 where a kernel takes them): the v -> eps conversion
+        (sqrt(1 - a_t), sqrt(a_t)) and prev = x_scale * sample + eps_scale * eps."""
+        if self.config.prediction_type not in ("epsilon", "v_prediction"):
+            raise ValueError(f"prediction_type {self.config.prediction_type!r} must be epsilon or v_prediction")
         a_t = self.alphas_cumprod[t]
         a_prev = self.alphas_cumprod[prev_t] if prev_t >= 0 else self.final_alpha_cumprod
         b_t, b_prev = 1 - a_t, 1 - a_prev
-        if self.config.prediction_type == "v_prediction":
-            k.axpby(sample, mo, float(b_t.sqrt()), float(a_t.sqrt()))     # eps = sqrt(a) v + sqrt(1 - a) x
-        elif self.config.prediction_type != "epsilon":
-            raise ValueError(f"prediction_type {self.config.prediction_type!r} must be epsilon or v_prediction")
         coeff = float((a_prev / a_t).sqrt())
         denom = float(a_t * b_prev.sqrt() + (a_t * b_t * a_prev).sqrt())
-        prev = sample.clone()
-        k.axpby(mo, prev, -float(a_prev - a_t) / denom, coeff)            # coeff * sample - (a_prev - a_t) eps / denom
-        return SimpleNamespace(prev_sample=prev) if return_dict else (prev,)
+        return float(b_t.sqrt()), float(a_t.sqrt()), -float(a_prev - a_t) / denom, coeff
+
+    def plms_rows(self):
+        """The schedule of set_timesteps() as pdmk_plms_row entries: what step() does at each index, its history (`ets`,
+        at most 4 entries) kept in 4 ring slots.  The scalars are step()'s own (_scalars)."""
+        ratio = self.config.num_train_timesteps // self.num_inference_steps
+        coefs = {2: (3 / 2, -1 / 2), 3: (23 / 12, -16 / 12, 5 / 12), 4: (55 / 24, -59 / 24, 37 / 24, -9 / 24)}
+        rows, appended = [], 0                        # appended: entries ever added to ets (step() skips counter 1)
+        for i, t in enumerate(self.timesteps.tolist()):
+            r = k.PlmsRow(t=int(t), vpred=int(self.config.prediction_type == "v_prediction"))
+            prev_t = t - ratio
+            if i == 1:
+                prev_t, t = t, t + ratio
+                r.mode, r.wslot, r.nterms = 1, -1, 1
+                r.rslot[0] = (appended - 1) % 4
+                r.coef[0] = r.coef[1] = 0.5
+            else:
+                r.wslot = appended % 4
+                appended += 1
+                r.nterms = min(appended, 4)
+                r.mode = 0 if i == 0 else 2
+                for j in range(3):
+                    r.rslot[j] = (appended - 2 - j) % 4
+                if r.mode == 2:
+                    for j, c in enumerate(coefs[r.nterms]):
+                        r.coef[j] = c
+            r.v_x, r.v_v, r.eps_scale, r.x_scale = self._scalars(t, prev_t)
+            rows.append(r)
+        return rows
+
+
+class _CapturedLoop:
+    """The denoising loop of one (batch, H, W, dtype, CFG, steps, text shape, guidance) as replays of ONE single-stream
+    captured graph (GraphedBilevel's docstring: graphs with parallel branches are not used): the U-Net forward over static
+    buffers, then pdmk_plms_step, which writes the next U-Net input and timesteps itself and advances the step counter.
+    The same graph is replayed once per U-Net call (N + 1 calls for N PLMS steps)."""
+
+    def __init__(self, unet, B, h, w, cfg_on, guidance_scale, nsteps, T, ctx):
+        dev, dt = unet.device, unet.dtype
+        self.unet, self.B, self.C, self.h, self.w, self.cfg_on, self.nsteps = unet, B, unet.cfg.in_channels, h, w, cfg_on, nsteps
+        self.g = (float(1.0 - guidance_scale), float(guidance_scale))       # axpby(out[:B], out[B:], 1 - g, g)
+        self.R, self.cp = (2 * B if cfg_on else B), padc(self.C)
+        n = B * self.C * h * w
+        self.x = torch.zeros((self.R * h * w, self.cp), device=dev, dtype=dt)
+        self.t = torch.zeros(self.R, device=dev, dtype=torch.int64)
+        self.ehs = torch.zeros((self.R * T, ctx), device=dev, dtype=dt)
+        self.sample = torch.zeros(n, device=dev)
+        self.cur = torch.zeros(n, device=dev)
+        self.ets = torch.zeros(4, n, device=dev)
+        self.state = torch.zeros(2, device=dev, dtype=torch.int32)
+        self.table = torch.zeros(nsteps * ctypes.sizeof(k.PlmsRow), device=dev, dtype=torch.uint8)
+        self.graph, self.keep = None, []
+        self._capture()
+
+    def _body(self):
+        pred, _ = self.unet.forward_nhwc(self.x, self.t, self.ehs, self.R, self.h, self.w, train=False)
+        k.plms_step(pred.t, pred.t.stride(0), *self.g, self.cfg_on, self.sample, self.cur, self.ets, self.table, self.nsteps,
+                    self.state, self.t, self.x, self.cp, self.B, self.C, self.h * self.w)
+        return pred
+
+    def _capture(self):
+        dev = self.x.device
+        # eager warm-up of the same body (plans the GEMMs of these shapes on random operands and sizes the engine's arenas;
+        # the counter is past the end, so the PLMS launch does nothing)
+        gen = torch.Generator(device=dev).manual_seed(1234)
+        self.x[:, :self.C].normal_(generator=gen)
+        self.ehs.normal_(generator=gen)
+        self.t.fill_(500)
+        self.state.fill_(self.nsteps)
+        cap = k.role_stream(dev, "capture")
+        cap.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(cap):
+            self._body()
+        torch.cuda.current_stream().wait_stream(cap)
+        torch.cuda.synchronize()
+        # like torch.cuda.graph(): collect garbage first and keep the collector off while capturing
+        gc.collect()
+        gc_was_on = gc.isenabled()
+        gc.disable()
+        self.graph = torch.cuda.CUDAGraph()
+        cap.wait_stream(torch.cuda.current_stream())
+        try:
+            with torch.cuda.stream(cap):
+                self.graph.capture_begin(capture_error_mode="thread_local")
+                try:
+                    pred = self._body()
+                finally:
+                    self.graph.capture_end()
+        finally:
+            if gc_was_on:
+                gc.enable()
+        torch.cuda.current_stream().wait_stream(cap)
+        torch.cuda.synchronize()
+        eng = self.unet.engine          # what the graph reads or writes beyond its own pool stays allocated
+        self.keep = [pred, eng.ws, getattr(eng, "_cs_arena", None)]
+
+    def run(self, latents, ehs, rows):
+        """latents: fp32 [B, C, h, w] (contiguous, on the device); ehs: [R, T, ctx] text embeddings (unconditional half
+        first); rows: the scheduler's plms_rows().  Returns the final latents (a new tensor)."""
+        B, C, HW = self.B, self.C, self.h * self.w
+        self.ehs.copy_(ehs.reshape(self.ehs.shape))                       # the batch's one cast of the text embeddings
+        self.table.copy_(torch.frombuffer(bytearray(bytes((k.PlmsRow * len(rows))(*rows))), dtype=torch.uint8))
+        self.sample.copy_(latents.reshape(-1))
+        k.nchw_to_nhwc(latents, self.x, B, C, HW, self.cp)
+        if self.cfg_on:
+            k.nchw_to_nhwc(latents, self.x[B * HW:], B, C, HW, self.cp)
+        self.t.fill_(rows[0].t)
+        self.state.zero_()
+        for _ in range(self.nsteps):
+            self.graph.replay()
+        return self.sample.view(B, C, self.h, self.w).clone()
+
+    def close(self):
+        torch.cuda.synchronize()
+        self.graph, self.keep = None, []
 
 
 class StableDiffusionPruningPipeline:
+    GRAPH_SHAPES = 3           # captured loops kept (least recently used evicted first), like training.hip_graph_shapes
+
     def __init__(self, vae, text_encoder, unet, scheduler=None, tokenizer=None):
         self.vae, self.text_encoder, self.unet, self.tokenizer = vae, text_encoder, unet, tokenizer
         self.scheduler = scheduler or PNDMScheduler()
         self.vae_scale_factor = 2 ** (len(vae.cfg.block_out_channels) - 1)
         self.device = unet.device
+        self._loops = {}
+        self.captures = 0          # loops captured so far (tests)
+
+    def _tokenize(self, prompt):
+        if self.tokenizer is None:
+            raise ValueError("string prompts need a tokenizer: pass prompt_ids / prompt_embeds, or build the pipeline with "
+                             "tokenizer=")
+        from ..utils.data import tokenize
+        return tokenize(self.tokenizer, [prompt] if isinstance(prompt, str) else list(prompt)).to(self.device)
 
     def encode_prompt(self, prompt_ids=None, negative_prompt_ids=None, prompt_embeds=None, negative_prompt_embeds=None,
                       do_classifier_free_guidance=True):
@@ -97,11 +265,45 @@ class StableDiffusionPruningPipeline:
             negative_prompt_embeds = self.text_encoder(negative_prompt_ids)[0]
         return prompt_embeds, negative_prompt_embeds
 
+    def _use_graph(self, graph, callback):
+        if graph is False or callback is not None or type(self.scheduler) is not PNDMScheduler:
+            return False
+        u = self.unet
+        blocks = list(getattr(u, "down_blocks", [])) + [getattr(u, "mid_block", None)] + list(getattr(u, "up_blocks", []))
+        if any(getattr(b, "_hooks", None) for b in blocks):            # block hooks fire in the eager U-Net call only
+            return False
+        return graph is True or os.environ.get("PDMK_SAMPLER_GRAPH", "1") != "0"
+
+    def _loop(self, B, h, w, cfg_on, guidance_scale, nsteps, T, ctx):
+        key = (B, h, w, self.unet.dtype, cfg_on, nsteps, T, ctx, float(guidance_scale))
+        loop = self._loops.pop(key, None)
+        if loop is None:
+            while len(self._loops) >= self.GRAPH_SHAPES:
+                self._loops.pop(next(iter(self._loops))).close()
+            loop = _CapturedLoop(self.unet, B, h, w, cfg_on, guidance_scale, nsteps, T, ctx)
+            self.captures += 1
+        self._loops[key] = loop                                       # most recently used last
+        return loop
+
     @torch.no_grad()
     def generate_samples(self, prompt_ids=None, height=None, width=None, num_inference_steps=50, guidance_scale=7.5,
                          negative_prompt_ids=None, generator=None, latents=None, prompt_embeds=None,
-                         negative_prompt_embeds=None, output_type="np", return_dict=True, callback=None, callback_steps=1):
+                         negative_prompt_embeds=None, output_type="np", return_dict=True, callback=None, callback_steps=1,
+                         prompt=None, negative_prompt=None, graph=None):
+        """prompt / negative_prompt: strings or lists of strings (needs the tokenizer; with guidance and no negative prompt
+        the empty prompt).  output_type "latent", "pt", "np" (float32 NHWC in [0, 1]) or "u8" (uint8 NHWC numpy, the FID
+        script's `(img * 255).astype(np.uint8)`, formed on the device).  graph: None = the captured loop when possible
+        (PDMK_SAMPLER_GRAPH=0 turns it off), False = the eager loop, True = captured whenever possible."""
         cfg_on = guidance_scale > 1.0
+        if isinstance(prompt_ids, (str, list, tuple)):            # the reference's positional `prompt`
+            prompt, prompt_ids = prompt_ids, None
+        if prompt is not None and prompt_ids is None and prompt_embeds is None:
+            prompt_ids = self._tokenize(prompt)
+        if cfg_on and negative_prompt_ids is None and negative_prompt_embeds is None and (
+                negative_prompt is not None or (prompt is not None and self.tokenizer is not None)):
+            n = prompt_ids.shape[0] if prompt_ids is not None else prompt_embeds.shape[0]
+            neg = negative_prompt if negative_prompt is not None else ""
+            negative_prompt_ids = self._tokenize([neg] * n if isinstance(neg, str) else neg)
         prompt_embeds, negative_prompt_embeds = self.encode_prompt(prompt_ids, negative_prompt_ids, prompt_embeds,
                                                                    negative_prompt_embeds, cfg_on)
         B = prompt_embeds.shape[0]
@@ -111,6 +313,8 @@ class StableDiffusionPruningPipeline:
         height, width = height or 64 * f, width or 64 * f     # unet.config.sample_size * vae_scale_factor at 512 px
         if height % f or width % f:
             raise ValueError(f"`height` and `width` have to be divisible by {f} but are {height} and {width}.")
+        if output_type not in ("latent", "pt", "np", "u8"):
+            raise ValueError("output_type must be 'latent', 'pt', 'np' or 'u8' (PIL conversion is left to the caller)")
         dev = self.device
         ehs = torch.cat([negative_prompt_embeds.to(dev), prompt_embeds.to(dev)]) if cfg_on else prompt_embeds.to(dev)
         sch = self.scheduler
@@ -120,6 +324,28 @@ class StableDiffusionPruningPipeline:
         if latents is None:
             latents = torch.randn(shape, device=dev, dtype=torch.float32, generator=generator)
         latents = (latents.to(dev, torch.float32) * sch.init_noise_sigma).contiguous()
+        if self._use_graph(graph, callback):
+            loop = self._loop(B, shape[2], shape[3], cfg_on, guidance_scale, len(sch.timesteps), ehs.shape[1], ehs.shape[2])
+            latents = loop.run(latents, ehs, sch.plms_rows())
+        else:
+            latents = self._eager_loop(latents, ehs, B, shape, cfg_on, guidance_scale, callback, callback_steps)
+        if output_type == "latent":
+            image = latents
+        else:
+            image = self.vae.decode(latents / self.vae.cfg.scaling_factor, return_dict=False)[0]
+            if output_type == "u8":
+                b, c, hh, ww = image.shape
+                u8 = torch.empty((b, hh, ww, c), device=image.device, dtype=torch.uint8)
+                k.image_to_u8(image.contiguous(), u8)
+                image = u8.cpu().numpy()
+            else:
+                image = (image / 2 + 0.5).clamp(0, 1)                     # VaeImageProcessor.postprocess (denormalize)
+                if output_type == "np":
+                    image = image.permute(0, 2, 3, 1).cpu().numpy()
+        return SimpleNamespace(images=image, nsfw_content_detected=None) if return_dict else (image, None)
+
+    def _eager_loop(self, latents, ehs, B, shape, cfg_on, guidance_scale, callback, callback_steps):
+        dev, sch = self.device, self.scheduler
         was_training = self.unet.training
         self.unet.eval()
         try:
@@ -140,15 +366,6 @@ class StableDiffusionPruningPipeline:
                     callback(i, t, latents)
         finally:
             self.unet.train(was_training)
-        if output_type == "latent":
-            image = latents
-        else:
-            image = self.vae.decode(latents / self.vae.cfg.scaling_factor, return_dict=False)[0]
-            image = (image / 2 + 0.5).clamp(0, 1)                         # VaeImageProcessor.postprocess (denormalize)
-            if output_type == "np":
-                image = image.permute(0, 2, 3, 1).cpu().numpy()
-            elif output_type != "pt":
-                raise ValueError("output_type must be 'latent', 'pt' or 'np' (PIL conversion is left to the caller)")
-        return SimpleNamespace(images=image, nsfw_content_detected=None) if return_dict else (image, None)
+        return latents
 
     __call__ = generate_samples

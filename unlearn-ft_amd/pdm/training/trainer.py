@@ -436,7 +436,7 @@ class Trainer:
                 if src in batch:
                     kw[dst] = batch[src]
             images.append(pipe.generate_samples(num_inference_steps=steps, generator=gen, output_type="pt", height=res,
-                                                width=res, **kw).images)
+                                                width=res, graph=False, **kw).images)       # (eager: no capture per log)
         images = torch.cat(images)
         if self.rank == 0:
             d = os.path.join(self.logging_dir, "images")

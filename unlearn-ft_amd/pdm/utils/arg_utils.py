@@ -39,6 +39,8 @@ def parse_args(argv=None):
     p.add_argument("--hip_graphs", action="store_true", help="replay the training step as captured hipGraphs (fixed batch shapes)")
     p.add_argument("--teacher_prefetch", action="store_true",
                    help="with --hip_graphs: look one batch ahead, the frozen teacher's pass over it runs beside this step's backward")
+    p.add_argument("--image_resolution", type=int, default=512,
+                   help="scripts/metrics/generate_fid_images.py: side of the generated images (the reference: 512)")
     args = p.parse_args(argv)
     env_local_rank = int(os.environ.get("LOCAL_RANK", -1))
     if env_local_rank != -1 and env_local_rank != args.local_rank:
