@@ -448,6 +448,39 @@ typedef struct {
 } pdmk_image_desc;
 int pdmk_image_prep(const uint8_t* src, int64_t src_bytes, const pdmk_image_desc* desc, const pdmk_image_desc* desc_dev,
                     int B, int R, float* out, pdmk_stream stream);
+/* pdmk_image_prep with the resample filter and the normalisation as parameters - CLIP's evaluation transform (Resize(R,
+ * BICUBIC), CenterCrop(R), ToTensor, Normalize(mean, std)) is filter = 1 with CLIP's mean / std.
+ * filter 0: bilinear (pdmk_image_prep is this entry with mean = std = 0.5, same bits); 1: Pillow's 8-bpc bicubic (cubic
+ *   kernel a = -0.5, support 2 x filterscale, negative fixed-point weights rounded as int(-0.5 + w * 2^22), the horizontal
+ *   pass clipped to uint8 before the vertical pass).
+ * mean, stdv: 3 floats each in HOST memory; out = (x / 255 - mean[c]) / stdv[c] in fp32.
+ * -1 as pdmk_image_prep, and also on another filter, a zero stdv, or a downscale above 63x with filter 1 (the vertical taps
+ *   of one output row, 4 * ceil(in / out) + 1, must fit the kernel's 256-entry table; bilinear keeps its 127x). */
+int pdmk_image_prep_ex(const uint8_t* src, int64_t src_bytes, const pdmk_image_desc* desc, const pdmk_image_desc* desc_dev,
+                       int B, int R, int filter, const float* mean, const float* stdv, float* out, pdmk_stream stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * CLIP score (pdm/utils/clip_utils.py): OpenAI CLIP ViT image tower and text tower, then the cosine of the two projected
+ * features.  LayerNorm, Linear (q|k|v fused, residuals in the epilogues), attention and the token + position gather run on
+ * the entry points above; these are the pieces with no other counterpart.  All in `dtype` unless stated.
+ * pdmk_patch_im2col: x fp32 NCHW [B, 3, S, S] (S % p == 0, g = S / p) -> out [B * g * g, ldo]: row (b, gy, gx), column
+ *   (c, ky, kx) = x[b, c, gy * p + ky, gx * p + kx]; columns 3 * p * p .. ldo - 1 are written 0.  The conv weight
+ *   [E, 3, p, p] read as [E, 3 * p * p] is then a plain Linear weight (no bias).
+ * pdmk_vit_tokens: out [B * (G2 + 1), ldo]: row b * (G2 + 1) is cls + pos[0], row b * (G2 + 1) + 1 + i is
+ *   patches[b * G2 + i] + pos[1 + i] (cls [E]; pos row stride ldpos, patches ldp).
+ * pdmk_quick_gelu_fwd: y = x * sigmoid(1.702 x) (hidden_act "quick_gelu") over n contiguous elements.
+ * pdmk_gather_rows: out[b, 0:D] = x[b * T + j, 0:D] with j = 0 when ids is NULL (the CLS row) and else the position of the
+ *   first maximum of ids[b, 0:T] (int64 on the device: the EOT token, as OpenAI CLIP pools); no host synchronisation.
+ * pdmk_clip_score_head: fp32 rows a [B, D] (row stride lda) and b (ldb): an = a / |a|, bn = b / |b| (contiguous [B, D], each
+ *   optional), *acc += sum_r an[r] . bn[r] in fp64 (optional; the caller zeroes it).  b NULL: normalise a into an only. */
+int pdmk_patch_im2col(const float* x, void* out, int B, int S, int p, int ldo, int dtype, pdmk_stream stream);
+int pdmk_vit_tokens(const void* patches, int ldp, const void* cls, const void* pos, int ldpos, void* out, int ldo, int B,
+                    int G2, int E, int dtype, pdmk_stream stream);
+int pdmk_quick_gelu_fwd(const void* x, void* y, int64_t n, int dtype, pdmk_stream stream);
+int pdmk_gather_rows(const void* x, int ldx, const int64_t* ids, int T, void* out, int ldo, int B, int D, int dtype,
+                     pdmk_stream stream);
+int pdmk_clip_score_head(const float* a, int lda, const float* b, int ldb, float* an, float* bn, double* acc, int B, int D,
+                         pdmk_stream stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Sampler (csrc/sampler.hip): what the eager denoising loop of StableDiffusionPruningPipeline.generate_samples does

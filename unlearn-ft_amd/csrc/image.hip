@@ -1,13 +1,14 @@
-// pdmk_image_prep: the training transform of the image-caption loader (Resize(R, BILINEAR) -> CenterCrop / RandomCrop ->
-// optional horizontal flip -> ToTensor -> Normalize(0.5, 0.5)) over a ragged batch of decoded 8-bit RGB images, bit-exact
-// with Pillow's 8-bpc two-pass resample (libImaging/Resample.c, Pillow >= 7):
-//   * per output coordinate: scale = in / out, filterscale = max(scale, 1), support = filterscale (triangle filter),
-//     center = (xx + 0.5) * scale, taps [int(center - support + 0.5), int(center + support + 0.5)) clipped to the input,
-//     w_i = tri((i + xmin - center + 0.5) * (1 / filterscale)), normalised by their sequential double sum, then
-//     k_i = int(0.5 + w_i * 2^22);
-//   * horizontal pass: (2^21 + sum_i px * k_i) >> 22, clipped to [0, 255] (uint8 intermediate); vertical pass likewise
-//     over the intermediate rows;
-//   * x / 255 then (x - 0.5) / 0.5 in fp32.
+// pdmk_image_prep / pdmk_image_prep_ex: the training transform of the image-caption loader (Resize(R, BILINEAR) ->
+// CenterCrop / RandomCrop -> optional horizontal flip -> ToTensor -> Normalize(0.5, 0.5)) and CLIP's evaluation transform
+// (Resize(R, BICUBIC) -> CenterCrop -> ToTensor -> Normalize(mean, std)) over a ragged batch of decoded 8-bit RGB images,
+// bit-exact with Pillow's 8-bpc two-pass resample (libImaging/Resample.c, Pillow >= 7):
+//   * per output coordinate: scale = in / out, filterscale = max(scale, 1), support = filterscale (triangle filter) or
+//     2 * filterscale (cubic, a = -0.5), center = (xx + 0.5) * scale, taps [int(center - support + 0.5),
+//     int(center + support + 0.5)) clipped to the input, w_i = filter((i + xmin - center + 0.5) * (1 / filterscale)),
+//     normalised by their sequential double sum, then k_i = int(0.5 + w_i * 2^22) (int(-0.5 + w_i * 2^22) for w_i < 0);
+//   * horizontal pass: (2^21 + sum_i px * k_i) >> 22, clipped to [0, 255] (uint8 intermediate; cubic sums can leave the
+//     range on both sides); vertical pass likewise over the intermediate rows;
+//   * x / 255 then (x - mean_c) / std_c in fp32 (divided, not multiplied by a reciprocal).
 // Every double / float operation above is written out in the order Pillow / torch perform it; FP contraction is off for this
 // file (an FMA would change the rounding of `center` or of the fixed-point coefficients, and with it the output bits).
 //
@@ -15,7 +16,9 @@
 // source rows [ymin(first row), ymax(last row)); their horizontal pass (only the R columns of the crop) goes to LDS as uint8,
 // in chunks of STAGE_BYTES when a large downscale needs more rows than fit, and each thread accumulates the vertical sums of
 // its (row, column) outputs in registers across the chunks.  Source reads are aligned 4-byte loads; neighbouring threads
-// read neighbouring words of the same row.
+// read neighbouring words of the same row.  The vertical taps of one output row are held in LDS (KVMAX): the triangle filter
+// needs at most 2 * ceil(in / out) + 1 of them, the cubic one 4 * ceil(in / out) + 1, so the largest downscale is 127x for
+// bilinear and 63x for bicubic.
 #include "common.h"
 
 #pragma clang fp contract(off)
@@ -25,7 +28,7 @@ namespace {
 constexpr int NT = 256;
 constexpr int BAND = 4;                 // output rows per workgroup
 constexpr int RMAX = 1024;              // largest output side
-constexpr int KVMAX = 256;              // vertical taps per output row: downscale <= 127x
+constexpr int KVMAX = 256;              // vertical taps per output row: downscale <= 127x bilinear, <= 63x bicubic
 constexpr int STAGE_BYTES = 24 * 1024;  // horizontal-pass rows staged in LDS (uint8, [row][channel][column])
 constexpr int PB = 22;                  // PRECISION_BITS
 
@@ -33,16 +36,25 @@ __device__ __forceinline__ double tri(double x) {
     if (x < 0.0) x = -x;
     return x < 1.0 ? 1.0 - x : 0.0;
 }
+// Pillow's bicubic_filter, a = -0.5, in its operation order
+__device__ __forceinline__ double cubic(double x) {
+    const double a = -0.5;
+    if (x < 0.0) x = -x;
+    if (x < 1.0) return ((a + 2.0) * x - (a + 3.0)) * x * x + 1;
+    if (x < 2.0) return (((x - 5) * x + 8) * x - 4) * a;
+    return 0.0;
+}
 
 // Pillow's precompute_coeffs for one output coordinate xx: first tap, tap count, the filter centre and the weight sum
 struct Axis {
     double scale, fs, support, ss;
 };
+template <bool CUBIC>
 __device__ __forceinline__ Axis make_axis(int in, int out) {
     Axis a;
     a.scale = (double)in / (double)out;
     a.fs = a.scale < 1.0 ? 1.0 : a.scale;
-    a.support = 1.0 * a.fs;
+    a.support = (CUBIC ? 2.0 : 1.0) * a.fs;
     a.ss = 1.0 / a.fs;
     return a;
 }
@@ -54,13 +66,15 @@ __device__ __forceinline__ void tap_range(const Axis& a, int in, int xx, double&
     if (xmax > in) xmax = in;
     cnt = xmax - xmin;
 }
+template <bool CUBIC>
 __device__ __forceinline__ double weight(const Axis& a, int i, int xmin, double center) {
-    return tri(((double)(i + xmin) - center + 0.5) * a.ss);
+    const double x = ((double)(i + xmin) - center + 0.5) * a.ss;
+    return CUBIC ? cubic(x) : tri(x);
 }
-// normalize_coeffs_8bpc (bilinear weights are never negative)
+// normalize_coeffs_8bpc: negative (cubic) weights round towards -inf by half a step
 __device__ __forceinline__ int fixed_coeff(double w, double ww) {
     if (ww != 0.0) w = w / ww;
-    return (int)(0.5 + w * (double)(1 << PB));
+    return w < 0 ? (int)(-0.5 + w * (double)(1 << PB)) : (int)(0.5 + w * (double)(1 << PB));
 }
 __device__ __forceinline__ int clip8(int v) {
     v >>= PB;
@@ -82,9 +96,13 @@ struct Bytes {
     }
 };
 
-template <int PER>
+struct Norm3 {
+    float mean[3], stdv[3];
+};
+
+template <int PER, bool CUBIC>
 __global__ __launch_bounds__(NT) void image_prep_kernel(const uint8_t* __restrict__ src, const pdmk_image_desc* __restrict__ descs,
-                                                        int R, float* __restrict__ out) {
+                                                        int R, Norm3 nm, float* __restrict__ out) {
     __shared__ double h_center[RMAX], h_ww[RMAX];
     __shared__ int h_min[RMAX], h_cnt[RMAX];
     __shared__ int v_k[BAND][KVMAX];
@@ -96,7 +114,7 @@ __global__ __launch_bounds__(NT) void image_prep_kernel(const uint8_t* __restric
     const int nb = R - y0 < BAND ? R - y0 : BAND;            // output rows of this band
     const pdmk_image_desc d = descs[img];
     const int H = (int)d.h, W = (int)d.w, RH = (int)d.rh, RW = (int)d.rw, top = (int)d.top, left = (int)d.left;
-    const Axis ax = make_axis(W, RW), ay = make_axis(H, RH);
+    const Axis ax = make_axis<CUBIC>(W, RW), ay = make_axis<CUBIC>(H, RH);
 
     // horizontal coefficients of the R crop columns: the weight sum is a sequential double sum, one thread per column
     for (int x = threadIdx.x; x < R; x += NT) {
@@ -104,7 +122,7 @@ __global__ __launch_bounds__(NT) void image_prep_kernel(const uint8_t* __restric
         int m, n;
         tap_range(ax, W, left + x, c, m, n);
         double ww = 0.0;
-        for (int i = 0; i < n; ++i) ww += weight(ax, i, m, c);
+        for (int i = 0; i < n; ++i) ww += weight<CUBIC>(ax, i, m, c);
         h_center[x] = c;
         h_ww[x] = ww;
         h_min[x] = m;
@@ -117,8 +135,8 @@ __global__ __launch_bounds__(NT) void image_prep_kernel(const uint8_t* __restric
         int m, n;
         tap_range(ay, H, top + y0 + y, c, m, n);
         double ww = 0.0;
-        for (int i = 0; i < n; ++i) ww += weight(ay, i, m, c);
-        for (int i = 0; i < n; ++i) v_k[y][i] = fixed_coeff(weight(ay, i, m, c), ww);
+        for (int i = 0; i < n; ++i) ww += weight<CUBIC>(ay, i, m, c);
+        for (int i = 0; i < n; ++i) v_k[y][i] = fixed_coeff(weight<CUBIC>(ay, i, m, c), ww);
         v_min[y] = m;
         v_cnt[y] = n;
     }
@@ -144,7 +162,7 @@ __global__ __launch_bounds__(NT) void image_prep_kernel(const uint8_t* __restric
             long q = d.offset + (long)(c0 + r) * row_bytes + 3L * m;
             int s[3] = {1 << (PB - 1), 1 << (PB - 1), 1 << (PB - 1)};
             for (int i = 0; i < n; ++i, q += 3) {
-                const int k = fixed_coeff(weight(ax, i, m, c), ww);
+                const int k = fixed_coeff(weight<CUBIC>(ax, i, m, c), ww);
                 s[0] += rd.at(q) * k;
                 s[1] += rd.at(q + 1) * k;
                 s[2] += rd.at(q + 2) * k;
@@ -187,40 +205,59 @@ __global__ __launch_bounds__(NT) void image_prep_kernel(const uint8_t* __restric
 #pragma unroll
             for (int ch = 0; ch < 3; ++ch) {
                 const float v = __fdiv_rn((float)clip8(acc[j][ch]), 255.0f);
-                o[ch * plane + at] = __fdiv_rn(__fsub_rn(v, 0.5f), 0.5f);
+                o[ch * plane + at] = __fdiv_rn(__fsub_rn(v, nm.mean[ch]), nm.stdv[ch]);
             }
         }
     }
 }
 
-bool desc_ok(const pdmk_image_desc& d, int R, int64_t src_bytes) {
+bool desc_ok(const pdmk_image_desc& d, int R, int64_t src_bytes, int filter) {
     const int64_t lim = 1 << 20;
     if (d.h < 1 || d.w < 1 || d.rh < 1 || d.rw < 1 || d.h > lim || d.w > lim || d.rh > lim || d.rw > lim) return false;
     if (d.top < 0 || d.left < 0 || d.top + R > d.rh || d.left + R > d.rw) return false;
     if (d.flip != 0 && d.flip != 1) return false;
-    if ((d.h + d.rh - 1) / d.rh > (KVMAX - 1) / 2) return false;          // vertical taps of one output row fit v_k
+    if ((d.h + d.rh - 1) / d.rh > (KVMAX - 1) / (filter ? 4 : 2)) return false;   // vertical taps of one output row fit v_k
     if (d.offset < 0 || d.h * d.w * 3 > src_bytes) return false;
     const int64_t end = d.offset + d.h * d.w * 3;
     return end <= src_bytes && ((end + 3) & ~int64_t(3)) <= src_bytes;   // the last aligned word is inside the buffer
 }
 
+template <bool CUBIC>
+void launch(const uint8_t* src, const pdmk_image_desc* desc_dev, int B, int R, const Norm3& nm, float* out, hipStream_t st) {
+    const int per = (BAND * R + NT - 1) / NT;
+    dim3 grid((unsigned)((R + BAND - 1) / BAND), (unsigned)B);
+    if (per <= 1) hipLaunchKernelGGL((image_prep_kernel<1, CUBIC>), grid, dim3(NT), 0, st, src, desc_dev, R, nm, out);
+    else if (per <= 2) hipLaunchKernelGGL((image_prep_kernel<2, CUBIC>), grid, dim3(NT), 0, st, src, desc_dev, R, nm, out);
+    else if (per <= 4) hipLaunchKernelGGL((image_prep_kernel<4, CUBIC>), grid, dim3(NT), 0, st, src, desc_dev, R, nm, out);
+    else if (per <= 8) hipLaunchKernelGGL((image_prep_kernel<8, CUBIC>), grid, dim3(NT), 0, st, src, desc_dev, R, nm, out);
+    else hipLaunchKernelGGL((image_prep_kernel<16, CUBIC>), grid, dim3(NT), 0, st, src, desc_dev, R, nm, out);
+}
+
 }  // namespace
+
+extern "C" int pdmk_image_prep_ex(const uint8_t* src, int64_t src_bytes, const pdmk_image_desc* desc,
+                                  const pdmk_image_desc* desc_dev, int B, int R, int filter, const float* mean,
+                                  const float* stdv, float* out, pdmk_stream stream) {
+    if (!src || !desc || !desc_dev || !out || !mean || !stdv || B < 1 || B > 65535 || R < 1 || R > RMAX || src_bytes < 1 ||
+        (filter != 0 && filter != 1) || ((uintptr_t)src & 3) || ((uintptr_t)desc_dev & 7) || ((uintptr_t)out & 3))
+        return -1;
+    Norm3 nm;
+    for (int c = 0; c < 3; ++c) {
+        if (!(stdv[c] != 0.0f)) return -1;
+        nm.mean[c] = mean[c];
+        nm.stdv[c] = stdv[c];
+    }
+    for (int i = 0; i < B; ++i)
+        if (!desc_ok(desc[i], R, src_bytes, filter)) return -1;
+    hipStream_t st = (hipStream_t)stream;
+    if (filter) launch<true>(src, desc_dev, B, R, nm, out, st);
+    else launch<false>(src, desc_dev, B, R, nm, out, st);
+    PDMK_CHECK_LAUNCH();
+    return 0;
+}
 
 extern "C" int pdmk_image_prep(const uint8_t* src, int64_t src_bytes, const pdmk_image_desc* desc,
                                const pdmk_image_desc* desc_dev, int B, int R, float* out, pdmk_stream stream) {
-    if (!src || !desc || !desc_dev || !out || B < 1 || B > 65535 || R < 1 || R > RMAX || src_bytes < 1 ||
-        ((uintptr_t)src & 3) || ((uintptr_t)desc_dev & 7) || ((uintptr_t)out & 3))
-        return -1;
-    for (int i = 0; i < B; ++i)
-        if (!desc_ok(desc[i], R, src_bytes)) return -1;
-    const int per = (BAND * R + NT - 1) / NT;
-    dim3 grid((unsigned)((R + BAND - 1) / BAND), (unsigned)B);
-    hipStream_t st = (hipStream_t)stream;
-    if (per <= 1) hipLaunchKernelGGL(image_prep_kernel<1>, grid, dim3(NT), 0, st, src, desc_dev, R, out);
-    else if (per <= 2) hipLaunchKernelGGL(image_prep_kernel<2>, grid, dim3(NT), 0, st, src, desc_dev, R, out);
-    else if (per <= 4) hipLaunchKernelGGL(image_prep_kernel<4>, grid, dim3(NT), 0, st, src, desc_dev, R, out);
-    else if (per <= 8) hipLaunchKernelGGL(image_prep_kernel<8>, grid, dim3(NT), 0, st, src, desc_dev, R, out);
-    else hipLaunchKernelGGL(image_prep_kernel<16>, grid, dim3(NT), 0, st, src, desc_dev, R, out);
-    PDMK_CHECK_LAUNCH();
-    return 0;
+    const float half[3] = {0.5f, 0.5f, 0.5f};
+    return pdmk_image_prep_ex(src, src_bytes, desc, desc_dev, B, R, 0, half, half, out, stream);
 }

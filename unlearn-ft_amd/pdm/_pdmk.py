@@ -106,6 +106,12 @@ _SIGS = {
     "pdmk_attn_fwd_causal": ([vp, vp, vp, vp, vp, i32, i32, i32, i64, i32, i64, i32, i64, i32, i64, i32, f32, i32, vp], i32),
     "pdmk_gelu_fwd": ([vp, vp, i64, i32, vp], i32),
     "pdmk_image_prep": ([vp, i64, vp, vp, i32, i32, vp, vp], i32),
+    "pdmk_image_prep_ex": ([vp, i64, vp, vp, i32, i32, i32, vp, vp, vp, vp], i32),
+    "pdmk_patch_im2col": ([vp, vp, i32, i32, i32, i32, i32, vp], i32),
+    "pdmk_vit_tokens": ([vp, i32, vp, vp, i32, vp, i32, i32, i32, i32, i32, vp], i32),
+    "pdmk_quick_gelu_fwd": ([vp, vp, i64, i32, vp], i32),
+    "pdmk_gather_rows": ([vp, i32, vp, i32, vp, i32, i32, i32, i32, vp], i32),
+    "pdmk_clip_score_head": ([vp, i32, vp, i32, vp, vp, vp, i32, i32, vp], i32),
     "pdmk_plms_step": ([vp, i32, f32, f32, i32, vp, vp, vp, vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, vp], i32),
     "pdmk_image_to_u8": ([vp, vp, i32, i32, i32, vp], i32),
     "pdmk_gemm_splitk_workspace_bytes": ([i64, i32, i32], i64),
@@ -917,6 +923,49 @@ def image_prep(src, desc, desc_dev, out):
             or not out.is_contiguous()):
         raise PdmkError("image_prep: src uint8, desc int64 [B, 8] on the host, desc_dev its device copy, out fp32 [B, 3, R, R]")
     _chk(_lib.pdmk_image_prep(_p(src), src.numel(), _p(desc), _p(desc_dev), B, R, _p(out), _st()), "pdmk_image_prep")
+
+
+CLIP_MEAN = (0.48145466, 0.4578275, 0.40821073)
+CLIP_STD = (0.26862954, 0.26130258, 0.27577711)
+
+
+def image_prep_ex(src, desc, desc_dev, out, filter=1, mean=CLIP_MEAN, std=CLIP_STD):
+    """image_prep with the resample filter (0 bilinear, 1 Pillow bicubic) and the Normalize(mean, std) as parameters."""
+    B, R = out.shape[0], out.shape[-1]
+    if (desc.device.type != "cpu" or desc.dtype != torch.int64 or tuple(desc.shape) != (B, 8) or not desc.is_contiguous()
+            or desc_dev.dtype != torch.int64 or desc_dev.numel() != 8 * B or not desc_dev.is_contiguous()
+            or src.dtype != torch.uint8 or out.dtype != torch.float32 or tuple(out.shape) != (B, 3, R, R)
+            or not out.is_contiguous()):
+        raise PdmkError("image_prep_ex: src uint8, desc int64 [B, 8] on the host, desc_dev its device copy, out fp32 [B, 3, R, R]")
+    m, s = (f32 * 3)(*mean), (f32 * 3)(*std)
+    _chk(_lib.pdmk_image_prep_ex(_p(src), src.numel(), _p(desc), _p(desc_dev), B, R, int(filter), m, s, _p(out), _st()),
+         "pdmk_image_prep_ex")
+
+
+def patch_im2col(x, out, B, S, p):
+    """x fp32 [B, 3, S, S] -> out [B * (S / p)^2, ld] rows in the compute dtype, columns (c, ky, kx), padding columns 0."""
+    _chk(_lib.pdmk_patch_im2col(_p(x), _p(out), B, S, p, out.stride(0), dt(out), _st()), "pdmk_patch_im2col")
+
+
+def vit_tokens(patches, cls, pos, ldpos, out, B, G2, E):
+    _chk(_lib.pdmk_vit_tokens(_p(patches), patches.stride(0), _p(cls), _p(pos), ldpos, _p(out), out.stride(0), B, G2, E,
+                              dt(out), _st()), "pdmk_vit_tokens")
+
+
+def quick_gelu_fwd(x, y):
+    _chk(_lib.pdmk_quick_gelu_fwd(_p(x), _p(y), x.numel(), dt(x), _st()), "pdmk_quick_gelu_fwd")
+
+
+def gather_rows(x, ids, T, out, B, D):
+    """out[b] = x[b * T + j] with j = 0 (ids None: CLS) or the first argmax of ids[b] (EOT), computed on the device."""
+    _chk(_lib.pdmk_gather_rows(_p(x), x.stride(0), _p(ids), T, _p(out), out.stride(0), B, D, dt(x), _st()),
+         "pdmk_gather_rows")
+
+
+def clip_score_head(a, b, an, bn, acc, B, D):
+    """fp32 rows: an = a / |a|, bn = b / |b|, acc (fp64 [1] on the device) += sum of the row dot products."""
+    _chk(_lib.pdmk_clip_score_head(_p(a), a.stride(0), _p(b), 0 if b is None else b.stride(0), _p(an), _p(bn), _p(acc), B,
+                                   D, _st()), "pdmk_clip_score_head")
 
 
 def plms_table(rows, device):

@@ -32,13 +32,14 @@ class CLIPTextConfig:
     num_attention_heads: int = 16
     max_position_embeddings: int = 77
     layer_norm_eps: float = 1e-5
+    hidden_act: str = "gelu"          # "gelu" (SD-2.1's OpenCLIP encoder) or "quick_gelu" (OpenAI CLIP)
 
     @staticmethod
     def sd21():
         return CLIPTextConfig()
 
 
-def build_entries(cfg: CLIPTextConfig):
+def build_entries(cfg: CLIPTextConfig, projection_dim=0):
     E, F = cfg.hidden_size, cfg.intermediate_size
     out = [_lin("embeddings.token_embedding", [("embeddings.token_embedding.weight", cfg.vocab_size)], E),
            _lin("embeddings.position_embedding", [("embeddings.position_embedding.weight", cfg.max_position_embeddings)], E)]
@@ -58,6 +59,8 @@ def build_entries(cfg: CLIPTextConfig):
         lin(p + ".mlp.fc1", [(p + ".mlp.fc1", F)], E)
         lin(p + ".mlp.fc2", [(p + ".mlp.fc2", E)], F)
     norm("final_layer_norm")
+    if projection_dim:                  # CLIPModel's text_projection (no bias)
+        out.append(_lin("text_projection", [("text_projection.weight", projection_dim)], E))
     off = 0
     for e in out:
         e.off = off
@@ -74,15 +77,17 @@ class _Output(tuple):
 
 
 class CLIPTextModel:
-    def __init__(self, cfg: CLIPTextConfig = None, device=None, dtype=torch.bfloat16, seed=0, init=True):
+    def __init__(self, cfg: CLIPTextConfig = None, device=None, dtype=torch.bfloat16, seed=0, init=True, projection_dim=0):
         if not torch.cuda.is_available():
             raise RuntimeError("CLIPTextModel (MI355X engine) needs a GPU; there is no CPU fallback")
         self.cfg = cfg or CLIPTextConfig.sd21()
         assert self.cfg.hidden_size // self.cfg.num_attention_heads == 64, "attention kernels are specialised for head dim 64"
         assert self.cfg.hidden_size % 32 == 0 and self.cfg.intermediate_size % 32 == 0
+        if self.cfg.hidden_act not in ("gelu", "quick_gelu"):
+            raise NotImplementedError(f"hidden_act {self.cfg.hidden_act!r}")
         self.device = torch.device(device or "cuda:0")
         self.dtype = dtype
-        self.store = ParamStore(build_entries(self.cfg), self.device, dtype, train=False)
+        self.store = ParamStore(build_entries(self.cfg, projection_dim), self.device, dtype, train=False)
         self.ops = _Ops(self.store, dtype)
         self.config = SimpleNamespace(**self.cfg.__dict__)
         # ~10 launches per layer on 77-token inputs are launch-bound from Python (3.2 ms eager for 23 layers): each
@@ -139,8 +144,9 @@ class CLIPTextModel:
         return self.dtype
 
     # ------------------------------------------------------------------ forward
-    def encode_2d(self, input_ids):
-        """ids [B, T] (T <= 77) -> last hidden state as a 2-D [B*T, hidden] matrix in the compute dtype."""
+    def encode_2d(self, input_ids, final_norm=True):
+        """ids [B, T] (T <= 77) -> last hidden state as a 2-D [B*T, hidden] matrix in the compute dtype (final_norm=False:
+        before final_layer_norm, for callers that normalise only the rows they pool)."""
         cfg, o, P = self.cfg, self.ops, self.store
         B, T = input_ids.shape
         assert T <= cfg.max_position_embeddings
@@ -163,9 +169,9 @@ class CLIPTextModel:
             h = o.layernorm(x, p + ".layer_norm2")
             f = o.linear(h, p + ".mlp.fc1", bias=p + ".mlp.fc1.bias").t
             a = torch.empty_like(f)
-            k.gelu_fwd(f, a)
+            (k.quick_gelu_fwd if cfg.hidden_act == "quick_gelu" else k.gelu_fwd)(f, a)
             x = o.linear(Act(a), p + ".mlp.fc2", bias=p + ".mlp.fc2.bias", residual=x)
-        return o.layernorm(x, "final_layer_norm").t
+        return o.layernorm(x, "final_layer_norm").t if final_norm else x.t
 
     def _replay(self, input_ids):
         key = tuple(input_ids.shape)
