@@ -521,6 +521,39 @@ int pdmk_plms_step(const void* pred, int ld, float g_u, float g_t, int cfg, floa
 int pdmk_image_to_u8(const float* src, uint8_t* dst, int B, int C, int HW, pdmk_stream stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * FID (pdm/utils/fid_utils.py, pdm/models/inception): clean-fid's `legacy_pytorch` mode = pytorch-fid's InceptionV3 pool3
+ * features of the images resized to 299 x 299 without antialiasing, then the Frechet distance of two Gaussians.  All fp32
+ * (exact-fp32 MFMA), inference only; the statistics accumulate in fp64.
+ * pdmk_resize_bilinear_u8: ragged batch of packed HWC uint8 images (desc as pdmk_image_prep: only offset, h, w are read; any
+ *   size >= 1) -> out fp32 NHWC [B, S, S, 3] = 2 * (clip(bilinear(x), 0, 255) / 255) - 1 with torch's CPU
+ *   F.interpolate(mode="bilinear", align_corners=False) arithmetic: scale = (float)in / S, src = fmaf(scale, dst + 0.5f, -0.5f)
+ *   clamped at 0 (one rounding), i1 = min(i0 + 1, in - 1), weights 1 - l and l, along x then y, nothing else fused.
+ * pdmk_image_resize_u8: Pillow's 8-bpc bicubic Image.resize((OW, OH)) (x and y scaled independently, no crop) of B images to
+ *   out uint8 HWC [B, OH, OW, 3]; desc[i] = (offset, h, w, OH, OW, 0, 0, 0).  OW <= 1024, downscale <= 63x per axis.
+ * pdmk_conv2d_fwd: y[(b, oy, ox)][0:Co] = act(bias + sum_{ky, kx, ci} x[(b, oy*stride - pad_h + ky, ox*stride - pad_w + kx)][ci]
+ *   * w[co][(ky * kw + kx) * Ci + ci]); x NHWC with row (pixel) stride lda >= Ci, y with row stride ldc >= Co (a column slice
+ *   of a wider buffer: columns outside [0, Co) are not touched), w [Co][kh * kw * Ci] contiguous, bias [Co] or NULL, relu 0 / 1.
+ *   Taps outside the image read zero.  16-byte loads when Ci % 4 == 0, lda % 4 == 0 and x, w are 16-byte aligned; any
+ *   geometry otherwise (element gathers).
+ * pdmk_pool2d: 3 x 3 window, mode 0 max, mode 1 average over the taps inside the image (count_include_pad=False); stride
+ *   >= 1, pad 0 or 1; x [B, H, W, ldx], y [B, Ho, Wo, ldy], C channels of each row.
+ * pdmk_global_avgpool: x [B, HW, ldx] -> y [B, C] contiguous, rows summed in order then divided by HW.
+ * pdmk_fid_accumulate: x fp32 [B, D] (row stride ldx): sum[D] += sum_r x[r], outer[i][j] += sum_r x[r][i] x[r][j] for every
+ *   64 x 64 tile that touches the upper triangle (entries below the diagonal outside those tiles are NOT updated), fp64, rows
+ *   in order, no atomics: the same batches in the same order give the same bits.  The caller zeroes sum / outer first.
+ * All: -1 on a null / misaligned pointer, a size < 1 or out of range, a stride smaller than the row. */
+int pdmk_resize_bilinear_u8(const uint8_t* src, int64_t src_bytes, const pdmk_image_desc* desc, const pdmk_image_desc* desc_dev,
+                            int B, int S, float* out, pdmk_stream stream);
+int pdmk_image_resize_u8(const uint8_t* src, int64_t src_bytes, const pdmk_image_desc* desc, const pdmk_image_desc* desc_dev,
+                         int B, int OH, int OW, uint8_t* out, pdmk_stream stream);
+int pdmk_conv2d_fwd(const float* x, int lda, const float* w, const float* bias, float* y, int ldc, int B, int H, int W, int Ci,
+                    int Co, int kh, int kw, int stride, int pad_h, int pad_w, int relu, pdmk_stream stream);
+int pdmk_pool2d(const float* x, int ldx, float* y, int ldy, int B, int H, int W, int C, int mode, int stride, int pad,
+                pdmk_stream stream);
+int pdmk_global_avgpool(const float* x, int ldx, float* y, int B, int HW, int C, pdmk_stream stream);
+int pdmk_fid_accumulate(const float* x, int ldx, int B, int D, double* sum, double* outer, pdmk_stream stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Data-parallel gradient exchange: DDP's all-reduce inside accelerator.backward
  * (pdm/training/trainer.py:117-129, 2782, 2808) as RCCL all-reduces over xGMI behind an explicit communicator handle.
  * pdmk_comm_unique_id: rank 0 fills 128 bytes (ncclUniqueId) and hands them to the other ranks out of band (the Python

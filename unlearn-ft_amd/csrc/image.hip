@@ -19,6 +19,12 @@
 // read neighbouring words of the same row.  The vertical taps of one output row are held in LDS (KVMAX): the triangle filter
 // needs at most 2 * ceil(in / out) + 1 of them, the cubic one 4 * ceil(in / out) + 1, so the largest downscale is 127x for
 // bilinear and 63x for bicubic.
+//
+// pdmk_image_resize_u8 is the same bicubic resample with a rectangular window (the whole resized image, x and y scaled
+// independently) and the bytes themselves as output: Pillow's Image.resize((W, H)).
+// pdmk_resize_bilinear_u8 is NOT Pillow's resample but torch's CPU F.interpolate(mode="bilinear", align_corners=False) on the
+// float image (two taps per axis whatever the scale, no antialiasing), the resize of clean-fid's legacy_pytorch FID mode; its
+// source coordinate is the one explicit fma of this file.
 #include "common.h"
 
 #pragma clang fp contract(off)
@@ -100,9 +106,12 @@ struct Norm3 {
     float mean[3], stdv[3];
 };
 
-template <int PER, bool CUBIC>
+// R x CH: the crop window (columns x rows; the square R x R of the transforms, or the whole resized image of
+// pdmk_image_resize_u8).  U8: the resampled bytes themselves go out as HWC uint8 instead of the normalised NCHW floats.
+template <int PER, bool CUBIC, bool U8>
 __global__ __launch_bounds__(NT) void image_prep_kernel(const uint8_t* __restrict__ src, const pdmk_image_desc* __restrict__ descs,
-                                                        int R, Norm3 nm, float* __restrict__ out) {
+                                                        int R, int CH, Norm3 nm, float* __restrict__ out,
+                                                        uint8_t* __restrict__ out8) {
     __shared__ double h_center[RMAX], h_ww[RMAX];
     __shared__ int h_min[RMAX], h_cnt[RMAX];
     __shared__ int v_k[BAND][KVMAX];
@@ -111,7 +120,7 @@ __global__ __launch_bounds__(NT) void image_prep_kernel(const uint8_t* __restric
 
     const int img = blockIdx.y;
     const int y0 = blockIdx.x * BAND;
-    const int nb = R - y0 < BAND ? R - y0 : BAND;            // output rows of this band
+    const int nb = CH - y0 < BAND ? CH - y0 : BAND;          // output rows of this band
     const pdmk_image_desc d = descs[img];
     const int H = (int)d.h, W = (int)d.w, RH = (int)d.rh, RW = (int)d.rw, top = (int)d.top, left = (int)d.left;
     const Axis ax = make_axis<CUBIC>(W, RW), ay = make_axis<CUBIC>(H, RH);
@@ -193,8 +202,23 @@ __global__ __launch_bounds__(NT) void image_prep_kernel(const uint8_t* __restric
         __syncthreads();
     }
 
+    if constexpr (U8) {
+        uint8_t* o8 = out8 + (long)img * CH * R * 3;
+#pragma unroll
+        for (int j = 0; j < PER; ++j) {
+            const int p = threadIdx.x + j * NT;
+            const int y = p / R, x = p - y * R;
+            if (y < nb) {
+                uint8_t* q = o8 + ((long)(y0 + y) * R + x) * 3;
+                q[0] = (uint8_t)clip8(acc[j][0]);
+                q[1] = (uint8_t)clip8(acc[j][1]);
+                q[2] = (uint8_t)clip8(acc[j][2]);
+            }
+        }
+        return;
+    }
     // ToTensor + Normalize, NCHW fp32; the flip mirrors the crop's columns
-    const long plane = (long)R * R;
+    const long plane = (long)R * CH;
     float* o = out + (long)img * 3 * plane;
 #pragma unroll
     for (int j = 0; j < PER; ++j) {
@@ -211,10 +235,10 @@ __global__ __launch_bounds__(NT) void image_prep_kernel(const uint8_t* __restric
     }
 }
 
-bool desc_ok(const pdmk_image_desc& d, int R, int64_t src_bytes, int filter) {
+bool desc_ok(const pdmk_image_desc& d, int R, int RH, int64_t src_bytes, int filter) {
     const int64_t lim = 1 << 20;
     if (d.h < 1 || d.w < 1 || d.rh < 1 || d.rw < 1 || d.h > lim || d.w > lim || d.rh > lim || d.rw > lim) return false;
-    if (d.top < 0 || d.left < 0 || d.top + R > d.rh || d.left + R > d.rw) return false;
+    if (d.top < 0 || d.left < 0 || d.top + RH > d.rh || d.left + R > d.rw) return false;
     if (d.flip != 0 && d.flip != 1) return false;
     if ((d.h + d.rh - 1) / d.rh > (KVMAX - 1) / (filter ? 4 : 2)) return false;   // vertical taps of one output row fit v_k
     if (d.offset < 0 || d.h * d.w * 3 > src_bytes) return false;
@@ -222,15 +246,55 @@ bool desc_ok(const pdmk_image_desc& d, int R, int64_t src_bytes, int filter) {
     return end <= src_bytes && ((end + 3) & ~int64_t(3)) <= src_bytes;   // the last aligned word is inside the buffer
 }
 
-template <bool CUBIC>
-void launch(const uint8_t* src, const pdmk_image_desc* desc_dev, int B, int R, const Norm3& nm, float* out, hipStream_t st) {
+template <bool CUBIC, bool U8 = false>
+void launch(const uint8_t* src, const pdmk_image_desc* desc_dev, int B, int R, int RH, const Norm3& nm, float* out, uint8_t* out8,
+            hipStream_t st) {
     const int per = (BAND * R + NT - 1) / NT;
-    dim3 grid((unsigned)((R + BAND - 1) / BAND), (unsigned)B);
-    if (per <= 1) hipLaunchKernelGGL((image_prep_kernel<1, CUBIC>), grid, dim3(NT), 0, st, src, desc_dev, R, nm, out);
-    else if (per <= 2) hipLaunchKernelGGL((image_prep_kernel<2, CUBIC>), grid, dim3(NT), 0, st, src, desc_dev, R, nm, out);
-    else if (per <= 4) hipLaunchKernelGGL((image_prep_kernel<4, CUBIC>), grid, dim3(NT), 0, st, src, desc_dev, R, nm, out);
-    else if (per <= 8) hipLaunchKernelGGL((image_prep_kernel<8, CUBIC>), grid, dim3(NT), 0, st, src, desc_dev, R, nm, out);
-    else hipLaunchKernelGGL((image_prep_kernel<16, CUBIC>), grid, dim3(NT), 0, st, src, desc_dev, R, nm, out);
+    dim3 grid((unsigned)((RH + BAND - 1) / BAND), (unsigned)B);
+    if (per <= 1) hipLaunchKernelGGL((image_prep_kernel<1, CUBIC, U8>), grid, dim3(NT), 0, st, src, desc_dev, R, RH, nm, out, out8);
+    else if (per <= 2) hipLaunchKernelGGL((image_prep_kernel<2, CUBIC, U8>), grid, dim3(NT), 0, st, src, desc_dev, R, RH, nm, out, out8);
+    else if (per <= 4) hipLaunchKernelGGL((image_prep_kernel<4, CUBIC, U8>), grid, dim3(NT), 0, st, src, desc_dev, R, RH, nm, out, out8);
+    else if (per <= 8) hipLaunchKernelGGL((image_prep_kernel<8, CUBIC, U8>), grid, dim3(NT), 0, st, src, desc_dev, R, RH, nm, out, out8);
+    else hipLaunchKernelGGL((image_prep_kernel<16, CUBIC, U8>), grid, dim3(NT), 0, st, src, desc_dev, R, RH, nm, out, out8);
+}
+
+// torch's CPU upsample_bilinear2d (align_corners=False, no antialiasing) source coordinate: ONE rounding of scale * (dst + 0.5)
+// - 0.5 (an explicit fma; nothing else in this file may fuse), clamped at 0; first tap, second tap and the second tap's weight
+__device__ __forceinline__ void lerp_axis(int in, float scale, int dst, int& i0, int& i1, float& lam) {
+    float s = fmaf(scale, (float)dst + 0.5f, -0.5f);
+    if (s < 0.f) s = 0.f;
+    i0 = (int)s;
+    if (i0 > in - 1) i0 = in - 1;
+    i1 = i0 + 1 < in ? i0 + 1 : in - 1;
+    lam = s - (float)i0;
+    lam = lam < 0.f ? 0.f : (lam > 1.f ? 1.f : lam);
+}
+
+// one thread per output pixel (3 channels): out[b][y][x][c] = 2 * (clip(bilinear, 0, 255) / 255) - 1, fp32 NHWC
+__global__ __launch_bounds__(NT) void resize_bilinear_kernel(const uint8_t* __restrict__ src, const pdmk_image_desc* __restrict__ descs,
+                                                             int B, int S, float* __restrict__ out) {
+    const long n = (long)B * S * S;
+    for (long i = (long)blockIdx.x * NT + threadIdx.x; i < n; i += (long)gridDim.x * NT) {
+        const int b = (int)(i / ((long)S * S)), p = (int)(i - (long)b * S * S);
+        const int y = p / S, x = p - y * S;
+        const pdmk_image_desc d = descs[b];
+        const int H = (int)d.h, W = (int)d.w;
+        int x0, x1, y0, y1;
+        float lx, ly;
+        lerp_axis(W, (float)W / (float)S, x, x0, x1, lx);
+        lerp_axis(H, (float)H / (float)S, y, y0, y1, ly);
+        const float wx0 = 1.0f - lx, wy0 = 1.0f - ly;
+        const uint8_t* r0 = src + d.offset + (long)y0 * W * 3;
+        const uint8_t* r1 = src + d.offset + (long)y1 * W * 3;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const float t = wx0 * (float)r0[3 * x0 + c] + lx * (float)r0[3 * x1 + c];
+            const float u = wx0 * (float)r1[3 * x0 + c] + lx * (float)r1[3 * x1 + c];
+            float v = wy0 * t + ly * u;
+            v = v < 0.f ? 0.f : (v > 255.f ? 255.f : v);
+            out[i * 3 + c] = 2.0f * (v / 255.0f) - 1.0f;
+        }
+    }
 }
 
 }  // namespace
@@ -248,10 +312,10 @@ extern "C" int pdmk_image_prep_ex(const uint8_t* src, int64_t src_bytes, const p
         nm.stdv[c] = stdv[c];
     }
     for (int i = 0; i < B; ++i)
-        if (!desc_ok(desc[i], R, src_bytes, filter)) return -1;
+        if (!desc_ok(desc[i], R, R, src_bytes, filter)) return -1;
     hipStream_t st = (hipStream_t)stream;
-    if (filter) launch<true>(src, desc_dev, B, R, nm, out, st);
-    else launch<false>(src, desc_dev, B, R, nm, out, st);
+    if (filter) launch<true>(src, desc_dev, B, R, R, nm, out, nullptr, st);
+    else launch<false>(src, desc_dev, B, R, R, nm, out, nullptr, st);
     PDMK_CHECK_LAUNCH();
     return 0;
 }
@@ -260,4 +324,37 @@ extern "C" int pdmk_image_prep(const uint8_t* src, int64_t src_bytes, const pdmk
                                const pdmk_image_desc* desc_dev, int B, int R, float* out, pdmk_stream stream) {
     const float half[3] = {0.5f, 0.5f, 0.5f};
     return pdmk_image_prep_ex(src, src_bytes, desc, desc_dev, B, R, 0, half, half, out, stream);
+}
+
+extern "C" int pdmk_image_resize_u8(const uint8_t* src, int64_t src_bytes, const pdmk_image_desc* desc,
+                                    const pdmk_image_desc* desc_dev, int B, int OH, int OW, uint8_t* out, pdmk_stream stream) {
+    if (!src || !desc || !desc_dev || !out || B < 1 || B > 65535 || OH < 1 || OW < 1 || OW > RMAX || OH > (1 << 20) ||
+        src_bytes < 1 || ((uintptr_t)src & 3) || ((uintptr_t)desc_dev & 7))
+        return -1;
+    for (int i = 0; i < B; ++i) {
+        const pdmk_image_desc& d = desc[i];
+        if (d.rh != OH || d.rw != OW || d.top != 0 || d.left != 0 || d.flip != 0 || !desc_ok(d, OW, OH, src_bytes, 1)) return -1;
+    }
+    launch<true, true>(src, desc_dev, B, OW, OH, Norm3{}, nullptr, out, (hipStream_t)stream);
+    PDMK_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int pdmk_resize_bilinear_u8(const uint8_t* src, int64_t src_bytes, const pdmk_image_desc* desc,
+                                       const pdmk_image_desc* desc_dev, int B, int S, float* out, pdmk_stream stream) {
+    if (!src || !desc || !desc_dev || !out || B < 1 || S < 1 || S > (1 << 14) || src_bytes < 1 || ((uintptr_t)desc_dev & 7) ||
+        ((uintptr_t)out & 3))
+        return -1;
+    const int64_t lim = 1 << 20;
+    for (int i = 0; i < B; ++i) {
+        const pdmk_image_desc& d = desc[i];
+        if (d.h < 1 || d.w < 1 || d.h > lim || d.w > lim || d.offset < 0 || d.h * d.w * 3 > src_bytes ||
+            d.offset + d.h * d.w * 3 > src_bytes)
+            return -1;
+    }
+    const long g = ((long)B * S * S + NT - 1) / NT;
+    hipLaunchKernelGGL(resize_bilinear_kernel, dim3((unsigned)(g < 65536 ? g : 65536)), dim3(NT), 0, (hipStream_t)stream, src,
+                       desc_dev, B, S, out);
+    PDMK_CHECK_LAUNCH();
+    return 0;
 }

@@ -114,6 +114,12 @@ _SIGS = {
     "pdmk_clip_score_head": ([vp, i32, vp, i32, vp, vp, vp, i32, i32, vp], i32),
     "pdmk_plms_step": ([vp, i32, f32, f32, i32, vp, vp, vp, vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, vp], i32),
     "pdmk_image_to_u8": ([vp, vp, i32, i32, i32, vp], i32),
+    "pdmk_resize_bilinear_u8": ([vp, i64, vp, vp, i32, i32, vp, vp], i32),
+    "pdmk_image_resize_u8": ([vp, i64, vp, vp, i32, i32, i32, vp, vp], i32),
+    "pdmk_conv2d_fwd": ([vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp], i32),
+    "pdmk_pool2d": ([vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp], i32),
+    "pdmk_global_avgpool": ([vp, i32, vp, i32, i32, i32, vp], i32),
+    "pdmk_fid_accumulate": ([vp, i32, i32, i32, vp, vp, vp], i32),
     "pdmk_gemm_splitk_workspace_bytes": ([i64, i32, i32], i64),
     "pdmk_groupnorm_workspace_bytes": ([i32, i32], i64),
     "pdmk_groupnorm_bwd_part_workspace_bytes": ([i32, i32], i64),
@@ -997,6 +1003,75 @@ def image_to_u8(src, dst):
             or tuple(dst.shape) != (B, H, W, Cc)):
         raise PdmkError("image_to_u8: src fp32 contiguous [B, C, H, W], dst uint8 contiguous [B, H, W, C]")
     _chk(_lib.pdmk_image_to_u8(_p(src), _p(dst), B, Cc, H * W, _st()), "pdmk_image_to_u8")
+
+
+def _avail(t):
+    """Elements from t's first element to the end of its storage (t may be a strided view of a wider buffer)."""
+    return t.untyped_storage().nbytes() // t.element_size() - t.storage_offset()
+
+
+def _desc_ok(desc, desc_dev, B):
+    return (desc.device.type == "cpu" and desc.dtype == torch.int64 and tuple(desc.shape) == (B, 8) and desc.is_contiguous()
+            and desc_dev.dtype == torch.int64 and desc_dev.numel() == 8 * B and desc_dev.is_contiguous())
+
+
+def resize_bilinear_u8(src, desc, desc_dev, out):
+    """Packed uint8 HWC images (desc as image_prep: offset, h, w used) -> out fp32 NHWC [B, S, S, 3] in [-1, 1]: torch's
+    CPU bilinear F.interpolate (no antialiasing), clip, / 255, * 2 - 1."""
+    B, S = out.shape[0], out.shape[1]
+    if (not _desc_ok(desc, desc_dev, B) or src.dtype != torch.uint8 or out.dtype != torch.float32
+            or tuple(out.shape) != (B, S, S, 3) or not out.is_contiguous()):
+        raise PdmkError("resize_bilinear_u8: src uint8, desc int64 [B, 8] on the host, desc_dev its device copy, out fp32 [B, S, S, 3]")
+    _chk(_lib.pdmk_resize_bilinear_u8(_p(src), src.numel(), _p(desc), _p(desc_dev), B, S, _p(out), _st()),
+         "pdmk_resize_bilinear_u8")
+
+
+def image_resize_u8(src, desc, desc_dev, out):
+    """Pillow's 8-bpc bicubic Image.resize((OW, OH)) of the packed images into out uint8 [B, OH, OW, 3]."""
+    B, OH, OW = out.shape[:3]
+    if (not _desc_ok(desc, desc_dev, B) or src.dtype != torch.uint8 or out.dtype != torch.uint8
+            or tuple(out.shape) != (B, OH, OW, 3) or not out.is_contiguous()):
+        raise PdmkError("image_resize_u8: src uint8, desc int64 [B, 8] on the host, desc_dev its device copy, out uint8 [B, OH, OW, 3]")
+    _chk(_lib.pdmk_image_resize_u8(_p(src), src.numel(), _p(desc), _p(desc_dev), B, OH, OW, _p(out), _st()),
+         "pdmk_image_resize_u8")
+
+
+def conv2d_fwd(x, lda, w, bias, y, ldc, B, H, W, Ci, Co, kh, kw, stride, pad_h, pad_w, relu=True):
+    """NHWC fp32 convolution + bias + ReLU (include/pdmk.h pdmk_conv2d_fwd).  x / y may be column slices of wider buffers
+    (row strides lda / ldc in elements); w [Co, kh * kw * Ci] with k = (ky, kx, ci)."""
+    Ho, Wo = (H + 2 * pad_h - kh) // stride + 1, (W + 2 * pad_w - kw) // stride + 1
+    if (any(t.dtype != torch.float32 for t in (x, w, y)) or (bias is not None and (bias.dtype != torch.float32 or bias.numel() < Co))
+            or w.numel() < Co * kh * kw * Ci or not w.is_contiguous() or _avail(x) < (B * H * W - 1) * lda + Ci
+            or _avail(y) < (B * Ho * Wo - 1) * ldc + Co):
+        raise PdmkError("conv2d_fwd: fp32 buffers, x >= [B*H*W rows of lda], y >= [B*Ho*Wo rows of ldc], w [Co, kh*kw*Ci]")
+    _chk(_lib.pdmk_conv2d_fwd(_p(x), lda, _p(w), _p(bias), _p(y), ldc, B, H, W, Ci, Co, kh, kw, stride, pad_h, pad_w,
+                              int(bool(relu)), _st()), "pdmk_conv2d_fwd")
+
+
+def pool2d(x, ldx, y, ldy, B, H, W, Cc, mode, stride, pad):
+    """3x3 NHWC pool: mode "max" or "avg" (valid-count divisor: count_include_pad=False)."""
+    Ho, Wo = (H + 2 * pad - 3) // stride + 1, (W + 2 * pad - 3) // stride + 1
+    if (x.dtype != torch.float32 or y.dtype != torch.float32 or mode not in ("max", "avg")
+            or _avail(x) < (B * H * W - 1) * ldx + Cc or _avail(y) < (B * Ho * Wo - 1) * ldy + Cc):
+        raise PdmkError("pool2d: fp32 buffers, x >= [B*H*W rows of ldx], y >= [B*Ho*Wo rows of ldy], mode max / avg")
+    _chk(_lib.pdmk_pool2d(_p(x), ldx, _p(y), ldy, B, H, W, Cc, 1 if mode == "avg" else 0, stride, pad, _st()), "pdmk_pool2d")
+
+
+def global_avgpool(x, ldx, y, B, HW, Cc):
+    if (x.dtype != torch.float32 or y.dtype != torch.float32 or not y.is_contiguous() or y.numel() != B * Cc
+            or _avail(x) < (B * HW - 1) * ldx + Cc):
+        raise PdmkError("global_avgpool: x fp32 >= [B*HW rows of ldx], y fp32 contiguous [B, C]")
+    _chk(_lib.pdmk_global_avgpool(_p(x), ldx, _p(y), B, HW, Cc, _st()), "pdmk_global_avgpool")
+
+
+def fid_accumulate(x, total, outer):
+    """total [D] += column sums, outer [D, D] += x^T x (upper-triangle 64 x 64 tiles) in fp64 on the device; x fp32 [B, D]."""
+    B, D = x.shape
+    if (x.dtype != torch.float32 or x.stride(1) != 1 or total.dtype != torch.float64 or outer.dtype != torch.float64
+            or tuple(total.shape) != (D,) or tuple(outer.shape) != (D, D) or not total.is_contiguous()
+            or not outer.is_contiguous()):
+        raise PdmkError("fid_accumulate: x fp32 [B, D], total fp64 [D], outer fp64 [D, D] contiguous")
+    _chk(_lib.pdmk_fid_accumulate(_p(x), x.stride(0), B, D, _p(total), _p(outer), _st()), "pdmk_fid_accumulate")
 
 
 def softmax_rows(s, p, rows, cols, lds, ldp):

@@ -1,0 +1,8 @@
+from .spec import ConvUnit, build_units, state_dict_shapes, fold_batchnorm  # noqa: F401
+
+
+def __getattr__(name):          # the model itself needs the GPU library's host side; the table above does not
+    if name in ("InceptionV3FID", "default_weights_path", "WEIGHTS_NAME"):
+        from . import inception_v3
+        return getattr(inception_v3, name)
+    raise AttributeError(name)
