@@ -299,6 +299,11 @@ int pdmk_attn_bwd(const void* q, const void* k, const void* v, const void* o, co
                   int dtype, pdmk_stream stream);
 /* Bytes of `ws` worth passing for this shape (0: pass NULL - the key blocks alone fill the chip). */
 int64_t pdmk_attn_bwd_workspace_bytes(int B, int H, int Nq, int Nk);
+/* Measurement helper (like pdmk_gemm_last_candidate): the kernel forms of the calling thread's last pdmk_attn_fwd[_causal] /
+ * pdmk_attn_bwd.  Bits 0-3: forward rows-per-wave form (1 = 16 queries per wave, 2 = 32); bits 4-7: the dQ form; bits 8-11:
+ * the dK/dV form (1 when the query sweep is split); bits 12..: the dK/dV query split actually used (1 = none).  A field is 0
+ * until its call has run.  No device work. */
+int pdmk_attn_last_forms(void);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Elementwise / reduction family.

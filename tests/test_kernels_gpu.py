@@ -362,13 +362,31 @@ def test_attention(dev, dn, Nq, Nk, H):
     close(dv.view(Bn, Nk, H, D).transpose(1, 2), gv, TOL[dn] * 2, "attn dv")
 
 
+@pytest.fixture
+def force_attn_forms():
+    """Force the rows-per-wave form (1 = 16, 2 = 32) of the attention forward, dQ and dK/dV kernels."""
+    names = ("PDMK_ATTN_NQ", "PDMK_ATTN_NQ_DQ", "PDMK_ATTN_NQ_DKV")
+    saved = {n: os.environ.get(n) for n in names}
+    def setter(forms):
+        for n, f in zip(names, forms):
+            os.environ[n] = str(f)
+    yield setter
+    for n, val in saved.items():
+        if val is None:
+            os.environ.pop(n, None)
+        else:
+            os.environ[n] = val
+
+
+@pytest.mark.parametrize("forms", [(1, 1, 1), (2, 2, 2), (2, 1, 1), (1, 2, 1), (1, 1, 2)], ids=lambda f: "%d%d%d" % f)
 @pytest.mark.parametrize("Nq,Nk", [(128, 77), (200, 200), (256, 13)])
-def test_attention_strongly_negative_scores_with_a_key_tail(dev, Nq, Nk):
+def test_attention_strongly_negative_scores_with_a_key_tail(dev, force_attn_forms, Nq, Nk, forms):
     """Rows whose real scores are ALL far below zero (log-sum-exp < -128 in base 2) next to key blocks with missing keys: a
     missing key has K = 0, i.e. score 0 and exp2(0 - lse) = inf - the masked tail block of the forward and of the dQ kernel must
     keep that out of the sums (an unmasked inf * 0 poisons the whole dQ row; found by the step-parity suite after a large-lr
     update), and the wide / narrow forms of all three kernels must agree with fp32 math."""
     from pdm import _pdmk as k
+    force_attn_forms(forms)        # (forward, dQ, dK/dV)
     torch.manual_seed(19)
     dt = torch.bfloat16
     Bn, H, D = 2, 2, 64
@@ -381,6 +399,7 @@ def test_attention_strongly_negative_scores_with_a_key_tail(dev, Nq, Nk):
     o = torch.zeros(Bn, Nq, H * D, device=dev, dtype=dt)
     lse = torch.zeros(Bn, H, Nq, device=dev)
     k.attn_fwd(q, kk, v, o, lse, Bn, H, Nq, Nk, qs, ks, ks, os_, scale)
+    assert k.attn_last_forms()[0] == forms[0]
     assert float(lse.max()) < -128.0, float(lse.max())          # the regime under test
     qr = q.float().reshape(Bn, Nq, H, D).transpose(1, 2).clone().requires_grad_(True)
     kr = kk.float().reshape(Bn, Nk, H, D).transpose(1, 2).clone().requires_grad_(True)
@@ -393,6 +412,7 @@ def test_attention_strongly_negative_scores_with_a_key_tail(dev, Nq, Nk):
     dq, dk, dv = (torch.zeros(Bn, n, H * D, device=dev, dtype=dt) for n in (Nq, Nk, Nk))
     delta = torch.zeros(Bn, H, Nq, device=dev)
     k.attn_bwd(q, kk, v, o, do, lse, delta, dq, dk, dv, Bn, H, Nq, Nk, qs, ks, ks, os_, os_, ks, ks, scale)
+    assert k.attn_last_forms()[1:] == (forms[1], forms[2], 1)
     for name, got in (("dq", dq), ("dk", dk), ("dv", dv)):
         assert torch.isfinite(got.float()).all(), name
     close(dq.view(Bn, Nq, H, D).transpose(1, 2), gq, 8e-2, "attn dq, negative scores")   # (ill-conditioned on purpose)

@@ -134,6 +134,14 @@ template <typename MM, int NS> struct AccLoop<MM, NS, NS> {
     template <typename F> static __device__ __forceinline__ void run(F&&) {}
 };
 
+// fp32 only: the sums that run over the whole sequence (O and l in the forward, dQ over the keys, dK / dV over the queries) are
+// formed per streamed block in accumulators that start at zero and then added to the running sums with ordinary fp32 adds.  A
+// single MFMA accumulator chained through all 1024 steps of a 4096-key row left errors that GROW LINEARLY with the sequence
+// (o, dq, dk 11-27 x torch's own fp32 error at N = 4096, 1.0-1.7 x at N <= 333: tests/test_attention_gpu.py) - each step's
+// accumulate loses a little in the same direction; 8 chained steps per block and a rounded add per block do not.  bf16 keeps
+// the single chain: its error is the bf16 rounding of P / dS, three orders of magnitude above this.
+template <typename T> struct BlockSums : std::is_same<T, float> {};
+
 // ================================================================================================ forward
 // one workgroup = 64*NQ queries of one (b,h); wave w owns NQ tiles of 16 queries (on the lanes) and sweeps the keys in
 // tiles of KVB.  NQ = 2 halves the K / V fragment reads per MFMA (every fragment feeds both query tiles): the loop is
@@ -149,6 +157,7 @@ __global__ __launch_bounds__(NT) void attn_fwd_kernel(const T* __restrict__ q, c
     typedef Mma<T> MM;
     typedef ACfg<T> AC;
     constexpr int RS = AC::RS, KVB = AC::KVB, NKT = KVB / 16, QROWS = 64 * NQ;
+    constexpr bool BLOCK_SUMS = BlockSums<T>::value;
     typedef TileIO<T, QROWS> QIO;
     typedef TileIO<T, KVB> KIO;
     __shared__ __attribute__((aligned(16))) T Qs[QROWS * RS];
@@ -271,6 +280,17 @@ __global__ __launch_bounds__(NT) void attn_fwd_kernel(const T* __restrict__ q, c
                     st[n][t][r + 1] = __builtin_amdgcn_exp2f(e2[1]);
                 }
         }
+        // fp32 (BLOCK_SUMS): this block's products go into accumulators of their own, which are then ADDED to the running ones - see
+        // BlockSums above
+        f32x4 otb[BLOCK_SUMS ? NQ : 1][4], olb[BLOCK_SUMS ? NQ : 1];
+        if constexpr (BLOCK_SUMS) {
+#pragma unroll
+            for (int n = 0; n < NQ; ++n) {
+                olb[n] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int i = 0; i < 4; ++i) otb[n][i] = f32x4{0.f, 0.f, 0.f, 0.f};
+            }
+        }
 #pragma unroll
         for (int pr = 0; pr < NKT / 2; ++pr) {
             AccLoop<MM, 0, MM::ACC_STEPS>::run([&](auto sc) {
@@ -279,15 +299,28 @@ __global__ __launch_bounds__(NT) void attn_fwd_kernel(const T* __restrict__ q, c
 #pragma unroll
                 for (int n = 0; n < NQ; ++n) {
                     pf[n] = MM::template acc_frag<S>(st[n][2 * pr], st[n][2 * pr + 1]);
-                    ol[n] = MM::mma(ones, pf[n], ol[n]);             // row sums of P: every row of ol is l
+                    // row sums of P: every row of ol is l
+                    if constexpr (BLOCK_SUMS) olb[n] = MM::mma(ones, pf[n], olb[n]);
+                    else ol[n] = MM::mma(ones, pf[n], ol[n]);
                 }
 #pragma unroll
                 for (int dt = 0; dt < 4; ++dt) {
                     const typename MM::frag vf = AT<T>::template colk_accs<S>(Vs[cur], pr * 32, dt * 16, lane);
 #pragma unroll
-                    for (int n = 0; n < NQ; ++n) ot[n][dt] = MM::mma(vf, pf[n], ot[n][dt]);
+                    for (int n = 0; n < NQ; ++n) {
+                        if constexpr (BLOCK_SUMS) otb[n][dt] = MM::mma(vf, pf[n], otb[n][dt]);
+                        else ot[n][dt] = MM::mma(vf, pf[n], ot[n][dt]);
+                    }
                 }
             });
+        }
+        if constexpr (BLOCK_SUMS) {
+#pragma unroll
+            for (int n = 0; n < NQ; ++n) {
+                ol[n] += olb[n];
+#pragma unroll
+                for (int dt = 0; dt < 4; ++dt) ot[n][dt] += otb[n][dt];
+            }
         }
         if (more) {
             KIO::store(Ks[cur ^ 1], rk_, tid);
@@ -356,6 +389,7 @@ __global__ __launch_bounds__(NT) void attn_bwd_dkv_kernel(const T* __restrict__ 
     typedef Mma<T> MM;
     typedef ACfg<T> AC;
     constexpr int RS = AC::RS, QB = AC::KVB, NQT = QB / 16, KROWS = 64 * NKW;
+    constexpr bool BLOCK_SUMS = BlockSums<T>::value;
     typedef TileIO<T, KROWS> KIO;
     typedef TileIO<T, QB> QIO;
     static_assert(!SPLIT || NKW == 1, "the query split is for few-key grids");
@@ -428,7 +462,8 @@ __global__ __launch_bounds__(NT) void attn_bwd_dkv_kernel(const T* __restrict__ 
             const f32x4 nd = *reinterpret_cast<const f32x4*>(&Ds[cur][t * 16 + (lane >> 4) * 4]);
             const f32x4 nlv = *reinterpret_cast<const f32x4*>(&Ls[cur][t * 16 + (lane >> 4) * 4]);
 #pragma unroll
-            for (int j = 0; j < NKW; ++j) { sacc[j] = f32x4{0.f, 0.f, 0.f, 0.f}; dp[j] = nd; }
+            // (fp32: dP is formed from zero and delta subtracted afterwards - see the dQ kernel)
+            for (int j = 0; j < NKW; ++j) { sacc[j] = f32x4{0.f, 0.f, 0.f, 0.f}; dp[j] = BLOCK_SUMS ? f32x4{0.f, 0.f, 0.f, 0.f} : nd; }
 #pragma unroll
             for (int kk = 0; kk < D / MM::KS; ++kk) {
                 const typename MM::frag qa = AT<T>::rowk(Qs[cur], t * 16, kk * MM::KS, lane);
@@ -448,13 +483,22 @@ __global__ __launch_bounds__(NT) void attn_bwd_dkv_kernel(const T* __restrict__ 
                 for (int j = 0; j < NKW; ++j) {
                     const f32x2 e2 = __builtin_elementwise_fma(f32x2{sacc[j][r], sacc[j][r + 1]}, f32x2{scale2, scale2}, f32x2{nlv[r], nlv[r + 1]});
                     const f32x2 pv = {__builtin_amdgcn_exp2f(e2[0]), __builtin_amdgcn_exp2f(e2[1])};
-                    const f32x2 d2 = pv * f32x2{dp[j][r], dp[j][r + 1]};
+                    f32x2 dpd = {dp[j][r], dp[j][r + 1]};
+                    if constexpr (BLOCK_SUMS) dpd += f32x2{nd[r], nd[r + 1]};
+                    const f32x2 d2 = pv * dpd;
                     p[j][t][r] = pv[0];
                     p[j][t][r + 1] = pv[1];
                     ds[j][t][r] = d2[0];
                     ds[j][t][r + 1] = d2[1];
                 }
             }
+        }
+        f32x4 dkb[BLOCK_SUMS ? NKW : 1][4], dvb[BLOCK_SUMS ? NKW : 1][4];      // fp32: this query block's sums (BlockSums)
+        if constexpr (BLOCK_SUMS) {
+#pragma unroll
+            for (int j = 0; j < NKW; ++j)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) { dkb[j][i] = f32x4{0.f, 0.f, 0.f, 0.f}; dvb[j][i] = f32x4{0.f, 0.f, 0.f, 0.f}; }
         }
 #pragma unroll
         for (int pr = 0; pr < NQT / 2; ++pr) {
@@ -472,11 +516,22 @@ __global__ __launch_bounds__(NT) void attn_bwd_dkv_kernel(const T* __restrict__ 
                     const typename MM::frag qc = AT<T>::template colk_accs<S>(Qs[cur], pr * 32, dt * 16, lane);
 #pragma unroll
                     for (int j = 0; j < NKW; ++j) {
-                        dvt[j][dt] = MM::mma(oc, pf[j], dvt[j][dt]);
-                        dkt[j][dt] = MM::mma(qc, sf[j], dkt[j][dt]);
+                        if constexpr (BLOCK_SUMS) {
+                            dvb[j][dt] = MM::mma(oc, pf[j], dvb[j][dt]);
+                            dkb[j][dt] = MM::mma(qc, sf[j], dkb[j][dt]);
+                        } else {
+                            dvt[j][dt] = MM::mma(oc, pf[j], dvt[j][dt]);
+                            dkt[j][dt] = MM::mma(qc, sf[j], dkt[j][dt]);
+                        }
                     }
                 }
             });
+        }
+        if constexpr (BLOCK_SUMS) {
+#pragma unroll
+            for (int j = 0; j < NKW; ++j)
+#pragma unroll
+                for (int dt = 0; dt < 4; ++dt) { dvt[j][dt] += dvb[j][dt]; dkt[j][dt] += dkb[j][dt]; }
         }
         if (more) {
             QIO::store(Qs[cur ^ 1], rq_, tid);
@@ -529,6 +584,13 @@ __global__ __launch_bounds__(NT) void attn_bwd_dq_kernel(const T* __restrict__ q
     typedef Mma<T> MM;
     typedef ACfg<T> AC;
     constexpr int RS = AC::RS, KVB = AC::KVB, NKT = KVB / 16, QROWS = 64 * NQ;
+    constexpr bool BLOCK_SUMS = BlockSums<T>::value;
+    // fp32 only: delta = sum_j P_j dP_j / sum_j P_j from a first sweep over the keys, as the softmax backward defines it, instead of
+    // rowsum(dO * O).  The two are equal in exact arithmetic, but rowsum(dO * O) inherits the rounding of the STORED O times
+    // sum |dO * O|, and dS = P (dP - delta) cancels: on rows whose dQ is small that alone is ~ 10 x the error of torch's fp32
+    // backward (4.6e-5 against 4.3e-6 of the row's maximum at N = 128; a correctly rounded fp32 O already costs 3e-6).  bf16
+    // keeps the one-sweep form: the bf16 rounding of O is part of its policy (tests/attention_fixtures.py, twin_slice_bf16).
+    constexpr bool DELTA_SWEEP = std::is_same<T, float>::value;
     typedef TileIO<T, QROWS> QIO;
     typedef TileIO<T, KVB> KIO;
     __shared__ __attribute__((aligned(16))) T Qs[QROWS * RS];   // Q staging, then dQ output staging
@@ -571,7 +633,7 @@ __global__ __launch_bounds__(NT) void attn_bwd_dq_kernel(const T* __restrict__ q
             const int c = tid + i * NT, row = c / CPR;
             if ((c % CPR) == 0) {
                 dls[row] = s_;
-                if (q0 + row < Nq) delta[((long)b * H + h) * Nq + q0 + row] = s_;
+                if (!DELTA_SWEEP && q0 + row < Nq) delta[((long)b * H + h) * Nq + q0 + row] = s_;
             }
         }
     }
@@ -599,13 +661,22 @@ __global__ __launch_bounds__(NT) void attn_bwd_dq_kernel(const T* __restrict__ q
     // second copy of the body: the full blocks carry no mask arithmetic (the select per score element was half of this loop's VALU
     // instructions).  The mask itself cannot go: a missing key has K = 0, so s = 0 and p = exp2(-lse), which overflows when the
     // row's real scores are all below -128 (base 2) - inf * 0 in the dQ = dS K product would poison the whole row.
+    // FIRST (DELTA_SWEEP only) is the sweep that forms delta: the same scores and dP, summed as P * dP per query, no dQ product;
+    // after its last block it fetches block 0 again for the second sweep.
     int cur = 0;
-    auto block = [&](auto tail_c, const int kb) {
-        constexpr bool TAIL = decltype(tail_c)::value;
-        const bool more = kb + KVB < Nk;
+    // FIRST: this lane's share of sum_j P_j dP_j and of sum_j P_j, in double: on a saturated row delta is one term of size |dP|
+    // and dP - delta cancels to nothing, so delta has to be good to its last fp32 bit - products and sums rounded to fp32 left
+    // 14 x torch's error on such rows at Nk = 4096
+    double dacc[NQ], zacc[NQ];
+#pragma unroll
+    for (int n = 0; n < NQ; ++n) dacc[n] = zacc[n] = 0.f;
+    auto block = [&](auto tail_c, auto first_c, const int kb) {
+        constexpr bool TAIL = decltype(tail_c)::value, FIRST = decltype(first_c)::value;
+        const bool more = FIRST || kb + KVB < Nk;
+        const int nxt = FIRST && kb + KVB >= Nk ? 0 : kb + KVB;
         if (more) {
-            KIO::load(rk_, rk, k_ld, kb + KVB, Nk, tid);
-            KIO::load(rv_, rv, v_ld, kb + KVB, Nk, tid);
+            KIO::load(rk_, rk, k_ld, nxt, Nk, tid);
+            KIO::load(rv_, rv, v_ld, nxt, Nk, tid);
         }
         f32x4 dst[NQ][NKT];                 // dS^T[key = 16t + 4g + r][query]
 #pragma unroll
@@ -614,7 +685,12 @@ __global__ __launch_bounds__(NT) void attn_bwd_dq_kernel(const T* __restrict__ q
 #pragma unroll
             for (int n = 0; n < NQ; ++n) {  // dP starts at -delta: dS = P * (dP - delta) needs no subtraction
                 s[n] = f32x4{0.f, 0.f, 0.f, 0.f};
-                dp[n] = f32x4{ndl[n], ndl[n], ndl[n], ndl[n]};
+                // fp32: dP is formed from zero in BOTH sweeps, so it is bit for bit the dP that delta was summed from, and delta is
+                // subtracted afterwards: on a saturated row delta rounds to dP of the dominant key and dS is exactly 0 there, as in
+                // torch.  An MFMA chain started at -delta rounds at the size of delta (several ulp of |dP|) where the true
+                // difference is 1e-8 of it: 14 x torch's error on such a row.
+                const float d0 = (FIRST || DELTA_SWEEP) ? 0.f : ndl[n];
+                dp[n] = f32x4{d0, d0, d0, d0};
             }
 #pragma unroll
             for (int kk = 0; kk < D / MM::KS; ++kk) {
@@ -636,10 +712,25 @@ __global__ __launch_bounds__(NT) void attn_bwd_dq_kernel(const T* __restrict__ q
                         if (kb + t * 16 + (lane >> 4) * 4 + r >= Nk) pv[0] = 0.f;
                         if (kb + t * 16 + (lane >> 4) * 4 + r + 1 >= Nk) pv[1] = 0.f;
                     }
-                    const f32x2 d2 = pv * f32x2{dp[n][r], dp[n][r + 1]};
-                    dst[n][t][r] = d2[0];
-                    dst[n][t][r + 1] = d2[1];
+                    f32x2 dpd = {dp[n][r], dp[n][r + 1]};
+                    if constexpr (DELTA_SWEEP && !FIRST) dpd += f32x2{ndl[n], ndl[n]};
+                    const f32x2 d2 = pv * dpd;
+                    if constexpr (FIRST) {
+                        dacc[n] += (double)pv[0] * (double)dp[n][r] + (double)pv[1] * (double)dp[n][r + 1];
+                        zacc[n] += (double)pv[0] + (double)pv[1];
+                    } else {
+                        dst[n][t][r] = d2[0];
+                        dst[n][t][r + 1] = d2[1];
+                    }
                 }
+        }
+        if constexpr (!FIRST) {
+        f32x4 dqb[BLOCK_SUMS ? NQ : 1][4];                                       // fp32: this key block's sums (BlockSums)
+        if constexpr (BLOCK_SUMS) {
+#pragma unroll
+            for (int n = 0; n < NQ; ++n)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) dqb[n][i] = f32x4{0.f, 0.f, 0.f, 0.f};
         }
 #pragma unroll
         for (int pr = 0; pr < NKT / 2; ++pr) {
@@ -652,9 +743,19 @@ __global__ __launch_bounds__(NT) void attn_bwd_dq_kernel(const T* __restrict__ q
                 for (int dt = 0; dt < 4; ++dt) {
                     const typename MM::frag kc = AT<T>::template colk_accs<S>(Ks[cur], pr * 32, dt * 16, lane);
 #pragma unroll
-                    for (int n = 0; n < NQ; ++n) dqt[n][dt] = MM::mma(kc, sf[n], dqt[n][dt]);
+                    for (int n = 0; n < NQ; ++n) {
+                        if constexpr (BLOCK_SUMS) dqb[n][dt] = MM::mma(kc, sf[n], dqb[n][dt]);
+                        else dqt[n][dt] = MM::mma(kc, sf[n], dqt[n][dt]);
+                    }
                 }
             });
+        }
+        if constexpr (BLOCK_SUMS) {
+#pragma unroll
+            for (int n = 0; n < NQ; ++n)
+#pragma unroll
+                for (int dt = 0; dt < 4; ++dt) dqt[n][dt] += dqb[n][dt];
+        }
         }
         if (more) {
             KIO::store(Ks[cur ^ 1], rk_, tid);
@@ -664,8 +765,26 @@ __global__ __launch_bounds__(NT) void attn_bwd_dq_kernel(const T* __restrict__ q
         cur ^= 1;
     };
     const int nfull = Nk / KVB * KVB;
-    for (int kb = 0; kb < nfull; kb += KVB) block(std::false_type{}, kb);
-    if (nfull < Nk) block(std::true_type{}, nfull);
+    if constexpr (DELTA_SWEEP) {
+        for (int kb = 0; kb < nfull; kb += KVB) block(std::false_type{}, std::true_type{}, kb);
+        if (nfull < Nk) block(std::true_type{}, std::true_type{}, nfull);
+#pragma unroll
+        for (int n = 0; n < NQ; ++n) {      // the four lane groups hold the keys 4g .. 4g + 3 of every 16: add them (same order on every lane)
+            double dd = dacc[n], z = zacc[n];
+            dd += __shfl_xor(dd, 16, 64);
+            z += __shfl_xor(z, 16, 64);
+            dd += __shfl_xor(dd, 32, 64);
+            z += __shfl_xor(z, 32, 64);
+            // P = exp2(s - lse) sums to 1 only up to the rounding of the saved lse (~ 1e-6): dividing by the sum that was actually
+            // formed takes that common factor out of delta, which matters on saturated rows (P_max -> 1, dP_max - delta -> 0)
+            const int qi = q0 + (wave * NQ + n) * 16 + (lane & 15);
+            const float d = qi < Nq ? (float)(dd / z) : 0.f;
+            ndl[n] = -d;
+            if (lane < 16 && qi < Nq) delta[((long)b * H + h) * Nq + qi] = d;     // for the dK / dV kernel
+        }
+    }
+    for (int kb = 0; kb < nfull; kb += KVB) block(std::false_type{}, std::false_type{}, kb);
+    if (nfull < Nk) block(std::true_type{}, std::false_type{}, nfull);
 #pragma unroll
     for (int n = 0; n < NQ; ++n) stage_t<T>(Qs + (wave * NQ + n) * 16 * RS, dqt[n], scale, lane);
     __syncthreads();
@@ -696,6 +815,10 @@ __global__ void attn_dkv_reduce_kernel(const float* __restrict__ ws, T* __restri
     o[0] = from_f32<T>(a.x); o[1] = from_f32<T>(a.y); o[2] = from_f32<T>(a.z); o[3] = from_f32<T>(a.w);
 }
 
+// What the calling thread's last pdmk_attn_fwd / pdmk_attn_bwd launched (pdmk_attn_last_forms): rows-per-wave form of the
+// forward, of dQ and of dK/dV (1 = 16 rows per wave, 2 = 32), and the query split of dK/dV.  Host bookkeeping only.
+thread_local int g_fwd_form = 0, g_dq_form = 0, g_dkv_form = 0, g_nsplit = 0;
+
 template <typename T> bool aligned_ok(const void* p, long bs, int ld, long nrows) {
     constexpr int CH = ACfg<T>::CH;
     return (((uintptr_t)p) & 15) == 0 && (bs % CH) == 0 && (ld % CH) == 0 &&
@@ -712,6 +835,7 @@ int attn_fwd(const void* q, const void* k, const void* v, void* o, float* lse, i
         hipLaunchKernelGGL((attn_fwd_kernel<T, 1, true>), dim3((Nq + 63) / 64, H, B), dim3(NT), 0, st, (const T*)q, (const T*)k,
                            (const T*)v, (T*)o, lse, H, Nq, Nk, q_bs, q_ld, k_bs, k_ld, v_bs, v_ld, o_bs, o_ld, scale * LOG2E);
         PDMK_CHECK_LAUNCH();
+        g_fwd_form = 1;
         return 0;
     }
     // 32 queries per wave when there are enough query blocks to fill the chip that way, else 16 (PDMK_ATTN_NQ forces)
@@ -727,6 +851,7 @@ int attn_fwd(const void* q, const void* k, const void* v, void* o, float* lse, i
                            (const T*)v, (T*)o, lse, H, Nq, Nk, q_bs, q_ld, k_bs, k_ld, v_bs, v_ld, o_bs, o_ld, scale * LOG2E);
     }
     PDMK_CHECK_LAUNCH();
+    g_fwd_form = wide ? 2 : 1;
     return 0;
 }
 
@@ -747,7 +872,8 @@ int attn_bwd(const void* q, const void* k, const void* v, const void* o, const v
     if (forced < 0 || dynamic) { const char* e = getenv("PDMK_ATTN_NQ"); forced = e ? atoi(e) : 0; }
 #define PDMK_DQ_ARGS (const T*)q, (const T*)k, (const T*)v, (const T*)o, (const T*)d_o, lse, delta, (T*)dq, H, Nq, Nk, q_bs, q_ld, k_bs, k_ld, \
                      v_bs, v_ld, o_bs, o_ld, dq_bs, dq_ld, scale, scale * LOG2E
-    // 32 rows per wave in the backward kernels too, by the forward's rule (bf16 only: the fp32 forms need > 256 registers).  With
+    // 32 rows per wave in the backward kernels too, by the forward's rule (bf16 only: the fp32 forms need > 256 registers, so
+    // they are not instantiated and a forced wide form is ignored for fp32 - DESIGN.md "Attention: dispatch forms").  With
     // the MFMA results in ordinary VGPRs (Makefile) the wide forms are the faster ones at N = 4096 (one MI355X, B = 8, H = 5,
     // dQ + dK/dV: 791 -> 649 us; with AGPR accumulators they were the slower ones, 853 vs 874); PDMK_ATTN_NQ_DQ / _DKV force one
     static int f_dq = -1, f_dkv = -1;
@@ -764,10 +890,12 @@ int attn_bwd(const void* q, const void* k, const void* v, const void* o, const v
 #else
     const bool auto_wide = true;
 #endif
-    const bool wide_dq = want_dq ? want_dq == 2 : (auto_wide && is_bf16 && (long)((Nq + 127) / 128) * H * B >= 384 && Nk >= 256);
-    const bool wide_dkv = want_dkv ? want_dkv == 2 : (auto_wide && is_bf16 && (long)((Nk + 127) / 128) * H * B >= 384 && Nq >= 256);
+    const bool wide_dq = is_bf16 && (want_dq ? want_dq == 2 : (auto_wide && (long)((Nq + 127) / 128) * H * B >= 384 && Nk >= 256));
+    const bool wide_dkv = is_bf16 && (want_dkv ? want_dkv == 2 : (auto_wide && (long)((Nk + 127) / 128) * H * B >= 384 && Nq >= 256));
+    // (BW = 2 exactly when T is bf16: `if constexpr` keeps the fp32 wide forms out of the library)
+    constexpr int BW = is_bf16 ? 2 : 1;
     if (wide_dq)
-        hipLaunchKernelGGL((attn_bwd_dq_kernel<T, 2>), dim3((Nq + 127) / 128, H, B), dim3(NT), 0, st, PDMK_DQ_ARGS);
+        hipLaunchKernelGGL((attn_bwd_dq_kernel<T, BW>), dim3((Nq + 127) / 128, H, B), dim3(NT), 0, st, PDMK_DQ_ARGS);
     else
         hipLaunchKernelGGL((attn_bwd_dq_kernel<T, 1>), dim3((Nq + 63) / 64, H, B), dim3(NT), 0, st, PDMK_DQ_ARGS);
 #undef PDMK_DQ_ARGS
@@ -777,7 +905,7 @@ int attn_bwd(const void* q, const void* k, const void* v, const void* o, const v
     if (ws && kblocks * H * B < 128 && qblocks >= 8) {
         nsplit = min(min(32, qblocks / 4), (256 + kblocks * H * B - 1) / (kblocks * H * B));
         const long per = (long)2 * B * H * Nk * 64;
-        if (nsplit > ws_elems / per) nsplit = (int)(ws_elems / per);
+        if (nsplit > ws_elems / per) nsplit = max(1, (int)(ws_elems / per));
     }
 #define PDMK_DKV_ARGS (const T*)q, (const T*)k, (const T*)v, (const T*)d_o, lse, delta, (T*)dk, (T*)dv, H, Nq, Nk, q_bs, q_ld, \
                       k_bs, k_ld, v_bs, v_ld, o_bs, o_ld, dk_bs, dk_ld, dv_bs, dv_ld, scale, scale * LOG2E
@@ -788,13 +916,16 @@ int attn_bwd(const void* q, const void* k, const void* v, const void* o, const v
         hipLaunchKernelGGL(attn_dkv_reduce_kernel<T>, dim3((unsigned)((items + NT - 1) / NT)), dim3(NT), 0, st, ws, (T*)dk,
                            (T*)dv, B, H, Nk, nsplit, dk_bs, dk_ld, dv_bs, dv_ld);
     } else if (wide_dkv) {         // 32 keys per wave (242 VGPRs, 65 KiB LDS)
-        hipLaunchKernelGGL((attn_bwd_dkv_kernel<T, false, 2>), dim3((Nk + 127) / 128, H, B), dim3(NT), 0, st, PDMK_DKV_ARGS,
+        hipLaunchKernelGGL((attn_bwd_dkv_kernel<T, false, BW>), dim3((Nk + 127) / 128, H, B), dim3(NT), 0, st, PDMK_DKV_ARGS,
                            nullptr, 1);
     } else {
         hipLaunchKernelGGL((attn_bwd_dkv_kernel<T, false, 1>), dim3(kblocks, H, B), dim3(NT), 0, st, PDMK_DKV_ARGS, nullptr, 1);
     }
 #undef PDMK_DKV_ARGS
     PDMK_CHECK_LAUNCH();
+    g_dq_form = wide_dq ? 2 : 1;
+    g_dkv_form = nsplit > 1 ? 1 : (wide_dkv ? 2 : 1);
+    g_nsplit = nsplit;
     return 0;
 }
 
@@ -840,4 +971,8 @@ extern "C" int pdmk_attn_bwd(const void* q, const void* k, const void* v, const 
         return attn_bwd<float>(q, k, v, o, d_o, lse, delta, dq, dk, dv, B, H, Nq, Nk, q_bs, q_ld, k_bs, k_ld, v_bs,
                                v_ld, o_bs, o_ld, dq_bs, dq_ld, dk_bs, dk_ld, dv_bs, dv_ld, scale, ws, (long)ws_elems, st);
     return -2;
+}
+
+extern "C" int pdmk_attn_last_forms(void) {
+    return g_fwd_form | (g_dq_form << 4) | (g_dkv_form << 8) | (g_nsplit << 12);
 }

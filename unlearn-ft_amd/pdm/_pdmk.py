@@ -125,6 +125,7 @@ _SIGS = {
     "pdmk_groupnorm_bwd_part_workspace_bytes": ([i32, i32], i64),
     "pdmk_layernorm_bwd_part_workspace_bytes": ([i32, i32], i64),
     "pdmk_attn_bwd_workspace_bytes": ([i32, i32, i32, i32], i64),
+    "pdmk_attn_last_forms": ([], i32),
     "pdmk_plan_export": ([C.c_char_p], i32),
     "pdmk_plan_import": ([C.c_char_p], i32),
     "pdmk_plan_size": ([], i32),
@@ -470,6 +471,13 @@ def zero_(t):
     return t
 
 
+def attn_last_forms():
+    """(forward form, dQ form, dK/dV form, nsplit) of the calling thread's last attn_fwd[_causal] / attn_bwd: forms are 1 (16
+    rows per wave) or 2 (32), nsplit the query split of dK/dV that ran."""
+    w = int(_lib.pdmk_attn_last_forms())
+    return w & 15, (w >> 4) & 15, (w >> 8) & 15, w >> 12
+
+
 def last_candidate():
     """Candidate id of the calling thread's last pdmk_gemm launch (0 = K-step-32 kernels, 1.. = ring / halo shapes)."""
     return int(_lib.pdmk_gemm_last_candidate())
@@ -750,8 +758,11 @@ def attn_fwd(q, k, v, o, lse, B, H, Nq, Nk, qs, ks, vs, os_, scale):
                             vs[1], os_[0], os_[1], scale, dt(q), _st()), "pdmk_attn_fwd")
 
 
-def attn_bwd(q, k, v, o, do, lse, delta, dq, dk, dv, B, H, Nq, Nk, qs, ks, vs, os_, dqs, dks, dvs, scale):
+def attn_bwd(q, k, v, o, do, lse, delta, dq, dk, dv, B, H, Nq, Nk, qs, ks, vs, os_, dqs, dks, dvs, scale, ws_elems=None):
+    """ws_elems: floats of dK/dV split workspace to pass (None = what the library asks for, 0 = none; tests of the clamp)."""
     nws = _ws_bytes(_lib.pdmk_attn_bwd_workspace_bytes(B, H, Nq, Nk)) // 4   # > 0: few keys, the dK/dV pass also splits the queries
+    if ws_elems is not None:
+        nws = min(nws, int(ws_elems))
     ws = torch.empty(nws, device=q.device, dtype=torch.float32) if nws else None
     _chk(_lib.pdmk_attn_bwd(_p(q), _p(k), _p(v), _p(o), _p(do), _p(lse), _p(delta), _p(dq), _p(dk), _p(dv), B, H, Nq,
                             Nk, qs[0], qs[1], ks[0], ks[1], vs[0], vs[1], os_[0], os_[1], dqs[0], dqs[1], dks[0],
