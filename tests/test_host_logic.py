@@ -50,6 +50,22 @@ def test_workspace_queries_and_plan_file_roundtrip(tmp_path):
     assert k.plan_size() == 0
 
 
+def test_gemm_candidate_ids_name_the_pinned_kernels():
+    """Candidate ids are what plan files, tests and tools name GEMM kernels by: every id of every family names the kernel
+    instantiation listed in tests/golden/gemm_candidates.json, and the id behind the last one does not exist.  A new
+    candidate appends a line to that file."""
+    import json
+    import pytest
+    from pdm import _pdmk as k
+    golden = json.load(open(os.path.join(ROOT, "tests", "golden", "gemm_candidates.json")))
+    assert sorted(golden) == ["A_COLK,B_COLK", "A_COLK,B_COLK_CONV", "A_CONV,B_ROWK", "A_ROWK,B_ROWK"]
+    for fam, names in golden.items():
+        a, b = (getattr(k, m) for m in fam.split(","))
+        assert [k.candidate_name(a, b, i) for i in range(len(names))] == names, fam
+        with pytest.raises(k.PdmkError):
+            k.candidate_name(a, b, len(names))
+
+
 def test_partial_dims_queries_and_deferred_queues_chunk_by_32(monkeypatch):
     """The geometry queries of the deferred reductions answer without a GPU and agree with the workspace queries; the two
     queues hand the library at most 32 items per launch, keep their slabs alive until then, and the slab queue reports

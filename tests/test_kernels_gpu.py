@@ -1142,7 +1142,10 @@ def _group_call(k, recs_fn, n_expected, cand, monkey_env):
         del os.environ["PDMK_GROUP_CFG"]
 
 
-@pytest.mark.parametrize("cand", [1, 3, 6, 7, 9, 12, 17, 19])
+RING_CANDS = [1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 17, 18, 19]      # every row of the ring table (13-16: the halo convs)
+
+
+@pytest.mark.parametrize("cand", RING_CANDS)
 def test_gemm_group_linear_bit_equal_to_separate(dev, force_cfg, cand):
     """pdmk_gemm_group: 2, 3 and 4 independent Linear problems of DIFFERENT ragged shapes (bias / residual / accumulate /
     strided rows / fused GEGLU mixed) in one launch of ring candidate `cand` == the same problems launched one by one with
@@ -1192,9 +1195,9 @@ def test_gemm_group_linear_bit_equal_to_separate(dev, force_cfg, cand):
     close(grp[0][:, :N].float(), ref, 2e-2, "group vs fp32")
 
 
-@pytest.mark.parametrize("cand", [13, 14, 15, 16, 3, 12])
+@pytest.mark.parametrize("cand", [13, 14, 15, 16] + RING_CANDS)
 def test_gemm_group_conv_bit_equal_to_separate(dev, force_cfg, cand):
-    """Grouped stride-1 3x3 convs (halo kernels 13-16; ring kernels 3 / 12 gather per tap): a dense and a pruned layer of one
+    """Grouped stride-1 3x3 convs (halo kernels 13-16; the ring kernels gather per tap): a dense and a pruned layer of one
     level, different channel counts, per-image time-embedding row / residual - one launch == separate launches."""
     from pdm import _pdmk as k
     torch.manual_seed(100 + cand)

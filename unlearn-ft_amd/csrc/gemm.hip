@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "common.h"
+#include "gemm_candidates.h"
 #include <algorithm>
 
 namespace {
@@ -480,13 +481,6 @@ template <typename T> int launch(const pdmk_gemm_args& g, hipStream_t st) {
 
 }  // namespace
 
-int pdmk_gemm_dma_launch(const pdmk_gemm_args& g, hipStream_t st, long a_bytes, long b_bytes);   // gemm_dma.hip
-int pdmk_gemm_ring_launch(const pdmk_gemm_args& g, hipStream_t st, long a_bytes, long b_bytes, int id);  // gemm_ring.hip
-int pdmk_gemm_ring_num_configs();
-int pdmk_gemm_ring_pick(const pdmk_gemm_args& g);
-int pdmk_wgrad_ring_launch(const pdmk_gemm_args& g, hipStream_t st, long a_bytes, long b_bytes, int id);
-int pdmk_wgrad_ring_num_configs();
-
 static int env_int(const char* name, int def, int* cache) {     // cached unless PDMK_ENV_DYNAMIC is set (A/B tools)
     static int dynamic = -1;
     if (dynamic < 0) dynamic = getenv("PDMK_ENV_DYNAMIC") ? 1 : 0;
@@ -684,6 +678,23 @@ bool scratch_check() {
     return true;
 }
 
+// microseconds per repetition of fn(), best of two rounds of `reps`
+template <typename F> float time_us(F fn, hipStream_t st, hipEvent_t e0, hipEvent_t e1, int reps = 3) {
+    if (fn() != 0) { (void)hipGetLastError(); return 1e30f; }
+    float best = 1e30f;
+    for (int round = 0; round < 2; ++round) {        // two rounds, keep the faster: one-off stalls must not pick the plan
+        (void)hipEventRecord(e0, st);
+        for (int r = 0; r < reps; ++r)
+            if (fn() != 0) { (void)hipGetLastError(); return 1e30f; }
+        (void)hipEventRecord(e1, st);
+        if (hipEventSynchronize(e1) != hipSuccess) { (void)hipGetLastError(); return 1e30f; }
+        float ms = 0.f;
+        (void)hipEventElapsedTime(&ms, e0, e1);
+        if (ms < best) best = ms;
+    }
+    return best * 1000.f / reps;
+}
+
 // time `reps` launches of candidate `id` (plus, for split-K, the workspace clear and the finish pass) in microseconds
 float time_candidate(const pdmk_gemm_args& a, hipStream_t st, int id, float* ws, void* fin_out, hipEvent_t e0, hipEvent_t e1) {
     static const int reps = getenv("PDMK_TUNE_REPS") ? std::max(1, atoi(getenv("PDMK_TUNE_REPS"))) : 3;     // (A/B knob: 8 / 20 give the same step as 3)
@@ -696,19 +707,7 @@ float time_candidate(const pdmk_gemm_args& a, hipStream_t st, int id, float* ws,
         }
         return launch_candidate(a, st, id);
     };
-    if (once() != 0) { (void)hipGetLastError(); return 1e30f; }
-    float best = 1e30f;
-    for (int round = 0; round < 2; ++round) {        // two rounds, keep the faster: one-off stalls must not pick the plan
-        (void)hipEventRecord(e0, st);
-        for (int r = 0; r < reps; ++r)
-            if (once() != 0) { (void)hipGetLastError(); return 1e30f; }
-        (void)hipEventRecord(e1, st);
-        if (hipEventSynchronize(e1) != hipSuccess) { (void)hipGetLastError(); return 1e30f; }
-        float ms = 0.f;
-        (void)hipEventElapsedTime(&ms, e0, e1);
-        if (ms < best) best = ms;
-    }
-    float us = best * 1000.f / reps;
+    float us = time_us(once, st, e0, e1, reps);
     // weight-gradient slabs: their sum is deferred to one grouped launch for many weights (pdmk_splitk_finish_group); it is
     // priced here by its traffic at 4 TB/s instead of being launched per candidate
     if (a.a_mode == PDMK_A_COLK && a.accumulate == 2) us += (float)(a.splitk + 1) * (float)a.M * (float)a.N * 4.f / 4.0e6f;
@@ -758,7 +757,7 @@ int tune_cfg(const pdmk_gemm_args& g, hipStream_t st, int sk, float* t_out) {
 
 int heuristic_cfg(const pdmk_gemm_args& g) {
     if (!ring_mode()) return 0;
-    if (g.a_mode == PDMK_A_COLK) return (g.b_mode == PDMK_B_COLK_CONV || g.conv_mode >= 5) ? 2 : 0;   // what the tuned plans pick most often
+    if (g.a_mode == PDMK_A_COLK) return (g.b_mode == PDMK_B_COLK_CONV || g.conv_mode >= 5) ? pdmk_cand::kWgradHeuristic : 0;   // what the tuned plans pick most often
     return 1 + pdmk_gemm_ring_pick(g);
 }
 
@@ -849,8 +848,6 @@ static int validate_args(const pdmk_gemm_args& g) {
     return 0;
 }
 
-int pdmk_gemm_rowblock_launch(const pdmk_gemm_args& g, hipStream_t st, long a_bytes, long b_bytes, int id, bool dry);   // gemm_rowblock.hip
-int pdmk_gemm_rowblock_num_configs();
 // LayerNorm prologue (pdmk_gemm_args.ln_gamma): the row-block candidate whose register image holds K, or -1
 static int ln_candidate(const pdmk_gemm_args& g, long* ab, long* bb) {
     if (g.dtype != PDMK_BF16 || g.a_mode != PDMK_A_ROWK || g.b_mode != PDMK_B_ROWK || g.splitk > 1 || g.colstat || g.out_f32 ||
@@ -877,7 +874,7 @@ extern "C" int pdmk_gemm(const pdmk_gemm_args* a, pdmk_stream stream) {
         const int id = ln_candidate(g, &ab, &bb);
         if (id < 0) return -2;
         const int rc = pdmk_gemm_rowblock_launch(g, st, ab, bb, id, false);
-        g_last_candidate = 1 + pdmk_gemm_ring_num_configs() - pdmk_gemm_rowblock_num_configs() + id;
+        g_last_candidate = pdmk_cand::rowblock_first() + id;
         return rc == 1 ? -2 : rc;
     }
     if (!(ring_eligible(g) && (g.K % 8) == 0) && !wgrad_eligible(g)) return launch_legacy(g, st);
@@ -920,8 +917,6 @@ extern "C" int pdmk_gemm(const pdmk_gemm_args* a, pdmk_stream stream) {
 // pdmk_gemm_group: several independent problems in one launch (include/pdmk.h).  A group is launched with ONE kernel shape;
 // which one - or whether the members go out one by one after all - is measured once per group of shapes and cached.
 // ---------------------------------------------------------------------------------------------------------------
-int pdmk_gemm_ring_group_launch(const pdmk_gemm_args* gs, int n, hipStream_t st, const long* a_bytes, const long* b_bytes, int id);
-int pdmk_wgrad_ring_group_launch(const pdmk_gemm_args* gs, int n, hipStream_t st, const long* a_bytes, const long* b_bytes, int id);
 static int group_mode() { static int c = INT32_MIN; return env_int("PDMK_GEMM_GROUP", 1, &c); }   // 0: always one by one
 static int forced_group() { static int c = INT32_MIN; return env_int("PDMK_GROUP_CFG", -1, &c); } // >= 1: group with that candidate (tests)
 
@@ -953,23 +948,6 @@ int group_launch(const pdmk_gemm_args* a, int n, hipStream_t st, int id) {
     if (id <= 0) return 1;
     if (a[0].a_mode == PDMK_A_COLK) return pdmk_wgrad_ring_group_launch(a, n, st, ab, bb, id - 1);
     return pdmk_gemm_ring_group_launch(a, n, st, ab, bb, id - 1);
-}
-
-// microseconds per repetition of fn(), best of two rounds of `reps`
-template <typename F> float time_us(F fn, hipStream_t st, hipEvent_t e0, hipEvent_t e1, int reps = 3) {
-    if (fn() != 0) { (void)hipGetLastError(); return 1e30f; }
-    float best = 1e30f;
-    for (int round = 0; round < 2; ++round) {
-        (void)hipEventRecord(e0, st);
-        for (int r = 0; r < reps; ++r)
-            if (fn() != 0) { (void)hipGetLastError(); return 1e30f; }
-        (void)hipEventRecord(e1, st);
-        if (hipEventSynchronize(e1) != hipSuccess) { (void)hipGetLastError(); return 1e30f; }
-        float ms = 0.f;
-        (void)hipEventElapsedTime(&ms, e0, e1);
-        if (ms < best) best = ms;
-    }
-    return best * 1000.f / reps;
 }
 
 // grouped candidate for these members (ids = their own plans), or -1: launch them one by one.  Caller checked can_tune().
@@ -1019,11 +997,11 @@ int tune_group(const pdmk_gemm_args* a, int n, const int* ids, hipStream_t st) {
     for (int i = 0; i < n; ++i) cands[nc++] = ids[i];
     cands[nc++] = heuristic_cfg(a[0]);
     if (a[0].a_mode == PDMK_A_CONV)
-        for (int h = 0; h < 4; ++h) cands[nc++] = 1 + 12 + h;            // 1 + kNumBase + h (gemm_ring.hip)
+        for (int h = 0; h < pdmk_cand::kHaloCount; ++h) cands[nc++] = pdmk_cand::kHaloFirst + h;
     // Linear weight gradients (the block groups of pdm._pdmk.wgrad_group): every ring tile shape - a member's own plan was timed
     // with that member alone on the chip, where small tiles win by workgroup count; a full group has the workgroups
     if (a[0].a_mode == PDMK_A_COLK && a[0].b_mode == PDMK_B_COLK)
-        for (int w = 0; w < 5; ++w) cands[nc++] = 1 + w;                 // kWCfgs (gemm_ring.hip)
+        for (int w = 0; w < pdmk_cand::kWgradRingCount; ++w) cands[nc++] = 1 + w;
     for (int i = 0; i < nc; ++i) {
         bool seen = cands[i] <= 0;
         for (int j = 0; j < i; ++j) seen = seen || cands[j] == cands[i];
@@ -1118,8 +1096,6 @@ extern "C" int pdmk_gemm_group(const pdmk_gemm_args* a, int n, pdmk_stream strea
 /* Candidate the calling thread's last pdmk_gemm used (0 = K-step-32 kernels, 1.. = LDS-DMA ring shapes) and the kernel
  * symbol a profiler shows for it; measurement only (bench.py labels its HIP-event timings with these). */
 extern "C" int pdmk_gemm_last_candidate(void) { return g_last_candidate; }
-int pdmk_gemm_ring_name(int id, int conv, char* buf, int n);    // gemm_ring.hip
-int pdmk_wgrad_ring_name(int id, int conv, char* buf, int n);
 extern "C" int pdmk_gemm_candidate_name(int a_mode, int b_mode, int id, char* buf, int n) {
     if (!buf || n <= 0) return -1;
     if (id <= 0) {

@@ -9,6 +9,7 @@
 //     ds_read_b128 fragment reads are removed by XOR-swizzling the 16-byte chunk index with (row>>2)&3 on the SOURCE
 //     side (per-lane global address) and on the read side.
 #include "common.h"
+#include "gemm_candidates.h"
 
 #ifdef PDMK_STAMPS      // diagnostic build only: per-workgroup phase timestamps (s_memtime), read back by tools/
 __device__ unsigned long long pdmk_stamps[8192 * 6];

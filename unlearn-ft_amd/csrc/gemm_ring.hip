@@ -10,6 +10,7 @@
 //   * LDS image is lane-linear (what the DMA writes); ds_read_b128 bank conflicts are removed by XOR-ing the 16-byte
 //     chunk index with (row>>1)&7 on the SOURCE address and on the fragment reads (same involution on both sides).
 #include "common.h"
+#include "gemm_candidates.h"
 
 #include <stdio.h>
 #include <stdlib.h>
@@ -20,22 +21,11 @@
 #ifndef PDMK_HALO_PAIRS
 #define PDMK_HALO_PAIRS 1     // halo conv, rings of >= 4 slots: two taps per barrier (0: one, as in round 1)
 #endif
-#ifndef PDMK_RING_SPLIT_ISSUE
-#define PDMK_RING_SPLIT_ISSUE 0   // ring GEMM: a stage's DMA issue split by wave half (igemm_ring_body).  Measured (round 4): +-0 on the C x C shapes
-                                  // in isolation, -0.5 % for the step (187.8 -> 186.9 images/s) - unlike the halo conv, whose events carry 6-8 pieces
-                                  // per wave against 20-40 MFMAs, a ring stage is 3-5 pieces against 20 - so it is OFF
-#endif
 #ifndef PDMK_HALO_SPLIT_ISSUE
-#define PDMK_HALO_SPLIT_ISSUE 1   // ... and the event's DMA issue split by wave half (conv_halo_body); 2 = four issue points (waves 2, 3 / 6, 7 between
-                                  // a tap's two MFMA groups): measured 3-9 % SLOWER than 1 (64^2 320 -> 320: 71.2 -> 77.5 us), off
+#define PDMK_HALO_SPLIT_ISSUE 1   // ... and the event's DMA issue split by wave half (conv_halo_body; 0: all waves before the taps)
 #endif
-
-#ifndef PDMK_PRIO
-#define PDMK_PRIO 0               // wave priority experiments (MI355X_MICROARCH.md "Two waves per SIMD"): 1 = ONE s_setprio 1 for the second-dispatched
-                                  // half of the workgroup (waves 4-7) before the K-loop; 2 = s_setprio 1 / 0 around every MFMA cluster.
-                                  // Measured (round 4, ring + halo + weight-gradient bodies, same box, two builds): 193.4 images/s (0) vs 192.8 (1)
-                                  // vs 192.5 (2) - nothing to gain for these loops, OFF
-#endif
+// Wave priority (removed switch; MI355X_MICROARCH.md "Two waves per SIMD"): s_setprio 1 for waves 4-7 before the K-loop gave 192.8
+// images/s, s_setprio 1 / 0 around every MFMA cluster 192.5, against 193.4 without (round 4) - nothing to gain for these loops.
 
 namespace pdmk_ring {
 
@@ -104,11 +94,6 @@ __device__ __forceinline__ int conv_src_pixel(const ConvGeom& g, int b, int oy, 
 }
 
 __device__ __forceinline__ void wait_vmcnt_dyn(int n) { pdmk_wait_vmcnt(n); }   // n is wave-uniform
-__device__ __forceinline__ void prio_static(int wave) {       // wave is an SGPR value (readfirstlane): a scalar branch around one s_setprio
-    if (PDMK_PRIO == 1 && wave >= 4) __builtin_amdgcn_s_setprio(1);
-}
-#define PDMK_PRIO_UP() do { if (PDMK_PRIO == 2) __builtin_amdgcn_s_setprio(1); } while (0)
-#define PDMK_PRIO_DOWN() do { if (PDMK_PRIO == 2) __builtin_amdgcn_s_setprio(0); } while (0)
 
 // Epilogue shared by the ring kernels (same contract as gemm.hip): accumulators -> LDS staging image (64 rows per pass) ->
 // 16-byte rows of C with bias / rowvec / residual / accumulate fused, or fp32 atomics for split-K launches.
@@ -496,7 +481,6 @@ __device__ __forceinline__ void igemm_ring_body(const pdmk_gemm_args& g, unsigne
         if (kt0 + s < kt1) issue(s);
 
     int slot = 0;
-    prio_static(wave);
     for (int kt = kt0; kt < kt1; ++kt) {
         // younger K-steps already in flight: STAGES - 2 except in the last steps.  Immediate waits where the count is known at
         // compile time (always for the two-slot rings, in the steady state for the deep ones, per wave class): the computed
@@ -510,11 +494,10 @@ __device__ __forceinline__ void igemm_ring_body(const pdmk_gemm_args& g, unsigne
             wait_vmcnt_dyn(min(STAGES - 2, kt1 - 1 - kt) * ndma);
         }
         __builtin_amdgcn_s_barrier();
-        // the stage's DMA instructions go into the slot read LAST step: anywhere inside this step will do.  Waves 0-3 issue them
-        // first, their SIMD partners 4-7 between the two halves of the step's MFMAs (PDMK_RING_SPLIT_ISSUE; as in conv_halo_body:
-        // eight waves in the memory pipe together right behind the barrier leave the matrix pipes idle)
-        const bool late = PDMK_RING_SPLIT_ISSUE && wave >= 4;        // wave-uniform
-        if (!late && kt + STAGES - 1 < kt1) issue(slot == 0 ? STAGES - 1 : slot - 1);
+        // the stage's DMA instructions go into the slot read LAST step: anywhere inside this step will do.  (Removed switch: waves
+        // 4-7 issuing between the two halves of the step's MFMAs, as in conv_halo_body, was +-0 on the C x C shapes and -0.5 % for
+        // the step, 187.8 -> 186.9 images/s, round 4: a ring stage is 3-5 pieces per wave against 20 MFMAs, a halo event 6-8.)
+        if (kt + STAGES - 1 < kt1) issue(slot == 0 ? STAGES - 1 : slot - 1);
         const unsigned char* sa = smem + slot * SLOT;
         const unsigned char* sb = sa + A_BYTES;
 #pragma unroll
@@ -525,22 +508,14 @@ __device__ __forceinline__ void igemm_ring_body(const pdmk_gemm_args& g, unsigne
             for (int i = 0; i < IM; ++i) af[i] = *reinterpret_cast<const bf16x8*>(sa + a_row + fch + i * 2048);
 #pragma unroll
             for (int j = 0; j < NJ; ++j) bf[j] = *reinterpret_cast<const bf16x8*>(sb + b_row + fch + j * 2048);
-            PDMK_PRIO_UP();
 #pragma unroll
             for (int i = 0; i < IM; ++i)
 #pragma unroll
                 for (int j = 0; j < NJ; ++j) acc[i][j] = MM::mma(bf[j], af[i], acc[i][j]);
-            PDMK_PRIO_DOWN();
-            if (kk == 0 && late) {
-                __builtin_amdgcn_sched_barrier(0);
-                if (kt + STAGES - 1 < kt1) issue(slot == 0 ? STAGES - 1 : slot - 1);
-                __builtin_amdgcn_sched_barrier(0);
-            }
         }
         slot = slot + 1 == STAGES ? 0 : slot + 1;
     }
 
-    if (PDMK_PRIO == 1) __builtin_amdgcn_s_setprio(0);
     ring_epilogue<BM, NJ, STAGES * SLOT>(g, wgc, acc, smem, m0, n0);
 }
 
@@ -713,11 +688,10 @@ __device__ __forceinline__ void conv_halo_body(const pdmk_gemm_args& g, unsigned
 
     // one tap: 2 x (IM x NJ) MFMAs out of the patch (shifted rows) and one weight tile
     int ta = ta0, tb = tb0;                                          // tap phase of the block being multiplied
-    auto tap_compute = [&](const unsigned char* pbuf, const unsigned char* sb, int tap, auto&& mid) __attribute__((always_inline)) {
+    auto tap_compute = [&](const unsigned char* pbuf, const unsigned char* sb, int tap) __attribute__((always_inline)) {
         const int toff = NTAPS == 4 ? (ta + (tap >> 1)) * W2 + (tb + (tap & 1)) : (tap / 3) * W2 + (tap % 3);
 #pragma unroll
         for (int kk = 0; kk < 2; ++kk) {
-            if (kk == 1) mid();                      // (an issue point between the tap's two MFMA groups: conv_halo_body's event loop)
             bf16x8 af[IM], bf[NJ];
 #pragma unroll
             for (int i = 0; i < IM; ++i) {
@@ -727,18 +701,15 @@ __device__ __forceinline__ void conv_halo_body(const pdmk_gemm_args& g, unsigned
             const unsigned fch = kk ? fch1 : fch0;
 #pragma unroll
             for (int j = 0; j < NJ; ++j) bf[j] = *reinterpret_cast<const bf16x8*>(sb + b_row + fch + j * 2048);
-            PDMK_PRIO_UP();
 #pragma unroll
             for (int i = 0; i < IM; ++i)
 #pragma unroll
                 for (int j = 0; j < NJ; ++j) acc[i][j] = MM::mma(bf[j], af[i], acc[i][j]);
-            PDMK_PRIO_DOWN();
         }
         __builtin_amdgcn_sched_barrier(0);            // no cross-tap code motion: keeps fragment live ranges to one tap
     };
 
     const int nsteps = cb1 > cb0 ? (cb1 - cb0) * NTAPS : 0;
-    prio_static(wave);
     if (BSTAGES >= 4 && PDMK_HALO_PAIRS) {
         // ---- two taps per barrier (rings of >= 4 slots: the 128-row tiles).  A K-step of an 8-wave workgroup has ~480 cycles
         // of fixed cost (wait + barrier rendezvous + restart of the MFMA stream) next to 640 cycles of MFMA work
@@ -805,19 +776,16 @@ __device__ __forceinline__ void conv_halo_body(const pdmk_gemm_args& g, unsigned
                 // (measured, tools/conv_ab.py, B = 8: the 128 x 160 tiles gain 2.5-12 % - 64^2 320 -> 320 79.1 -> 70.5 us, 32^2 640 -> 640
                 // 62.6 -> 59.4 - the 128 x 128 tiles LOSE 1-9 % - 960 -> 320 210.7 -> 229.7 us: with 16 MFMAs per tap and two pieces per
                 // weight tile their partners finish the first tap before the early half is out of the memory pipe - so NJ = 5 only)
-                // issue point of this wave: 0 = before the first tap, 2 = between the taps (PDMK_HALO_SPLIT_ISSUE >= 1, by wave half);
-                // PDMK_HALO_SPLIT_ISSUE == 2 adds 1 / 3 = between the two MFMA groups of the first / second tap (waves 2, 3 / 6, 7)
-                const int ip = (PDMK_HALO_SPLIT_ISSUE && NJ >= 5 && ne == 2)
-                                   ? ((wave >= 4 ? 2 : 0) + ((PDMK_HALO_SPLIT_ISSUE == 2 && (wave & 2)) ? 1 : 0)) : 0;   // wave-uniform
-                auto nomid = [&]() __attribute__((always_inline)) {};
+                // (removed switch: four issue points - waves 2, 3 / 6, 7 between a tap's two MFMA groups - measured 3-9 % SLOWER than
+                // two, 64^2 320 -> 320: 71.2 -> 77.5 us)
+                // issue point of this wave: 0 = before the first tap, 2 = between the taps (by wave half)
+                const int ip = (PDMK_HALO_SPLIT_ISSUE && NJ >= 5 && ne == 2) ? (wave >= 4 ? 2 : 0) : 0;      // wave-uniform
                 if (ip == 0) issue_all();
-                if (PDMK_HALO_SPLIT_ISSUE == 2) tap_compute(pbuf, bring + slot_c * B_BYTES, t0, [&]() __attribute__((always_inline)) { if (ip == 1) issue_all(); });
-                else tap_compute(pbuf, bring + slot_c * B_BYTES, t0, nomid);
+                tap_compute(pbuf, bring + slot_c * B_BYTES, t0);
                 slot_c = slot_c + 1 == BSTAGES ? 0 : slot_c + 1;
                 if (ip == 2) issue_all();
                 if (ne == 2) {
-                    if (PDMK_HALO_SPLIT_ISSUE == 2) tap_compute(pbuf, bring + slot_c * B_BYTES, t0 + 1, [&]() __attribute__((always_inline)) { if (ip == 3) issue_all(); });
-                    else tap_compute(pbuf, bring + slot_c * B_BYTES, t0 + 1, nomid);
+                    tap_compute(pbuf, bring + slot_c * B_BYTES, t0 + 1);
                     slot_c = slot_c + 1 == BSTAGES ? 0 : slot_c + 1;
                 }
             }
@@ -872,7 +840,7 @@ __device__ __forceinline__ void conv_halo_body(const pdmk_gemm_args& g, unsigned
                         else issue_piece(cb + 1, poff[0], 0);
                     }
                 }
-                tap_compute(pbuf, bring + slot_c * B_BYTES, tap, []() {});
+                tap_compute(pbuf, bring + slot_c * B_BYTES, tap);
                 slot_c = slot_c + 1 == BSTAGES ? 0 : slot_c + 1;
             }
         }
@@ -881,7 +849,6 @@ __device__ __forceinline__ void conv_halo_body(const pdmk_gemm_args& g, unsigned
     // zeros into LDS); the epilogue reuses that LDS as its staging image, so drain them explicitly - a late zero write
     // must not land on a staged tile, and what __syncthreads() happens to emit is not a contract
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (PDMK_PRIO == 1) __builtin_amdgcn_s_setprio(0);
     __builtin_amdgcn_s_barrier();
     if (NTAPS == 4 && !dgr) {
         if (tw == W) ring_epilogue<BM, NJ, 2 * P_BYTES + BSTAGES * B_BYTES, false, NTAPS == 4>(g, wgc, acc, smem, m0, n0);
@@ -1043,7 +1010,6 @@ __device__ __forceinline__ void wgrad_ring_body(const pdmk_gemm_args& g, int lg_
         if (kt0 + s < kt1) issue(kt0 + s, s);
 
     int slot = 0;
-    prio_static(wave);
     for (int kt = kt0; kt < kt1; ++kt) {
         if (STAGES == 2) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         else if (kt + STAGES - 1 <= kt1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"((STAGES - 2) * (PA + PB)) : "memory");
@@ -1059,12 +1025,10 @@ __device__ __forceinline__ void wgrad_ring_body(const pdmk_gemm_args& g, int lg_
             for (int i = 0; i < IM; ++i) af[i] = tr_frag(sa, RA, kk, wm * (16 * IM) + i * 16);
 #pragma unroll
             for (int j = 0; j < NJ; ++j) bf[j] = tr_frag(sb, RB, kk, wn * (16 * NJ) + j * 16);
-            PDMK_PRIO_UP();
 #pragma unroll
             for (int i = 0; i < IM; ++i)
 #pragma unroll
                 for (int j = 0; j < NJ; ++j) acc[i][j] = MM::mma(bf[j], af[i], acc[i][j]);
-            PDMK_PRIO_DOWN();
             if (do_colsum) {
 #pragma unroll
                 for (int i = 0; i < IM; ++i) acs[i] = MM::mma(ones, af[i], acs[i]);
@@ -1072,7 +1036,6 @@ __device__ __forceinline__ void wgrad_ring_body(const pdmk_gemm_args& g, int lg_
         }
         slot = slot + 1 == STAGES ? 0 : slot + 1;
     }
-    if (PDMK_PRIO == 1) __builtin_amdgcn_s_setprio(0);
     if (do_colsum && (lane >> 4) == 0) {
 #pragma unroll
         for (int i = 0; i < IM; ++i) {
@@ -1097,178 +1060,6 @@ __global__ __launch_bounds__(NT, OCC) void wgrad_ring_group_kernel(pdmk_gemm_gro
     if (!lc_group(gg, pi, wgc)) return;
     wgrad_ring_body<CONV, BM, NJ, STAGES, OCC>(gg.p[pi], gg.aux0[pi], gg.aux1[pi], gg.a_bytes[pi], gg.b_bytes[pi], wgc, smem);
 }
-
-struct Config {
-    int bm, nj, stages, occ;      // occ 4 = "shallow": short ring, two workgroups per CU (many-round grids, few K-steps)
-};
-// candidate table: the autotuner in gemm.hip times these per GEMM shape; ids are stable (plan cache values)
-static const Config kConfigs[] = {
-    {256, 4, 3, 2}, {256, 5, 3, 2}, {128, 4, 4, 2}, {128, 5, 4, 2}, {64, 4, 6, 2}, {64, 5, 5, 2},
-    {128, 4, 2, 4}, {64, 4, 3, 4},  {64, 5, 2, 4},  {128, 6, 3, 2}, {64, 6, 4, 2},  {128, 5, 2, 4},
-    // small tiles for the small / short GEMMs of the 8x8 .. 32x32 levels: a workgroup's K-loop is bound by the ~70 GB/s a
-    // CU takes in from L2, so a GEMM with fewer tiles than CUs runs at (tiles / 256) of the chip's intake - more, smaller
-    // tiles (and split-K) spread it over the CUs
-    {64, 2, 4, 4},  {128, 2, 3, 4}, {64, 3, 4, 4},
-};
-constexpr int kNumConfigs = sizeof(kConfigs) / sizeof(kConfigs[0]);
-// candidate numbering (stable: plan files and tests name candidates by id): ring ids 0 .. kNumBase-1 = the first kNumBase
-// ring shapes, kNumBase .. kNumBase+3 = the four halo-conv shapes, then the ring shapes added later
-constexpr int kNumBase = 12;
-
-// Halo-conv shapes (candidate ids kNumConfigs + h): tile rows, channel tiles, patch capacity; eligibility of a conv.
-// Tile width for halo shape h on this conv: the image width when whole rows fit the patch buffer, else the widest
-// power-of-two column block (images wider than a tile - the VAE encoder's 128^2..512^2 levels - are cut into
-// rows x tw blocks, e.g. 16 x 16 output pixels + halo = 324 patch rows); 0 = not eligible.
-static int halo_tile_w(const pdmk_gemm_args& g, int h, int splitk) {
-    const bool phase = g.conv_mode >= 5 && g.conv_mode <= 13;        // 2x2 phase(s) of an upsampling conv: the 128-row shapes only
-    if (g.a_mode != PDMK_A_CONV || !(g.conv_mode == 0 || phase) || g.conv_ho != g.conv_hi || g.conv_wo != g.conv_wi) return 0;
-    if (phase && (h < 2 || !PDMK_HALO_PAIRS || g.R || (splitk > 1))) return 0;
-    // (a phase's weights may be a column slice of the [N][16 ci] matrix of all four: ldb is then the full row)
-    if ((g.conv_ci % 8) || g.conv_wi < 4) return 0;
-    if (phase ? ((g.ldb % 8) || g.ldb < (g.conv_mode == 13 ? 16 : 4) * g.conv_ci) : g.ldb != 9 * g.conv_ci) return 0;
-    if ((splitk > 1 ? splitk : 1) > (g.conv_ci + 63) / 64) return 0;
-    const int bm = h < 2 ? 256 : 128, pmax = h < 2 ? 400 : 264;
-    const int H = g.conv_hi, W = g.conv_wi, HW = H * W;
-    if (HW < bm) return (bm % HW) == 0 && (bm / HW) * (H + 2) * (W + 2) <= pmax ? W : 0;
-    if (HW % bm) return 0;
-    static const int pref = getenv("PDMK_HALO_TW") ? atoi(getenv("PDMK_HALO_TW")) : 0;   // experiment knob: preferred block width
-    if (pref > 0 && pref < W && (W % pref) == 0 && (bm % pref) == 0 && (H % (bm / pref)) == 0 &&
-        (bm / pref + 2) * (pref + 2) <= pmax)
-        return pref;
-    if ((bm % W) == 0 && (bm / W + 2) * (W + 2) <= pmax) return W;
-    for (int tw = 128; tw >= 8; tw >>= 1) {
-        if (tw >= W || (W % tw) || (bm % tw)) continue;
-        const int rows = bm / tw;
-        if ((H % rows) == 0 && (rows + 2) * (tw + 2) <= pmax) return tw;
-    }
-    return 0;
-}
-static bool halo_ok(const pdmk_gemm_args& g, int h, int splitk) { return halo_tile_w(g, h, splitk) > 0; }
-
-// Untuned default (graph capture of a shape never seen eagerly, PDMK_GEMM_TUNE=0): the decision tree the tuned plans of
-// the SD-2.1 step condense to (tools/ring_sweep.py; plan files of bench.py).  Stride-1 convs: the halo kernel, 256-row
-// tiles once there are enough of them; Linear and the strided convs: the two-workgroups-per-CU shallow rings, tile rows
-// by M.  Returns the ring candidate index (halo shapes follow the ring shapes).
-static int pick_config(const pdmk_gemm_args& g, int splitk) {
-    enum { R256x128, R256x160, R128x128, R128x160, R64x128, R64x160, S128x128, S64x128, S64x160, R128x192, R64x192, S128x160 };
-    const bool n160 = (g.N % 160) == 0 || (g.N > 256 && (g.N % 128) != 0);
-    if (g.a_mode == PDMK_A_CONV && g.conv_mode >= 5) return kNumBase + (halo_ok(g, n160 ? 2 : 3, splitk) ? (n160 ? 2 : 3) : (n160 ? 3 : 2));
-    if (g.a_mode == PDMK_A_CONV && g.conv_mode == 0) {
-        const long t256 = (long)((g.M + 255) / 256) * ((g.N + 159) / 160);
-        const int h = (g.M >= 8192 && t256 >= 128) ? (n160 ? 0 : 1) : (n160 ? 2 : 3);
-        if (halo_ok(g, h, splitk)) return kNumBase + h;
-        if (halo_ok(g, h | 2, splitk)) return kNumBase + (h | 2);
-    }
-    if (g.M >= 8192) return n160 ? S128x160 : S128x128;
-    if (g.M >= 4096) return S64x160;
-    if (g.M >= 2048 && n160 && g.N >= 1280) return S64x160;
-    return S64x128;
-}
-
-}  // namespace pdmk_ring
-
-constexpr int kNumHalo = 4;      // halo-conv candidates follow the ring shapes in the candidate numbering
-// row-block Linear kernels (gemm_rowblock.hip): candidate ids after every ring / halo shape
-int pdmk_gemm_rowblock_num_configs();
-int pdmk_gemm_rowblock_name(int id, char* buf, int n);
-int pdmk_gemm_rowblock_launch(const pdmk_gemm_args& g, hipStream_t st, long a_bytes, long b_bytes, int id, bool dry = false);
-static int conv_halo_launch(const pdmk_gemm_args& g, hipStream_t st, long a_bytes, long b_bytes, int id) {
-    using namespace pdmk_ring;
-    const int tw = halo_tile_w(g, id, g.splitk);
-    if (tw <= 0) return 1;
-    const int bm = id < 2 ? 256 : 128, nj = (id & 1) ? 4 : 5;
-    const int sk = g.splitk > 1 ? g.splitk : 1;
-    const int bn = 32 * nj;
-    dim3 grid(((g.M + bm - 1) / bm) * ((g.N + bn - 1) / bn), sk);
-    if (g.conv_mode >= 5) {
-        if (id == 2) hipLaunchKernelGGL((conv_halo_kernel<128, 5, 4, 264, 4>), grid, dim3(NT), 0, st, g, (unsigned)a_bytes, (unsigned)b_bytes, tw);
-        else hipLaunchKernelGGL((conv_halo_kernel<128, 4, 5, 264, 4>), grid, dim3(NT), 0, st, g, (unsigned)a_bytes, (unsigned)b_bytes, tw);
-        return hipGetLastError() == hipSuccess ? 0 : -1000;
-    }
-    switch (id) {
-        case 0: hipLaunchKernelGGL((conv_halo_kernel<256, 5, 3, 400>), grid, dim3(NT), 0, st, g, (unsigned)a_bytes, (unsigned)b_bytes, tw); break;
-        case 1: hipLaunchKernelGGL((conv_halo_kernel<256, 4, 3, 400>), grid, dim3(NT), 0, st, g, (unsigned)a_bytes, (unsigned)b_bytes, tw); break;
-        case 2: hipLaunchKernelGGL((conv_halo_kernel<128, 5, 4, 264>), grid, dim3(NT), 0, st, g, (unsigned)a_bytes, (unsigned)b_bytes, tw); break;
-        case 3: hipLaunchKernelGGL((conv_halo_kernel<128, 4, 5, 264>), grid, dim3(NT), 0, st, g, (unsigned)a_bytes, (unsigned)b_bytes, tw); break;
-        default: return 1;
-    }
-    return hipGetLastError() == hipSuccess ? 0 : -1000;
-}
-
-// pdmk.h: can the 2x2 phase form serve the nearest-x2 upsample + 3x3 conv of a [B, H, W, Ci] image to Co channels?
-extern "C" int pdmk_conv_up2_supported(int B, int H, int W, int Ci, int Co, int dtype) {
-    if (dtype != PDMK_BF16 || B <= 0 || H <= 0 || W <= 0 || Ci <= 0 || Co <= 0 || (Ci % 32) || (Co % 32)) return 0;
-    pdmk_gemm_args g = {};
-    g.a_mode = PDMK_A_CONV;
-    g.b_mode = PDMK_B_ROWK;
-    g.dtype = PDMK_BF16;
-    g.conv_b = B;
-    g.conv_hi = g.conv_ho = H;
-    g.conv_wi = g.conv_wo = W;
-    g.M = B * H * W;
-    bool ok = true;
-    for (int dir = 0; dir < 2; ++dir) {          // forward (Ci -> Co) and input gradient (Co -> Ci)
-        g.conv_mode = dir ? 13 : 5;
-        g.conv_ci = dir ? Co : Ci;
-        g.N = dir ? Ci : Co;
-        g.K = (dir ? 16 : 4) * g.conv_ci;
-        g.ldb = g.K;
-        ok = ok && (pdmk_ring::halo_tile_w(g, 2, 1) > 0 || pdmk_ring::halo_tile_w(g, 3, 1) > 0);
-    }
-    return ok ? 1 : 0;
-}
-
-int pdmk_gemm_ring_num_configs() { return pdmk_ring::kNumConfigs + kNumHalo + pdmk_gemm_rowblock_num_configs(); }
-int pdmk_gemm_ring_name(int id, int conv, char* buf, int n) {      // the demangled symbol rocprofv3 reports
-    using namespace pdmk_ring;
-    if (id >= kNumConfigs + kNumHalo) return pdmk_gemm_rowblock_name(id - (kNumConfigs + kNumHalo), buf, n);
-    if (id < 0) return -1;
-    if (id >= kNumBase && id < kNumBase + kNumHalo) {
-        const int h = id - kNumBase;
-        snprintf(buf, n, "pdmk_ring::conv_halo_kernel<%d, %d, %d, %d, 9>", h < 2 ? 256 : 128, (h & 1) ? 4 : 5,
-                 h < 2 ? 3 : ((h & 1) ? 5 : 4), h < 2 ? 400 : 264);          // (2x2 phase launches run the <..., 4> instantiation)
-        return 0;
-    }
-    const Config c = kConfigs[id < kNumBase ? id : id - kNumHalo];
-    snprintf(buf, n, "pdmk_ring::igemm_ring_kernel<%s, %d, %d, %d, %d>", conv ? "true" : "false", c.bm, c.nj, c.stages, c.occ);
-    return 0;
-}
-int pdmk_gemm_ring_pick(const pdmk_gemm_args& g) { return pdmk_ring::pick_config(g, g.splitk); }
-
-// called by pdmk_gemm (gemm.hip) after argument validation; returns 1 if the shape/config is not handled here
-int pdmk_gemm_ring_launch(const pdmk_gemm_args& g, hipStream_t st, long a_bytes, long b_bytes, int id) {
-    using namespace pdmk_ring;
-    if (g.dtype != PDMK_BF16 || g.b_mode != PDMK_B_ROWK || g.a_mode == PDMK_A_COLK) return 1;
-    if ((g.K % 8) || (g.a_mode == PDMK_A_CONV && (g.conv_ci % 8))) return 1;
-    if (g.ln_gamma && id < kNumConfigs + kNumHalo) return 1;         // LayerNorm prologue: the row-block kernel only
-    if (id >= kNumBase && id < kNumBase + kNumHalo) return conv_halo_launch(g, st, a_bytes, b_bytes, id - kNumBase);
-    if (g.a_mode == PDMK_A_CONV && g.conv_mode >= 5) return 1;       // 2x2 phase convs: halo kernels only
-    if (id >= kNumConfigs + kNumHalo) return pdmk_gemm_rowblock_launch(g, st, a_bytes, b_bytes, id - (kNumConfigs + kNumHalo));
-    if (id < 0) return 1;
-    const int sk = g.splitk > 1 ? g.splitk : 1;
-    const Config c = kConfigs[id < kNumBase ? id : id - kNumHalo];
-    const int bn = 32 * c.nj;
-    dim3 grid(((g.M + c.bm - 1) / c.bm) * ((g.N + bn - 1) / bn), sk);
-    const bool conv = g.a_mode == PDMK_A_CONV;
-#define PDMK_RING_GO(BMv, NJv, STv, OCv)                                                                              \
-    case (BMv * 1000 + NJv * 100 + STv * 10 + OCv):                                                                   \
-        if (conv) hipLaunchKernelGGL((igemm_ring_kernel<true, BMv, NJv, STv, OCv>), grid, dim3(NT), 0, st, g,         \
-                                     (unsigned)a_bytes, (unsigned)b_bytes);                                           \
-        else hipLaunchKernelGGL((igemm_ring_kernel<false, BMv, NJv, STv, OCv>), grid, dim3(NT), 0, st, g,             \
-                                (unsigned)a_bytes, (unsigned)b_bytes);                                                \
-        break;
-    switch (c.bm * 1000 + c.nj * 100 + c.stages * 10 + c.occ) {
-        PDMK_RING_GO(256, 4, 3, 2) PDMK_RING_GO(256, 5, 3, 2) PDMK_RING_GO(128, 4, 4, 2) PDMK_RING_GO(128, 5, 4, 2)
-        PDMK_RING_GO(64, 4, 6, 2) PDMK_RING_GO(64, 5, 5, 2) PDMK_RING_GO(128, 4, 2, 4) PDMK_RING_GO(64, 4, 3, 4)
-        PDMK_RING_GO(64, 5, 2, 4) PDMK_RING_GO(128, 6, 3, 2) PDMK_RING_GO(64, 6, 4, 2) PDMK_RING_GO(128, 5, 2, 4)
-        PDMK_RING_GO(64, 2, 4, 4) PDMK_RING_GO(128, 2, 3, 4) PDMK_RING_GO(64, 3, 4, 4)
-        default: return 1;
-    }
-#undef PDMK_RING_GO
-    return hipGetLastError() == hipSuccess ? 0 : -1000;
-}
-
-namespace pdmk_ring {
 
 // ------------------------------------------------------------------------------------------------------------------
 // Halo weight gradient of a stride-1 3x3 conv:  dW[co][tap][ci] (+)= sum_px dY[px][co] * X[src(px, tap)][ci].
@@ -1506,24 +1297,209 @@ static bool wgrad_halo_ok(const pdmk_gemm_args& g) {
     return (128 % HW) == 0 && (128 / HW) * (H + 2) * W2 <= 288;
 }
 
-}  // namespace pdmk_ring
+// ------------------------------------------------------------------------------------------------------------------
+// Host side.  One table per kernel family; a row is the tile parameters of one instantiation plus its launchers, and table
+// order is the id order (gemm_candidates.h: pdmk_cand::decode).  A new candidate is one row here (behind the existing rows of
+// its table) and one line in tests/golden/gemm_candidates.json.
+// ------------------------------------------------------------------------------------------------------------------
+using PlainFn = void (*)(dim3 grid, hipStream_t st, const pdmk_gemm_args& g, unsigned ab, unsigned bb, int aux0, int aux1);
+using GroupFn = void (*)(dim3 grid, hipStream_t st, const pdmk_gemm_group_dev& gg);
+template <auto K> static void go_plain(dim3 grid, hipStream_t st, const pdmk_gemm_args& g, unsigned ab, unsigned bb, int, int) {
+    hipLaunchKernelGGL(K, grid, dim3(NT), 0, st, g, ab, bb);
+}
+template <auto K> static void go_halo(dim3 grid, hipStream_t st, const pdmk_gemm_args& g, unsigned ab, unsigned bb, int tw, int) {
+    hipLaunchKernelGGL(K, grid, dim3(NT), 0, st, g, ab, bb, tw);
+}
+template <auto K> static void go_wgrad(dim3 grid, hipStream_t st, const pdmk_gemm_args& g, unsigned ab, unsigned bb, int lg_wo, int lg_howo) {
+    hipLaunchKernelGGL(K, grid, dim3(NT), 0, st, g, lg_wo, lg_howo, ab, bb);
+}
+template <auto K> static void go_group(dim3 grid, hipStream_t st, const pdmk_gemm_group_dev& gg) {
+    hipLaunchKernelGGL(K, grid, dim3(NT), 0, st, gg);
+}
 
-// ---- grouped launches (pdmk_gemm_group): candidate `id` (numbering of pdmk_gemm_ring_launch) for n problems in one grid.
-// Returns 1 when a problem is not served by that candidate (the caller then launches the problems one by one).
-namespace {
+struct RingCand {                 // forward / dgrad ring and weight-gradient ring shapes; launchers [conv]
+    int bm, nj, stages, occ;      // occ 4 = "shallow": short ring, two workgroups per CU (many-round grids, few K-steps)
+    PlainFn plain[2];
+    GroupFn group[2];
+};
+template <int BM, int NJ, int ST, int OCC> constexpr RingCand ring_row() {
+    return {BM, NJ, ST, OCC,
+            {go_plain<igemm_ring_kernel<false, BM, NJ, ST, OCC>>, go_plain<igemm_ring_kernel<true, BM, NJ, ST, OCC>>},
+            {go_group<igemm_ring_group_kernel<false, BM, NJ, ST, OCC>>, go_group<igemm_ring_group_kernel<true, BM, NJ, ST, OCC>>}};
+}
+template <int BM, int NJ, int ST, int OCC> constexpr RingCand wgrad_row() {
+    return {BM, NJ, ST, OCC,
+            {go_wgrad<wgrad_ring_kernel<false, BM, NJ, ST, OCC>>, go_wgrad<wgrad_ring_kernel<true, BM, NJ, ST, OCC>>},
+            {go_group<wgrad_ring_group_kernel<false, BM, NJ, ST, OCC>>, go_group<wgrad_ring_group_kernel<true, BM, NJ, ST, OCC>>}};
+}
+struct HaloCand {                 // halo-conv shapes: tile rows, channel tiles, weight ring slots, patch capacity (rows)
+    int bm, nj, bstages, pmax;
+    PlainFn plain[2];             // [0] the 3x3 conv (NTAPS 9), [1] the 2x2 phases of an upsampling conv (NTAPS 4) or none
+    GroupFn group[2];
+};
+template <int BM, int NJ, int BS, int PMAX, bool PHASE> constexpr HaloCand halo_row() {
+    HaloCand c = {BM, NJ, BS, PMAX, {go_halo<conv_halo_kernel<BM, NJ, BS, PMAX, 9>>, nullptr},
+                  {go_group<conv_halo_group_kernel<BM, NJ, BS, PMAX, 9>>, nullptr}};
+    if constexpr (PHASE) {
+        c.plain[1] = go_halo<conv_halo_kernel<BM, NJ, BS, PMAX, 4>>;
+        c.group[1] = go_group<conv_halo_group_kernel<BM, NJ, BS, PMAX, 4>>;
+    }
+    return c;
+}
+struct WgradHaloCand {            // halo conv weight gradients: output rows (co) per workgroup = 32 IMW
+    int bm, imw, stages;
+    PlainFn plain;
+    GroupFn group;
+};
+template <int IMW, int ST> constexpr WgradHaloCand wgrad_halo_row() {
+    return {32 * IMW, IMW, ST, go_plain<conv_wgrad_halo_kernel<IMW, ST>>, go_group<conv_wgrad_halo_group_kernel<IMW, ST>>};
+}
+
+// the autotuner in gemm.hip times these per GEMM shape
+static const RingCand kRing[] = {
+    ring_row<256, 4, 3, 2>(), ring_row<256, 5, 3, 2>(), ring_row<128, 4, 4, 2>(), ring_row<128, 5, 4, 2>(),
+    ring_row<64, 4, 6, 2>(),  ring_row<64, 5, 5, 2>(),  ring_row<128, 4, 2, 4>(), ring_row<64, 4, 3, 4>(),
+    ring_row<64, 5, 2, 4>(),  ring_row<128, 6, 3, 2>(), ring_row<64, 6, 4, 2>(),  ring_row<128, 5, 2, 4>(),
+    // (the halo ids lie here.)  Small tiles for the small / short GEMMs of the 8x8 .. 32x32 levels: a workgroup's K-loop is
+    // bound by the ~70 GB/s a CU takes in from L2, so a GEMM with fewer tiles than CUs runs at (tiles / 256) of the chip's
+    // intake - more, smaller tiles (and split-K) spread it over the CUs
+    ring_row<64, 2, 4, 4>(),  ring_row<128, 2, 3, 4>(), ring_row<64, 3, 4, 4>(),
+};
+static const HaloCand kHalo[] = {
+    halo_row<256, 5, 3, 400, false>(), halo_row<256, 4, 3, 400, false>(), halo_row<128, 5, 4, 264, true>(), halo_row<128, 4, 5, 264, true>(),
+};
+// weight-gradient ring shapes: 128x128 deep / shallow rings, and the smaller tiles whose split-K epilogue moves a quarter to a
+// half of the atomic bytes per workgroup (what bounds the small weights: ~5 GB/s of atomics per CU)
+static const RingCand kWgrad[] = {
+    wgrad_row<128, 4, 4, 2>(), wgrad_row<128, 4, 2, 4>(), wgrad_row<64, 4, 3, 4>(), wgrad_row<128, 2, 3, 4>(), wgrad_row<64, 2, 4, 4>(),
+};
+static const WgradHaloCand kWgradHalo[] = {wgrad_halo_row<2, 3>(), wgrad_halo_row<4, 2>()};
+
+template <typename T, int N> constexpr int rows_of(const T (&)[N]) { return N; }
+constexpr int kNumRing = rows_of(kRing), kNumWgrad = rows_of(kWgrad);
+static_assert(kNumRing >= pdmk_cand::kRingBase && rows_of(kHalo) == pdmk_cand::kHaloCount, "gemm_candidates.h numbering");
+static_assert(kNumWgrad >= pdmk_cand::kWgradRingBase && rows_of(kWgradHalo) == pdmk_cand::kWgradHaloCount, "gemm_candidates.h numbering");
+static pdmk_cand::Ref fwd_decode(int id) {
+    return pdmk_cand::decode(id, pdmk_cand::kRingBase, pdmk_cand::kHaloCount, kNumRing, pdmk_gemm_rowblock_num_configs());
+}
+static pdmk_cand::Ref wgrad_decode(int id) {
+    return pdmk_cand::decode(id, pdmk_cand::kWgradRingBase, pdmk_cand::kWgradHaloCount, kNumWgrad, 0);
+}
+
+// Tile width for halo shape c on this conv: the image width when whole rows fit the patch buffer, else the widest
+// power-of-two column block (images wider than a tile - the VAE encoder's 128^2..512^2 levels - are cut into
+// rows x tw blocks, e.g. 16 x 16 output pixels + halo = 324 patch rows); 0 = not eligible.
+static int halo_tile_w(const pdmk_gemm_args& g, const HaloCand& c, int splitk) {
+    const bool phase = g.conv_mode >= 5 && g.conv_mode <= 13;        // 2x2 phase(s) of an upsampling conv: the shapes with a 4-tap form only
+    if (g.a_mode != PDMK_A_CONV || !(g.conv_mode == 0 || phase) || g.conv_ho != g.conv_hi || g.conv_wo != g.conv_wi) return 0;
+    if (phase && (!c.plain[1] || !PDMK_HALO_PAIRS || g.R || (splitk > 1))) return 0;
+    // (a phase's weights may be a column slice of the [N][16 ci] matrix of all four: ldb is then the full row)
+    if ((g.conv_ci % 8) || g.conv_wi < 4) return 0;
+    if (phase ? ((g.ldb % 8) || g.ldb < (g.conv_mode == 13 ? 16 : 4) * g.conv_ci) : g.ldb != 9 * g.conv_ci) return 0;
+    if ((splitk > 1 ? splitk : 1) > (g.conv_ci + 63) / 64) return 0;
+    const int bm = c.bm, pmax = c.pmax;
+    const int H = g.conv_hi, W = g.conv_wi, HW = H * W;
+    if (HW < bm) return (bm % HW) == 0 && (bm / HW) * (H + 2) * (W + 2) <= pmax ? W : 0;
+    if (HW % bm) return 0;
+    static const int pref = getenv("PDMK_HALO_TW") ? atoi(getenv("PDMK_HALO_TW")) : 0;   // experiment knob: preferred block width
+    if (pref > 0 && pref < W && (W % pref) == 0 && (bm % pref) == 0 && (H % (bm / pref)) == 0 &&
+        (bm / pref + 2) * (pref + 2) <= pmax)
+        return pref;
+    if ((bm % W) == 0 && (bm / W + 2) * (W + 2) <= pmax) return W;
+    for (int tw = 128; tw >= 8; tw >>= 1) {
+        if (tw >= W || (W % tw) || (bm % tw)) continue;
+        const int rows = bm / tw;
+        if ((H % rows) == 0 && (rows + 2) * (tw + 2) <= pmax) return tw;
+    }
+    return 0;
+}
+static bool halo_ok(const pdmk_gemm_args& g, int h, int splitk) { return halo_tile_w(g, kHalo[h], splitk) > 0; }
+
+// Untuned default (graph capture of a shape never seen eagerly, PDMK_GEMM_TUNE=0): the decision tree the tuned plans of
+// the SD-2.1 step condense to (tools/ring_sweep.py; plan files of bench.py).  Stride-1 convs: the halo kernel, 256-row
+// tiles once there are enough of them; Linear and the strided convs: the two-workgroups-per-CU shallow rings, tile rows
+// by M.  Returns the ring id; h is a row of kHalo (256 x 160, 256 x 128, 128 x 160, 128 x 128).
+static int pick_config(const pdmk_gemm_args& g, int splitk) {
+    enum { R256x128, R256x160, R128x128, R128x160, R64x128, R64x160, S128x128, S64x128, S64x160, R128x192, R64x192, S128x160 };
+    constexpr int kHalo0 = pdmk_cand::kRingBase;
+    const bool n160 = (g.N % 160) == 0 || (g.N > 256 && (g.N % 128) != 0);
+    if (g.a_mode == PDMK_A_CONV && g.conv_mode >= 5) return kHalo0 + (halo_ok(g, n160 ? 2 : 3, splitk) ? (n160 ? 2 : 3) : (n160 ? 3 : 2));
+    if (g.a_mode == PDMK_A_CONV && g.conv_mode == 0) {
+        const long t256 = (long)((g.M + 255) / 256) * ((g.N + 159) / 160);
+        const int h = (g.M >= 8192 && t256 >= 128) ? (n160 ? 0 : 1) : (n160 ? 2 : 3);
+        if (halo_ok(g, h, splitk)) return kHalo0 + h;
+        if (halo_ok(g, h | 2, splitk)) return kHalo0 + (h | 2);
+    }
+    if (g.M >= 8192) return n160 ? S128x160 : S128x128;
+    if (g.M >= 4096) return S64x160;
+    if (g.M >= 2048 && n160 && g.N >= 1280) return S64x160;
+    return S64x128;
+}
+
+// ---- eligibility and placement: does candidate row c serve problem g, and with which grid?  One function per family, shared by
+// the plain launch (once) and the grouped launch (per member).
+struct Place {
+    bool ok;                      // false = not served
+    int tiles, splits, aux0, aux1;          // aux: tw (halo conv) / lg_wo, lg_howo (conv weight-gradient rings)
+};
+constexpr Place kNotServed = {false, 0, 0, 0, 0};
+static int tiles_of(const pdmk_gemm_args& g, int bm, int bn) { return ((g.M + bm - 1) / bm) * ((g.N + bn - 1) / bn); }
+static int splits_of(const pdmk_gemm_args& g) { return g.splitk > 1 ? g.splitk : 1; }
+
+static bool fwd_ok(const pdmk_gemm_args& g) {
+    if (g.dtype != PDMK_BF16 || g.b_mode != PDMK_B_ROWK || g.a_mode == PDMK_A_COLK) return false;
+    return !((g.K % 8) || (g.a_mode == PDMK_A_CONV && (g.conv_ci % 8)));
+}
+static Place ring_place(const pdmk_gemm_args& g, const RingCand& c) {
+    if (!fwd_ok(g) || (g.a_mode == PDMK_A_CONV && g.conv_mode >= 5)) return kNotServed;       // 2x2 phase convs: halo kernels only
+    return {true, tiles_of(g, c.bm, 32 * c.nj), splits_of(g), 0, 0};
+}
+static Place halo_place(const pdmk_gemm_args& g, const HaloCand& c) {
+    const int tw = fwd_ok(g) ? halo_tile_w(g, c, g.splitk) : 0;
+    if (tw <= 0) return kNotServed;
+    return {true, tiles_of(g, c.bm, 32 * c.nj), splits_of(g), tw, 0};
+}
+
+static bool wgrad_ok(const pdmk_gemm_args& g) {
+    if (g.dtype != PDMK_BF16 || g.a_mode != PDMK_A_COLK || g.b_mode == PDMK_B_ROWK || !g.out_f32) return false;
+    const bool conv = g.b_mode == PDMK_B_COLK_CONV;
+    if ((g.M % 8) || (g.N % 8) || (g.lda % 8) || (!conv && (g.ldb % 8))) return false;
+    return !(conv && ((g.conv_ci % 8) || (g.conv_ld % 8) || g.conv_mode == 3 || g.conv_mode == 4 || g.conv_mode > 8));
+}
+static Place wgrad_place(const pdmk_gemm_args& g, const RingCand& c) {
+    if (!wgrad_ok(g)) return kNotServed;
+    int lg_wo = -1, lg_howo = -1;             // convs on power-of-two images: pixel -> (y, x) by shifts
+    if (g.b_mode == PDMK_B_COLK_CONV) {
+        auto lg = [](int v) { int l = 0; if (v <= 0 || (v & (v - 1))) return -1; while ((1 << l) < v) ++l; return l; };
+        lg_wo = lg(g.conv_wo);
+        lg_howo = lg(g.conv_ho * g.conv_wo);
+        if (lg_wo < 0 || lg_howo < 0) lg_wo = lg_howo = -1;
+    }
+    return {true, tiles_of(g, c.bm, 32 * c.nj), splits_of(g), lg_wo, lg_howo};
+}
+static Place wgrad_halo_place(const pdmk_gemm_args& g, const WgradHaloCand& c) {
+    if (!wgrad_ok(g) || !wgrad_halo_ok(g)) return kNotServed;
+    const int nblk = (g.K + 127) / 128, sk = splits_of(g);
+    if (sk > nblk) return kNotServed;
+    return {true, ((g.M + c.bm - 1) / c.bm) * ((g.conv_ci + 63) / 64), sk, 0, 0};
+}
+
+static int launched() { return hipGetLastError() == hipSuccess ? 0 : -1000; }
+
+// ---- grouped launches (pdmk_gemm_group): n problems of one kernel shape in one grid
 struct GroupGrid {
     pdmk_gemm_group_dev gg;
     unsigned total = 0;
-    void add(int i, const pdmk_gemm_args& g, int tiles, int splits, long ab, long bb, int aux0 = 0, int aux1 = 0) {
+    void add(int i, const pdmk_gemm_args& g, const Place& p, long ab, long bb) {
         gg.start[i] = (int)total;
-        gg.gx[i] = tiles;
-        gg.gy[i] = splits;
+        gg.gx[i] = p.tiles;
+        gg.gy[i] = p.splits;
         gg.a_bytes[i] = (unsigned)ab;
         gg.b_bytes[i] = (unsigned)bb;
-        gg.aux0[i] = aux0;
-        gg.aux1[i] = aux1;
+        gg.aux0[i] = p.aux0;
+        gg.aux1[i] = p.aux1;
         gg.p[i] = g;
-        total += ((unsigned)tiles * (unsigned)splits + 7u) & ~7u;
+        total += ((unsigned)p.tiles * (unsigned)p.splits + 7u) & ~7u;
     }
     void finish(int n) {
         gg.n = n;
@@ -1536,176 +1512,140 @@ struct GroupGrid {
         }
     }
 };
-}  // namespace
-
-int pdmk_gemm_ring_group_launch(const pdmk_gemm_args* gs, int n, hipStream_t st, const long* a_bytes, const long* b_bytes, int id) {
-    using namespace pdmk_ring;
-    if (n < 2 || n > PDMK_GEMM_GROUP_MAX || id < 0) return 1;
-    const bool halo = id >= kNumBase && id < kNumBase + kNumHalo;
-    if (id >= kNumConfigs + kNumHalo) return 1;                       // row-block kernels: not grouped
-    const bool conv = gs[0].a_mode == PDMK_A_CONV;
+// place(g) of every member, then one launch; 1 when a member is not served (the caller launches them one by one)
+template <typename F>
+static int group_go(const pdmk_gemm_args* gs, int n, hipStream_t st, const long* a_bytes, const long* b_bytes, GroupFn fn, F place) {
     GroupGrid G;
     for (int i = 0; i < n; ++i) {
-        const pdmk_gemm_args& g = gs[i];
-        if (g.dtype != PDMK_BF16 || g.b_mode != PDMK_B_ROWK || g.a_mode == PDMK_A_COLK) return 1;
-        if ((g.K % 8) || (g.a_mode == PDMK_A_CONV && (g.conv_ci % 8))) return 1;
-        if ((g.a_mode == PDMK_A_CONV) != conv) return 1;              // one template instantiation per launch
-        if (!halo && g.a_mode == PDMK_A_CONV && g.conv_mode >= 5) return 1;
-        const int sk = g.splitk > 1 ? g.splitk : 1;
-        if (halo) {
-            const int h = id - kNumBase;
-            const int tw = halo_tile_w(g, h, g.splitk);
-            if (tw <= 0) return 1;
-            const int bm = h < 2 ? 256 : 128, bn = 32 * ((h & 1) ? 4 : 5);
-            G.add(i, g, ((g.M + bm - 1) / bm) * ((g.N + bn - 1) / bn), sk, a_bytes[i], b_bytes[i], tw);
-        } else {
-            const Config c = kConfigs[id < kNumBase ? id : id - kNumHalo];
-            const int bn = 32 * c.nj;
-            G.add(i, g, ((g.M + c.bm - 1) / c.bm) * ((g.N + bn - 1) / bn), sk, a_bytes[i], b_bytes[i]);
-        }
+        const Place p = place(gs[i]);
+        if (!p.ok) return 1;
+        G.add(i, gs[i], p, a_bytes[i], b_bytes[i]);
     }
     G.finish(n);
-    const dim3 grid(G.total);
-    if (halo) {
-        bool phase = gs[0].conv_mode >= 5;
-        for (int i = 1; i < n; ++i)
-            if ((gs[i].conv_mode >= 5) != phase) return 1;
-        if (phase) {
-            if (id - kNumBase == 2) hipLaunchKernelGGL((conv_halo_group_kernel<128, 5, 4, 264, 4>), grid, dim3(NT), 0, st, G.gg);
-            else hipLaunchKernelGGL((conv_halo_group_kernel<128, 4, 5, 264, 4>), grid, dim3(NT), 0, st, G.gg);
-            return hipGetLastError() == hipSuccess ? 0 : -1000;
-        }
-        switch (id - kNumBase) {
-            case 0: hipLaunchKernelGGL((conv_halo_group_kernel<256, 5, 3, 400>), grid, dim3(NT), 0, st, G.gg); break;
-            case 1: hipLaunchKernelGGL((conv_halo_group_kernel<256, 4, 3, 400>), grid, dim3(NT), 0, st, G.gg); break;
-            case 2: hipLaunchKernelGGL((conv_halo_group_kernel<128, 5, 4, 264>), grid, dim3(NT), 0, st, G.gg); break;
-            default: hipLaunchKernelGGL((conv_halo_group_kernel<128, 4, 5, 264>), grid, dim3(NT), 0, st, G.gg); break;
-        }
-        return hipGetLastError() == hipSuccess ? 0 : -1000;
-    }
-    const Config c = kConfigs[id < kNumBase ? id : id - kNumHalo];
-#define PDMK_RING_GGO(BMv, NJv, STv, OCv)                                                                             \
-    case (BMv * 1000 + NJv * 100 + STv * 10 + OCv):                                                                   \
-        if (conv) hipLaunchKernelGGL((igemm_ring_group_kernel<true, BMv, NJv, STv, OCv>), grid, dim3(NT), 0, st, G.gg); \
-        else hipLaunchKernelGGL((igemm_ring_group_kernel<false, BMv, NJv, STv, OCv>), grid, dim3(NT), 0, st, G.gg);   \
-        break;
-    switch (c.bm * 1000 + c.nj * 100 + c.stages * 10 + c.occ) {
-        PDMK_RING_GGO(256, 4, 3, 2) PDMK_RING_GGO(256, 5, 3, 2) PDMK_RING_GGO(128, 4, 4, 2) PDMK_RING_GGO(128, 5, 4, 2)
-        PDMK_RING_GGO(64, 4, 6, 2) PDMK_RING_GGO(64, 5, 5, 2) PDMK_RING_GGO(128, 4, 2, 4) PDMK_RING_GGO(64, 4, 3, 4)
-        PDMK_RING_GGO(64, 5, 2, 4) PDMK_RING_GGO(128, 6, 3, 2) PDMK_RING_GGO(64, 6, 4, 2) PDMK_RING_GGO(128, 5, 2, 4)
-        PDMK_RING_GGO(64, 2, 4, 4) PDMK_RING_GGO(128, 2, 3, 4) PDMK_RING_GGO(64, 3, 4, 4)
-        default: return 1;
-    }
-#undef PDMK_RING_GGO
-    return hipGetLastError() == hipSuccess ? 0 : -1000;
+    fn(dim3(G.total), st, G.gg);
+    return launched();
 }
 
-// ---- weight-gradient ring candidates: 128x128 deep / shallow rings, and the smaller tiles whose split-K epilogue moves a
-// quarter to a half of the atomic bytes per workgroup (what bounds the small weights: ~5 GB/s of atomics per CU)
-struct WCfg { int bm, nj, stages, occ; };
-static const WCfg kWCfgs[] = {{128, 4, 4, 2}, {128, 4, 2, 4}, {64, 4, 3, 4}, {128, 2, 3, 4}, {64, 2, 4, 4}};
-constexpr int kNumW = sizeof(kWCfgs) / sizeof(kWCfgs[0]);
-int pdmk_wgrad_ring_num_configs() { return kNumW + 2; }      // + the halo conv weight gradients (64 / 128 output rows)
-int pdmk_wgrad_ring_name(int id, int conv, char* buf, int n) {
-    if (id == kNumW || id == kNumW + 1) {
-        snprintf(buf, n, "pdmk_ring::conv_wgrad_halo_kernel<%d, %d>", id == kNumW ? 2 : 4, id == kNumW ? 3 : 2);
+}  // namespace pdmk_ring
+
+// pdmk.h: can the 2x2 phase form serve the nearest-x2 upsample + 3x3 conv of a [B, H, W, Ci] image to Co channels?
+extern "C" int pdmk_conv_up2_supported(int B, int H, int W, int Ci, int Co, int dtype) {
+    if (dtype != PDMK_BF16 || B <= 0 || H <= 0 || W <= 0 || Ci <= 0 || Co <= 0 || (Ci % 32) || (Co % 32)) return 0;
+    pdmk_gemm_args g = {};
+    g.a_mode = PDMK_A_CONV;
+    g.b_mode = PDMK_B_ROWK;
+    g.dtype = PDMK_BF16;
+    g.conv_b = B;
+    g.conv_hi = g.conv_ho = H;
+    g.conv_wi = g.conv_wo = W;
+    g.M = B * H * W;
+    bool ok = true;
+    for (int dir = 0; dir < 2; ++dir) {          // forward (Ci -> Co) and input gradient (Co -> Ci)
+        g.conv_mode = dir ? 13 : 5;
+        g.conv_ci = dir ? Co : Ci;
+        g.N = dir ? Ci : Co;
+        g.K = (dir ? 16 : 4) * g.conv_ci;
+        g.ldb = g.K;
+        bool any = false;                        // (halo_tile_w refuses the shapes without a 4-tap form)
+        for (const pdmk_ring::HaloCand& c : pdmk_ring::kHalo) any = any || pdmk_ring::halo_tile_w(g, c, 1) > 0;
+        ok = ok && any;
+    }
+    return ok ? 1 : 0;
+}
+
+// ---- forward / dgrad candidates (ring ids, gemm_candidates.h)
+int pdmk_gemm_ring_num_configs() { return pdmk_ring::kNumRing + pdmk_cand::kHaloCount + pdmk_gemm_rowblock_num_configs(); }
+int pdmk_gemm_ring_name(int id, int conv, char* buf, int n) {      // the demangled symbol rocprofv3 reports
+    using namespace pdmk_ring;
+    const pdmk_cand::Ref r = fwd_decode(id);
+    if (r.fam == pdmk_cand::ROWBLOCK) return pdmk_gemm_rowblock_name(r.row, buf, n);
+    if (r.fam == pdmk_cand::HALO) {
+        const HaloCand& c = kHalo[r.row];                          // (2x2 phase launches run the <..., 4> instantiation)
+        snprintf(buf, n, "pdmk_ring::conv_halo_kernel<%d, %d, %d, %d, 9>", c.bm, c.nj, c.bstages, c.pmax);
         return 0;
     }
-    if (id < 0 || id >= kNumW) return -1;
-    const WCfg c = kWCfgs[id];
+    if (r.fam != pdmk_cand::RING) return -1;
+    const RingCand& c = kRing[r.row];
+    snprintf(buf, n, "pdmk_ring::igemm_ring_kernel<%s, %d, %d, %d, %d>", conv ? "true" : "false", c.bm, c.nj, c.stages, c.occ);
+    return 0;
+}
+int pdmk_gemm_ring_pick(const pdmk_gemm_args& g) { return pdmk_ring::pick_config(g, g.splitk); }
+
+// called by pdmk_gemm (gemm.hip) after argument validation; returns 1 if the shape/config is not handled here
+int pdmk_gemm_ring_launch(const pdmk_gemm_args& g, hipStream_t st, long a_bytes, long b_bytes, int id) {
+    using namespace pdmk_ring;
+    const pdmk_cand::Ref r = fwd_decode(id);
+    if (g.ln_gamma && r.fam != pdmk_cand::ROWBLOCK) return 1;        // LayerNorm prologue: the row-block kernel only
+    if (r.fam == pdmk_cand::ROWBLOCK) return fwd_ok(g) ? pdmk_gemm_rowblock_launch(g, st, a_bytes, b_bytes, r.row) : 1;
+    if (r.fam == pdmk_cand::NONE) return 1;
+    const bool halo = r.fam == pdmk_cand::HALO;
+    const Place p = halo ? halo_place(g, kHalo[r.row]) : ring_place(g, kRing[r.row]);
+    if (!p.ok) return 1;
+    const PlainFn fn = halo ? kHalo[r.row].plain[g.conv_mode >= 5] : kRing[r.row].plain[g.a_mode == PDMK_A_CONV];
+    fn(dim3(p.tiles, p.splits), st, g, (unsigned)a_bytes, (unsigned)b_bytes, p.aux0, p.aux1);
+    return launched();
+}
+
+// candidate `id` for n problems in one grid.  All members convs or none (one template instantiation per launch), and for the halo
+// shapes all members 2x2 phases or none.  A LayerNorm prologue is not looked at here: pdmk_gemm_group launches a group with such
+// a member one by one.
+int pdmk_gemm_ring_group_launch(const pdmk_gemm_args* gs, int n, hipStream_t st, const long* a_bytes, const long* b_bytes, int id) {
+    using namespace pdmk_ring;
+    const pdmk_cand::Ref r = fwd_decode(id);
+    if (n < 2 || n > PDMK_GEMM_GROUP_MAX || (r.fam != pdmk_cand::RING && r.fam != pdmk_cand::HALO)) return 1;   // row-block kernels: not grouped
+    const bool conv = gs[0].a_mode == PDMK_A_CONV, phase = gs[0].conv_mode >= 5;
+    if (r.fam == pdmk_cand::HALO) {
+        const HaloCand& c = kHalo[r.row];
+        return group_go(gs, n, st, a_bytes, b_bytes, c.group[phase], [&](const pdmk_gemm_args& g) {
+            return (g.conv_mode >= 5) == phase ? halo_place(g, c) : kNotServed;
+        });
+    }
+    const RingCand& c = kRing[r.row];
+    return group_go(gs, n, st, a_bytes, b_bytes, c.group[conv], [&](const pdmk_gemm_args& g) {
+        return (g.a_mode == PDMK_A_CONV) == conv ? ring_place(g, c) : kNotServed;
+    });
+}
+
+// ---- weight-gradient candidates (ring ids, gemm_candidates.h)
+int pdmk_wgrad_ring_num_configs() { return pdmk_ring::kNumWgrad + pdmk_cand::kWgradHaloCount; }
+int pdmk_wgrad_ring_name(int id, int conv, char* buf, int n) {
+    using namespace pdmk_ring;
+    const pdmk_cand::Ref r = wgrad_decode(id);
+    if (r.fam == pdmk_cand::HALO) {
+        snprintf(buf, n, "pdmk_ring::conv_wgrad_halo_kernel<%d, %d>", kWgradHalo[r.row].imw, kWgradHalo[r.row].stages);
+        return 0;
+    }
+    if (r.fam != pdmk_cand::RING) return -1;
+    const RingCand& c = kWgrad[r.row];
     snprintf(buf, n, "pdmk_ring::wgrad_ring_kernel<%s, %d, %d, %d, %d>", conv ? "true" : "false", c.bm, c.nj, c.stages, c.occ);
     return 0;
 }
 int pdmk_wgrad_ring_launch(const pdmk_gemm_args& g, hipStream_t st, long a_bytes, long b_bytes, int id) {
     using namespace pdmk_ring;
-    if (g.dtype != PDMK_BF16 || g.a_mode != PDMK_A_COLK || g.b_mode == PDMK_B_ROWK || !g.out_f32) return 1;
-    const bool conv = g.b_mode == PDMK_B_COLK_CONV;
-    if ((g.M % 8) || (g.N % 8) || (g.lda % 8) || (!conv && (g.ldb % 8))) return 1;
-    if (conv && ((g.conv_ci % 8) || (g.conv_ld % 8) || g.conv_mode == 3 || g.conv_mode == 4 || g.conv_mode > 8)) return 1;
-    if (id == kNumW || id == kNumW + 1) {
-        if (!wgrad_halo_ok(g)) return 1;
-        const int nblk = (g.K + 127) / 128, sk = g.splitk > 1 ? g.splitk : 1, bm = id == kNumW ? 64 : 128;
-        if (sk > nblk) return 1;
-        dim3 grid(((g.M + bm - 1) / bm) * ((g.conv_ci + 63) / 64), sk);
-        if (bm == 64) hipLaunchKernelGGL((conv_wgrad_halo_kernel<2, 3>), grid, dim3(NT), 0, st, g, (unsigned)a_bytes, (unsigned)b_bytes);
-        else hipLaunchKernelGGL((conv_wgrad_halo_kernel<4, 2>), grid, dim3(NT), 0, st, g, (unsigned)a_bytes, (unsigned)b_bytes);
-        return hipGetLastError() == hipSuccess ? 0 : -1000;
-    }
-    if (id < 0 || id >= kNumW) return 1;
-    int lg_wo = -1, lg_howo = -1;
-    if (conv) {
-        auto lg = [](int v) { int l = 0; if (v <= 0 || (v & (v - 1))) return -1; while ((1 << l) < v) ++l; return l; };
-        lg_wo = lg(g.conv_wo);
-        lg_howo = lg(g.conv_ho * g.conv_wo);
-        if (lg_wo < 0 || lg_howo < 0) lg_wo = lg_howo = -1;
-    }
-    const WCfg c = kWCfgs[id];
-    const int bn = 32 * c.nj;
-    dim3 grid(((g.M + c.bm - 1) / c.bm) * ((g.N + bn - 1) / bn), g.splitk > 1 ? g.splitk : 1);
-#define PDMK_WG_GO(BMv, NJv, STv, OCv)                                                                                \
-    case (BMv * 1000 + NJv * 100 + STv * 10 + OCv):                                                                   \
-        if (conv) hipLaunchKernelGGL((wgrad_ring_kernel<true, BMv, NJv, STv, OCv>), grid, dim3(NT), 0, st, g, lg_wo,  \
-                                     lg_howo, (unsigned)a_bytes, (unsigned)b_bytes);                                  \
-        else hipLaunchKernelGGL((wgrad_ring_kernel<false, BMv, NJv, STv, OCv>), grid, dim3(NT), 0, st, g, lg_wo,      \
-                                lg_howo, (unsigned)a_bytes, (unsigned)b_bytes);                                       \
-        break;
-    switch (c.bm * 1000 + c.nj * 100 + c.stages * 10 + c.occ) {
-        PDMK_WG_GO(128, 4, 4, 2) PDMK_WG_GO(128, 4, 2, 4) PDMK_WG_GO(64, 4, 3, 4) PDMK_WG_GO(128, 2, 3, 4) PDMK_WG_GO(64, 2, 4, 4)
-        default: return 1;
-    }
-#undef PDMK_WG_GO
-    return hipGetLastError() == hipSuccess ? 0 : -1000;
+    const pdmk_cand::Ref r = wgrad_decode(id);
+    if (r.fam == pdmk_cand::NONE) return 1;
+    const bool halo = r.fam == pdmk_cand::HALO;
+    const Place p = halo ? wgrad_halo_place(g, kWgradHalo[r.row]) : wgrad_place(g, kWgrad[r.row]);
+    if (!p.ok) return 1;
+    const PlainFn fn = halo ? kWgradHalo[r.row].plain : kWgrad[r.row].plain[g.b_mode == PDMK_B_COLK_CONV];
+    fn(dim3(p.tiles, p.splits), st, g, (unsigned)a_bytes, (unsigned)b_bytes, p.aux0, p.aux1);
+    return launched();
 }
 
-// grouped weight gradients: candidate `id` (numbering of pdmk_wgrad_ring_launch) for n problems in one grid; 1 = not served
+// grouped weight gradients: all members 3x3 convs or none
 int pdmk_wgrad_ring_group_launch(const pdmk_gemm_args* gs, int n, hipStream_t st, const long* a_bytes, const long* b_bytes, int id) {
     using namespace pdmk_ring;
-    if (n < 2 || n > PDMK_GEMM_GROUP_MAX || id < 0 || id > kNumW + 1) return 1;
+    const pdmk_cand::Ref r = wgrad_decode(id);
+    if (n < 2 || n > PDMK_GEMM_GROUP_MAX || r.fam == pdmk_cand::NONE) return 1;
     const bool conv = gs[0].b_mode == PDMK_B_COLK_CONV;
-    const bool halo = id == kNumW || id == kNumW + 1;
-    GroupGrid G;
-    for (int i = 0; i < n; ++i) {
-        const pdmk_gemm_args& g = gs[i];
-        if (g.dtype != PDMK_BF16 || g.a_mode != PDMK_A_COLK || g.b_mode == PDMK_B_ROWK || !g.out_f32) return 1;
-        if ((g.b_mode == PDMK_B_COLK_CONV) != conv) return 1;
-        if ((g.M % 8) || (g.N % 8) || (g.lda % 8) || (!conv && (g.ldb % 8))) return 1;
-        if (conv && ((g.conv_ci % 8) || (g.conv_ld % 8) || g.conv_mode == 3 || g.conv_mode == 4 || g.conv_mode > 8)) return 1;
-        const int sk = g.splitk > 1 ? g.splitk : 1;
-        if (halo) {
-            if (!wgrad_halo_ok(g)) return 1;
-            const int nblk = (g.K + 127) / 128, bm = id == kNumW ? 64 : 128;
-            if (sk > nblk) return 1;
-            G.add(i, g, ((g.M + bm - 1) / bm) * ((g.conv_ci + 63) / 64), sk, a_bytes[i], b_bytes[i]);
-        } else {
-            int lg_wo = -1, lg_howo = -1;
-            if (conv) {
-                auto lg = [](int v) { int l = 0; if (v <= 0 || (v & (v - 1))) return -1; while ((1 << l) < v) ++l; return l; };
-                lg_wo = lg(g.conv_wo);
-                lg_howo = lg(g.conv_ho * g.conv_wo);
-                if (lg_wo < 0 || lg_howo < 0) lg_wo = lg_howo = -1;
-            }
-            const WCfg c = kWCfgs[id];
-            const int bn = 32 * c.nj;
-            G.add(i, g, ((g.M + c.bm - 1) / c.bm) * ((g.N + bn - 1) / bn), sk, a_bytes[i], b_bytes[i], lg_wo, lg_howo);
-        }
+    if (r.fam == pdmk_cand::HALO) {
+        const WgradHaloCand& c = kWgradHalo[r.row];
+        return group_go(gs, n, st, a_bytes, b_bytes, c.group, [&](const pdmk_gemm_args& g) {
+            return (g.b_mode == PDMK_B_COLK_CONV) == conv ? wgrad_halo_place(g, c) : kNotServed;
+        });
     }
-    G.finish(n);
-    const dim3 grid(G.total);
-    if (halo) {
-        if (id == kNumW) hipLaunchKernelGGL((conv_wgrad_halo_group_kernel<2, 3>), grid, dim3(NT), 0, st, G.gg);
-        else hipLaunchKernelGGL((conv_wgrad_halo_group_kernel<4, 2>), grid, dim3(NT), 0, st, G.gg);
-        return hipGetLastError() == hipSuccess ? 0 : -1000;
-    }
-    const WCfg c = kWCfgs[id];
-#define PDMK_WG_GGO(BMv, NJv, STv, OCv)                                                                               \
-    case (BMv * 1000 + NJv * 100 + STv * 10 + OCv):                                                                   \
-        if (conv) hipLaunchKernelGGL((wgrad_ring_group_kernel<true, BMv, NJv, STv, OCv>), grid, dim3(NT), 0, st, G.gg); \
-        else hipLaunchKernelGGL((wgrad_ring_group_kernel<false, BMv, NJv, STv, OCv>), grid, dim3(NT), 0, st, G.gg);   \
-        break;
-    switch (c.bm * 1000 + c.nj * 100 + c.stages * 10 + c.occ) {
-        PDMK_WG_GGO(128, 4, 4, 2) PDMK_WG_GGO(128, 4, 2, 4) PDMK_WG_GGO(64, 4, 3, 4) PDMK_WG_GGO(128, 2, 3, 4) PDMK_WG_GGO(64, 2, 4, 4)
-        default: return 1;
-    }
-#undef PDMK_WG_GGO
-    return hipGetLastError() == hipSuccess ? 0 : -1000;
+    const RingCand& c = kWgrad[r.row];
+    return group_go(gs, n, st, a_bytes, b_bytes, c.group[conv], [&](const pdmk_gemm_args& g) {
+        return (g.b_mode == PDMK_B_COLK_CONV) == conv ? wgrad_place(g, c) : kNotServed;
+    });
 }

@@ -26,6 +26,7 @@
 // 0-20 % on the M = 32768, K = 320 shapes with N >= 640, reads A exactly once (PMC), and is bit-identical to it.
 // Fused epilogues: bias, residual OR accumulate (bf16), PDMK_EPI_GEGLU (with the optional pre-activation copy).
 #include "common.h"
+#include "gemm_candidates.h"
 
 #include <stdio.h>
 #include <stdlib.h>
