@@ -184,6 +184,11 @@ int pdmk_gemm_plan(const pdmk_gemm_args* args, pdmk_stream stream, int32_t* spli
  * 1.. = LDS-DMA ring shapes) and the symbol name a profiler reports for (a_mode, b_mode, candidate).
  * PDMK_PLAN_CACHE=<file> persists the plan cache across processes; PDMK_GEMM_TUNE=0 disables on-device tuning. */
 int pdmk_gemm_last_candidate(void);
+/* Measurement helper (like pdmk_attn_last_forms): which form of candidate 0 the calling thread's last pdmk_gemm launched -
+ * 0 = none (an LDS-DMA candidate ran, see pdmk_gemm_last_candidate), 1 = igemm_kernel with K-step chunks 8 (up to 512
+ * workgroups), 2 = igemm_kernel with K-step chunks 4 (more than 512 workgroups), 3 = igemm_dma_kernel with 128-row tiles,
+ * 4 = igemm_dma_kernel with 256-row tiles (320 or more of them). */
+int pdmk_gemm_last_form(void);
 int pdmk_gemm_candidate_name(int a_mode, int b_mode, int id, char* buf, int n);
 /* Second half of a split-K GEMM (small-M layers at 8x8 / 16x16 latents, every weight gradient: too few output tiles
  * to fill 256 CUs): pdmk_gemm left fp32 partials in ws - `nslab` slabs [nslab][M][N] written with accumulate = 2, or one

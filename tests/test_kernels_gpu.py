@@ -9,6 +9,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import gemm_fixtures as gf
+
 pytestmark = pytest.mark.gpu
 
 DT = {"f32": torch.float32, "bf16": torch.bfloat16}
@@ -590,15 +592,24 @@ def test_ring_gemm_every_tile_shape(dev, force_cfg, cand):
     force_cfg("PDMK_RING_CFG", cand)
     torch.manual_seed(7)
     dt = torch.bfloat16
+    # which candidate has to run: the ring rows 1..19 serve every problem here; the row-block ids keep all of K in registers
+    # (20: K <= 320, 21: K <= 640) and refuse split-K, fp32 output and convs - those fall back to candidate 0
+    ring = 1 <= cand <= 19
+    rowblock_k = {20: 320, 21: 640}.get(cand, 0)
+
+    def ran(served, what):
+        assert k.last_candidate() == (cand if served else 0), f"{what}: candidate {k.last_candidate()} ran"
     for M, N, K in ((515, 352, 608), (200, 136, 96), (64, 32, 32), (1000, 1280, 160)):
         A, B = rnd((M, K), dev, dt), rnd((N, K), dev, dt, K ** -0.5)
         bias, R = torch.randn(N, device=dev), rnd((M, N), dev, dt)
         C = torch.full((M, N), 3.0, device=dev, dtype=dt)
         k.gemm(A, B, C, M, N, K, K, K, N, bias=bias, R=R, ldr=N)
+        ran(ring or K <= rowblock_k, f"linear {M}x{N}x{K}")
         ref = A.float() @ B.float().t() + bias + R.float()
         close(C, ref, 2e-2, f"linear {M}x{N}x{K}")
         Cf = torch.zeros(M, N, device=dev)
         k.gemm(A, B, Cf, M, N, K, K, K, N, out_f32=True, splitk=3)
+        ran(ring, f"linear split-K {M}x{N}x{K}")
         close(Cf, A.float() @ B.float().t(), 2e-2, f"linear split-K {M}x{N}x{K}")
     Bn, Ci, Co, Hs = 2, 96, 72, 12
     x = rnd((Bn, Hs, Hs, Ci), dev, dt)
@@ -615,6 +626,7 @@ def test_ring_gemm_every_tile_shape(dev, force_cfg, cand):
         y = torch.zeros(Bn * Ho * Ho, Co, device=dev, dtype=dt)
         k.gemm(x, conv_w_pack(w), y, Bn * Ho * Ho, Co, 9 * Ci, 0, 9 * Ci, Co, a_mode=k.A_CONV,
                conv=(Bn, Hs, Hs, Ci, Ho, Ho, mode, Ci))
+        ran(ring, f"conv mode {mode}")
         close(y, ref.permute(0, 2, 3, 1).reshape(-1, Co), 2e-2, f"conv mode {mode}")
 
 
@@ -1189,10 +1201,14 @@ def test_gemm_group_linear_bit_equal_to_separate(dev, force_cfg, cand):
             assert torch.equal(a_, b_), (cand, n)
         for a_, b_ in zip(sep_f, grp_f):
             assert a_ is None or torch.equal(a_, b_)
-    # and against fp32 math (first problem)
-    M, N, K, A, W, b, R, acc, geglu, C0 = probs[0]
-    ref = A.float() @ W.float().t() + b + R[:, :N].float()
-    close(grp[0][:, :N].float(), ref, 2e-2, "group vs fp32")
+    # and EVERY member against fp64 of its own formula, through the derived bound of tests/gemm_fixtures.py (the fused-GEGLU
+    # member has its own reference test, test_gemm_fused_geglu_epilogue); the 16 columns behind N keep what they held
+    for (M, N, K, A, W, b, R, acc, geglu, C0), out in zip(probs, grp):
+        if geglu:
+            continue
+        addends = [t for t in (b, R[:, :N] if R is not None else None, C0[:, :N] if acc else None) if t is not None]
+        gf.assert_within_bound(out[:, :N], "linear", A, W, K, addends=addends, what=f"group cand{cand} linear {M}x{N}x{K}")
+        assert torch.equal(out[:, N:], C0[:, N:]), (cand, M, N, K)
 
 
 @pytest.mark.parametrize("cand", [13, 14, 15, 16] + RING_CANDS)
@@ -1225,10 +1241,10 @@ def test_gemm_group_conv_bit_equal_to_separate(dev, force_cfg, cand):
     assert got == 3, (cand, got)
     for a_, b_ in zip(sep, grp):
         assert torch.equal(a_, b_), cand
-    Ci, Co, x, w, b, rv, R = probs[0]
-    ref = F.conv2d(x.float().view(B, H, H, Ci).permute(0, 3, 1, 2), w.float().view(Co, 3, 3, Ci).permute(0, 3, 1, 2), b, padding=1)
-    ref = ref.permute(0, 2, 3, 1).reshape(B * H * H, Co) + rv.repeat_interleave(H * H, 0)
-    close(grp[0].float(), ref, 2e-2, "group conv vs fp32")
+    for (Ci, Co, x, w, b, rv, R), out in zip(probs, grp):          # every member against fp64, through the derived bound
+        addends = [t for t in (b, rv.repeat_interleave(H * H, 0) if rv is not None else None, R) if t is not None]
+        gf.assert_within_bound(out, "conv", x, w, 9 * Ci, c=gf.conv_geom(B, H, H, Ci, 0), addends=addends,
+                               what=f"group cand{cand} conv {Ci}->{Co}")
 
 
 @pytest.mark.parametrize("cand", [1, 2, 3, 4, 5, 6, 7])
@@ -1269,15 +1285,12 @@ def test_gemm_group_wgrad_matches_separate(dev, force_cfg, cand):
         assert torch.equal(a_, b_), cand
     for a_, b_ in zip(sep_c, grp_c):
         assert torch.allclose(a_, b_, rtol=1e-5, atol=1e-5)          # bias gradient: fp32 atomics over the splits
-    No, Ki, sk, dy, x = probs[0]
-    got0 = grp[0].view(sk, No, -1).sum(0)
-    if conv:
-        xi = x.float().view(B, H, H, Ki).permute(0, 3, 1, 2)
-        cols = torch.nn.functional.unfold(xi, 3, padding=1).view(B, Ki, 9, H * H).permute(0, 3, 2, 1).reshape(P, 9 * Ki)
-        ref = dy.float().t() @ cols
-    else:
-        ref = dy.float().t() @ x.float()
-    close(got0, ref, 2e-2, "group wgrad vs fp32")
+    for (No, Ki, sk, dy, x), ws, c in zip(probs, grp, grp_c):      # every member against fp64, through the derived bound
+        got = ws.view(sk, No, -1).double().sum(0).float()          # the slabs are fp32 partial sums: their exact sum, as fp32 output
+        gf.assert_within_bound(got, "wgrad_conv" if conv else "wgrad", dy, x, P, c=gf.conv_geom(B, H, H, Ki, 0) if conv else None,
+                               splitk=sk, what=f"group wcand{cand} wgrad {No}x{Ki} sk{sk}")
+        cs_bound = 2.0 * (P + sk + 8) * gf.U32 * dy.double().abs().sum(0).cpu()
+        assert gf.ratio(c, dy.double().sum(0).cpu(), cs_bound) <= 1.0, (cand, No, Ki)
 
 
 @pytest.mark.parametrize("B,H,Ci,Co", [(2, 8, 64, 160), (2, 16, 96, 64), (1, 32, 32, 320), (3, 8, 160, 128)])

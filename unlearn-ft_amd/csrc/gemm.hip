@@ -416,6 +416,8 @@ __global__ __launch_bounds__(64 * NW) void igemm_kernel(pdmk_gemm_args g, int lg
     }
 }
 
+thread_local int g_last_form = -1;     // pdmk_gemm_last_form(): which K-step-32 form the last pdmk_gemm launched (0 = none)
+
 inline int ilog2_exact(int v) {
     if (v <= 0 || (v & (v - 1))) return -1;
     int l = 0;
@@ -475,6 +477,7 @@ template <typename T> int launch(const pdmk_gemm_args& g, hipStream_t st) {
         }
     } else return -2;
 #undef PDMK_GO
+    g_last_form = many ? 2 : 1;
     PDMK_CHECK_LAUNCH();
     return 0;
 }
@@ -602,6 +605,7 @@ int launch_legacy(const pdmk_gemm_args& g, hipStream_t st) {
 }
 
 int launch_candidate(const pdmk_gemm_args& g, hipStream_t st, int id) {
+    g_last_form = 0;                                     // the K-step-32 launchers below set their own
     if (id <= 0) return launch_legacy(g, st);
     long ab, bb;
     if (!operand_bytes(g, &ab, &bb)) return 1;
@@ -869,6 +873,7 @@ extern "C" int pdmk_gemm(const pdmk_gemm_args* a, pdmk_stream stream) {
     if (const int vrc = validate_args(g)) return vrc;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     g_last_candidate = 0;
+    g_last_form = 0;
     if (g.ln_gamma) {                                   // one kernel family serves it: no plan, no tuning
         long ab, bb;
         const int id = ln_candidate(g, &ab, &bb);
@@ -1043,6 +1048,7 @@ extern "C" int pdmk_gemm_group(const pdmk_gemm_args* a, int n, pdmk_stream strea
         const int rc = group_launch(a, n, st, forced_group());
         if (rc == 0) {
             g_last_candidate = forced_group();
+            g_last_form = 0;
             if (grouped_out) *grouped_out = n;
             return 0;
         }
@@ -1085,6 +1091,7 @@ extern "C" int pdmk_gemm_group(const pdmk_gemm_args* a, int n, pdmk_stream strea
         const int rc = group_launch(a, n, st, id);
         if (rc == 0) {
             g_last_candidate = id;
+            g_last_form = 0;
             if (grouped_out) *grouped_out = n;
             return 0;
         }
@@ -1096,6 +1103,8 @@ extern "C" int pdmk_gemm_group(const pdmk_gemm_args* a, int n, pdmk_stream strea
 /* Candidate the calling thread's last pdmk_gemm used (0 = K-step-32 kernels, 1.. = LDS-DMA ring shapes) and the kernel
  * symbol a profiler shows for it; measurement only (bench.py labels its HIP-event timings with these). */
 extern "C" int pdmk_gemm_last_candidate(void) { return g_last_candidate; }
+extern "C" int pdmk_gemm_last_form(void) { return g_last_form; }
+void pdmk_gemm_note_form(int form) { g_last_form = form; }
 extern "C" int pdmk_gemm_candidate_name(int a_mode, int b_mode, int id, char* buf, int n) {
     if (!buf || n <= 0) return -1;
     if (id <= 0) {

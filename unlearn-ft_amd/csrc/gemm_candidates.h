@@ -13,6 +13,7 @@
 // All launch functions return 0 = launched, 1 = this candidate does not serve the problem (the caller falls back),
 // -1000 = launch error.  a_bytes / b_bytes: extent of the operands (buffer descriptors).
 int pdmk_gemm_dma_launch(const pdmk_gemm_args& g, hipStream_t st, long a_bytes, long b_bytes);                        // gemm_dma.hip
+void pdmk_gemm_note_form(int form);                                  // gemm.hip: what pdmk_gemm_last_form() reports (pdmk.h)
 int pdmk_gemm_ring_launch(const pdmk_gemm_args& g, hipStream_t st, long a_bytes, long b_bytes, int id);               // gemm_ring.hip
 int pdmk_gemm_ring_group_launch(const pdmk_gemm_args* gs, int n, hipStream_t st, const long* a_bytes, const long* b_bytes, int id);
 int pdmk_gemm_ring_num_configs();                                    // ring + halo + row-block ids

@@ -327,5 +327,6 @@ int pdmk_gemm_dma_launch(const pdmk_gemm_args& g, hipStream_t st, long a_bytes, 
         }
     }
 #undef PDMK_DMA_GO
+    pdmk_gemm_note_form(big ? 4 : 3);
     return hipGetLastError() == hipSuccess ? 0 : -1000;
 }

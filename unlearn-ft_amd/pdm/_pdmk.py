@@ -62,6 +62,7 @@ _SIGS = {
     "pdmk_up2_pack_weights": ([vp, vp, vp, i32, i32, i32, vp], i32),
     "pdmk_up2_combine_wgrad": ([vp, vp, i32, i32, vp], i32),
     "pdmk_gemm_last_candidate": ([], i32),
+    "pdmk_gemm_last_form": ([], i32),
     "pdmk_gemm_candidate_name": ([i32, i32, i32, C.c_char_p, i32], i32),
     "pdmk_splitk_finish": ([vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, i32, i32, i32, i32, vp], i32),
     "pdmk_splitk_finish_colstat": ([vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, i32, i32, i32, vp, i32, i32, i32, vp], i32),
@@ -481,6 +482,12 @@ def attn_last_forms():
 def last_candidate():
     """Candidate id of the calling thread's last pdmk_gemm launch (0 = K-step-32 kernels, 1.. = ring / halo shapes)."""
     return int(_lib.pdmk_gemm_last_candidate())
+
+
+def last_form():
+    """Form of candidate 0 the calling thread's last pdmk_gemm launched: 0 = none (an LDS-DMA candidate ran), 1 / 2 = igemm_kernel
+    KCH 8 / KCH 4, 3 / 4 = igemm_dma_kernel BM 128 / BM 256."""
+    return int(_lib.pdmk_gemm_last_form())
 
 
 def candidate_name(a_mode, b_mode, cand):
