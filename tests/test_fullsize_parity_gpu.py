@@ -349,8 +349,8 @@ def test_benchmarked_configuration_matches_oracle(dev, tmp_path):
     st = BilevelStepper(student, teacher)
     gr = GraphedBilevel(st, B, 4, 64, 64, 77, 1024, prefetch=True)      # as bench.py builds it: cross-step teacher prefetch, 12 shares
     gr.capture(bilevel=True)
-    assert len(gr.g_main.bwd) >= 2 and (gr.g_main.teacher is None) == st.lockstep
-    assert gr.prefetch != st.lockstep and (gr.g_main.loss is not None) == gr.prefetch
+    assert len(gr.g_main.bwd) >= 2 and gr.g_main.teacher is not None
+    assert gr.prefetch and gr.g_main.loss is not None
     # GroupNorm statistics from the producing GEMM's epilogue (pdmk_gemm_args.colstat): on unless PDMK_GN_EPI=0, and then the
     # path the captured step runs for most of its GroupNorms (the rest: split-K producers, copied concat halves)
     gc = student.engine.gn_count

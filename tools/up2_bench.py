@@ -2,7 +2,7 @@
 """Upsample2D conv (nearest x2 + 3x3) on one MI355X: the 3x3 form with the upsampling fused into the gather (conv_mode 2) against
 the four 2x2 phase convs on the low-resolution image (conv_mode 5..12), forward / input gradient / weight gradient, at the
 three upsampler shapes of SD-2.1 (B = 8).  python tools/up2_bench.py"""
-import os, sys
+import contextlib, os, sys
 os.environ["PDMK_ENV_DYNAMIC"] = "1"
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "unlearn-ft_amd"))
@@ -44,13 +44,11 @@ for (B, H, C) in [(8, 32, 640), (8, 16, 1280), (8, 8, 1280)]:
     print(f"  fwd 3x3 (mode 2, tuned)            {t:8.1f} us  {fl3/t/1e6:7.1f} TF/s(3x3 flops)")
 
     def fwd_phases(grouped):
-        with k.Recorder() as r:
+        with (k.Recorder() if grouped else contextlib.nullcontext()) as r:      # not recording: gemm() launches at once
             for p in range(4):
                 k.gemm(x, wp[p], y, Ml, C, 4 * C, 0, 4 * C, C, a_mode=k.A_CONV, conv=geo(5 + p, C), bias=bias)
         if grouped:
             k.gemm_group(r.recs)
-        else:
-            for rec in r.recs: rec.run()
     for cand in (15, 16):
         os.environ["PDMK_RING_CFG"] = str(cand)
         t = gtime(lambda: fwd_phases(False))
@@ -86,14 +84,12 @@ for (B, H, C) in [(8, 32, 640), (8, 16, 1280), (8, 8, 1280)]:
 
     def wgrad_new(grouped):
         k.zero_(dwp)
-        with k.Recorder() as r:
+        with (k.Recorder() if grouped else contextlib.nullcontext()) as r:
             for p in range(4):
                 k.gemm(dy, x, dwp[p], C, 4 * C, Ml, C, 0, 4 * C, a_mode=k.A_COLK, b_mode=k.B_COLK_CONV, conv=geo(5 + p, C),
                        out_f32=True, splitk=sk, accumulate=(sk == 1), dtype=k.BF16, colsum_out=db)
         if grouped:
             k.gemm_group(r.recs)
-        else:
-            for rec in r.recs: rec.run()
         k.up2_combine_wgrad(dwp, dw, C, C)
     t, tg = gtime(lambda: wgrad_new(False)), gtime(lambda: wgrad_new(True))
     print(f"  wgrad 4 phases (sk {sk}) + combine: separate {t:8.1f} us   grouped(tuned choice) {tg:8.1f} us ({fl2/tg/1e6:6.1f} TF/s exec)")

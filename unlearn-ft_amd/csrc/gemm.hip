@@ -26,9 +26,6 @@
 namespace {
 
 #define PDMK_GEMM_NBUF 2
-#ifndef PDMK_GEMM_PF2
-#define PDMK_GEMM_PF2 0      // 1: two K-tiles in flight in registers (measured SLOWER on MI355X: +60-120 VGPRs), 0: one
-#endif
 constexpr int BM = 128, BN = 128;
 // Three geometries are instantiated and chosen per launch (measured on MI355X, tools/gemm_bench.py):
 //   KCH = 16-byte chunks per tile row:  8 -> K-step 64 bf16, 72 KiB LDS (2 blocks/CU);  4 -> K-step 32, 48 KiB (3/CU)
@@ -138,9 +135,6 @@ __global__ __launch_bounds__(64 * NW) void igemm_kernel(pdmk_gemm_args g, int lg
     }
 
     u32x4 ra[NLD], rb[NLD];
-#if PDMK_GEMM_PF2
-    u32x4 ra2[NLD], rb2[NLD];     // second register set: two tiles in flight
-#endif
     // fused bias gradient (wgrad only): the blocks of the first n-tile also sum their A = dY tiles over the reduction
     // dim; every tile passes through store_tiles exactly once, which is where the registers are summed.
     const bool do_colsum = (AMODE == PDMK_A_COLK) && g.colsum_out != nullptr && n0 == 0;
@@ -245,29 +239,7 @@ __global__ __launch_bounds__(64 * NW) void igemm_kernel(pdmk_gemm_args g, int lg
         }
     };
 
-#if PDMK_GEMM_PF2
-    // two tiles in flight: while tile kt is multiplied out of LDS, tile kt+1 sits in one register set (written to LDS
-    // after the MFMAs) and tile kt+2 is being fetched into the other one
-    load_tiles(kt0, ra, rb);
-    if (kt0 + 1 < kt1) load_tiles(kt0 + 1, ra2, rb2);
-    store_tiles(0, ra, rb);
-    __syncthreads();
-    int cur = 0;
-    for (int kt = kt0;;) {
-        if (kt + 2 < kt1) load_tiles(kt + 2, ra, rb);
-        compute(cur);
-        if (kt + 1 < kt1) store_tiles(cur ^ 1, ra2, rb2);
-        __syncthreads();
-        cur ^= 1;
-        if (++kt >= kt1) break;
-        if (kt + 2 < kt1) load_tiles(kt + 2, ra2, rb2);
-        compute(cur);
-        if (kt + 1 < kt1) store_tiles(cur ^ 1, ra, rb);
-        __syncthreads();
-        cur ^= 1;
-        if (++kt >= kt1) break;
-    }
-#else
+    // one K-tile in flight in registers (two, with a second register set, measured SLOWER on MI355X: +60-120 VGPRs)
     load_tiles(kt0, ra, rb);
     store_tiles(0, ra, rb);
     __syncthreads();
@@ -280,7 +252,6 @@ __global__ __launch_bounds__(64 * NW) void igemm_kernel(pdmk_gemm_args g, int lg
         __syncthreads();
         cur ^= 1;
     }
-#endif
 
     if (do_colsum) {      // combine the BK k-rows through LDS (all tile reads are behind the last barrier)
         float* red = reinterpret_cast<float*>(smem);
@@ -701,7 +672,7 @@ template <typename F> float time_us(F fn, hipStream_t st, hipEvent_t e0, hipEven
 
 // time `reps` launches of candidate `id` (plus, for split-K, the workspace clear and the finish pass) in microseconds
 float time_candidate(const pdmk_gemm_args& a, hipStream_t st, int id, float* ws, void* fin_out, hipEvent_t e0, hipEvent_t e1) {
-    static const int reps = getenv("PDMK_TUNE_REPS") ? std::max(1, atoi(getenv("PDMK_TUNE_REPS"))) : 3;     // (A/B knob: 8 / 20 give the same step as 3)
+    constexpr int reps = 3;     // (8 / 20 timing launches per candidate gave the same step as 3: 194.0-195.1 images/s)
     auto once = [&]() -> int {
         if (a.splitk > 1 && a.a_mode != PDMK_A_COLK) {    // slab split-K + the finish pass that adds the slabs
             const int rc = launch_candidate(a, st, id);
@@ -1154,9 +1125,9 @@ extern "C" int pdmk_gemm_plan(const pdmk_gemm_args* a, pdmk_stream stream, int32
         if (id < 0) continue;
         g_plan_cfg[make_key(g, sk)] = id;
         plan_file_append('c', make_key(g, sk), id);
-        // a split must win by > 3 % (PDMK_SPLIT_MARGIN=<percent>: A/B knob - in the step the finish pass carries bias / residual /
-        // statistics and runs from cold operands, which the back-to-back timing launches do not see)
-        static const float margin = getenv("PDMK_SPLIT_MARGIN") ? 1.0f - 0.01f * (float)atof(getenv("PDMK_SPLIT_MARGIN")) : 0.97f;
+        // a split must win by > 3 %: in the step the finish pass carries bias / residual / statistics and runs from cold operands,
+        // which the back-to-back timing launches do not see (10 % / 20 % / never measured 194.2 / 192.5 / 157.1 against 195.3 images/s)
+        constexpr float margin = 0.97f;
         if (t < bt * (sk > 1 ? margin : 1.0f)) { bt = t; best_sk = sk; }
     }
     g_plan_sk[key0] = best_sk;

@@ -524,8 +524,8 @@ __global__ __launch_bounds__(NT, OCC) void igemm_ring_kernel(pdmk_gemm_args g, u
     __shared__ __attribute__((aligned(1024))) unsigned char smem[ring_smem_bytes(BM, NJ, STAGES)];
     igemm_ring_body<CONV, BM, NJ, STAGES, OCC>(g, a_bytes, b_bytes, lc_plain(), smem);
 }
-// the same body for up to PDMK_GEMM_GROUP_MAX independent problems in one grid (teacher || student layer pairs, the weight
-// gradients of several layers): longer launches, one boundary instead of several
+// the same body for up to PDMK_GEMM_GROUP_MAX independent problems in one grid (the four phases of an upsampling conv, the
+// weight gradients of several layers): longer launches, one boundary instead of several
 template <bool CONV, int BM, int NJ, int STAGES, int OCC>
 __global__ __launch_bounds__(NT, OCC) void igemm_ring_group_kernel(pdmk_gemm_group_dev gg) {
     __shared__ __attribute__((aligned(1024))) unsigned char smem[ring_smem_bytes(BM, NJ, STAGES)];
@@ -1401,10 +1401,7 @@ static int halo_tile_w(const pdmk_gemm_args& g, const HaloCand& c, int splitk) {
     const int H = g.conv_hi, W = g.conv_wi, HW = H * W;
     if (HW < bm) return (bm % HW) == 0 && (bm / HW) * (H + 2) * (W + 2) <= pmax ? W : 0;
     if (HW % bm) return 0;
-    static const int pref = getenv("PDMK_HALO_TW") ? atoi(getenv("PDMK_HALO_TW")) : 0;   // experiment knob: preferred block width
-    if (pref > 0 && pref < W && (W % pref) == 0 && (bm % pref) == 0 && (H % (bm / pref)) == 0 &&
-        (bm / pref + 2) * (pref + 2) <= pmax)
-        return pref;
+    // full rows first, then the widest power-of-two block that fits (a preferred narrower block width measured +-0)
     if ((bm % W) == 0 && (bm / W + 2) * (W + 2) <= pmax) return W;
     for (int tw = 128; tw >= 8; tw >>= 1) {
         if (tw >= W || (W % tw) || (bm % tw)) continue;

@@ -177,28 +177,26 @@ def _chk(rc, name):
 
 PROFILE = None   # bench.py sets this to a list: every gemm launch is then bracketed by HIP events on the launch stream
 
-# ---- lockstep recording (teacher || student forward, pdmk_gemm_group): while RECORD is a list every launch wrapper below
-# appends a record instead of launching; run_lockstep() then walks two record lists side by side and issues the launches of
-# both, pairing what the library can serve in one grouped launch.  Host-side work (allocation, planning queries) still
-# happens at record time; records keep their operand tensors alive until they have run.
+# ---- grouped launches (pdmk_gemm_group): while RECORD is a list gemm() appends its filled argument block instead of launching;
+# gemm_group() then issues the collected problems as one launch where the library has a kernel shape for all of them.
 RECORD = None
-TAG = ""         # set by the engine before every layer op: records of the same layer op of two models share a tag
 GROUP_MAX = 8
-STATS = {"launches": 0, "grouped": 0}      # launches issued through records since the last reset (tests / bench bookkeeping)
+STATS = {"launches": 0, "grouped": 0}      # launches issued through gemm_group since the last reset (tests / bench bookkeeping)
 
 
 class Rec:
-    __slots__ = ("tag", "kind", "fn", "g", "keep", "macs", "meta")
+    """One recorded gemm() call: the argument block, the logical MACs (profiling) and the operand tensors, kept alive until
+    the grouped launch has been issued."""
+    __slots__ = ("g", "macs", "keep")
+    kind = "gemm"       # the only kind left; the grouped-launch tests still assert it of every record
 
-    def __init__(self, kind, fn, g=None, keep=(), macs=None, meta=None):
-        self.tag, self.kind, self.fn, self.g, self.keep, self.macs, self.meta = TAG, kind, fn, g, keep, macs, meta
-
-    def run(self):
-        self.fn()
+    def __init__(self, g, macs=None, keep=()):
+        self.g, self.macs, self.keep = g, macs, keep
 
 
 class Recorder:
-    """with Recorder() as r: ...launch wrappers record...;  r.recs is the list."""
+    """with Recorder() as r: ...gemm() calls...;  r.recs is the list for gemm_group().  It collects the argument blocks of
+    gemm() for one grouped launch and nothing else: every other launch wrapper runs at once, recording or not."""
 
     def __enter__(self):
         global RECORD
@@ -210,19 +208,6 @@ class Recorder:
         global RECORD
         RECORD = self.prev
         return False
-
-
-def _recordable(kind):
-    """Launch wrapper that defers itself while recording (generic: replayed as a closure, never grouped)."""
-    def deco(fn):
-        def wrapped(*a, **kw):
-            if RECORD is not None:
-                RECORD.append(Rec(kind, lambda: fn(*a, **kw)))
-                return None
-            return fn(*a, **kw)
-        wrapped.__name__, wrapped.__doc__ = fn.__name__, fn.__doc__
-        return wrapped
-    return deco
 
 
 def _launch_gemm(g, macs, shape):
@@ -263,41 +248,6 @@ def gemm_group(recs):
     return int(got.value)
 
 
-def run_lockstep(ta, tb, group=True):
-    """Issue two recorded launch sequences (each in its own order) side by side: records of both lists with the same tag and
-    kind go out together - as ONE launch when they are GEMMs the library groups - everything else one by one.  Any
-    interleaving that keeps each list's order is valid (the two sequences are independent)."""
-    last = {}
-    for idx, r in enumerate(ta):
-        last[(r.tag, r.kind)] = idx
-    i = j = 0
-    while i < len(ta) or j < len(tb):
-        if i < len(ta) and j < len(tb) and ta[i].tag == tb[j].tag and ta[i].kind == tb[j].kind:
-            a, b = ta[i], tb[j]
-            i, j = i + 1, j + 1
-            if group and a.kind == "gemm":
-                gemm_group([a, b])
-            elif group and a.kind in _GROUP_FNS:
-                _GROUP_FNS[a.kind]([a, b])
-                STATS["launches"] += 1
-                STATS["grouped"] += 2
-            else:
-                a.run()
-                b.run()
-                STATS["launches"] += 2
-        elif j < len(tb) and (i >= len(ta) or last.get((tb[j].tag, tb[j].kind), -1) < i):
-            tb[j].run()
-            j += 1
-            STATS["launches"] += 1
-        else:
-            ta[i].run()
-            i += 1
-            STATS["launches"] += 1
-
-
-_GROUP_FNS = {}     # kind -> fn(list of Rec): grouped forms of the non-GEMM forward kernels (filled in below)
-
-
 def gemm(A, B, Cout, M, N, K, lda, ldb, ldc, *, bias=None, rowvec=None, rows_per_b=0, R=None, ldr=0,
          a_mode=A_ROWK, b_mode=B_ROWK, conv=None, dtype=None, out_f32=False, accumulate=False, splitk=1, alpha=1.0,
          macs=None, colsum_out=None, ldrv=0, epilogue=EPI_NONE, C2=None, ldc2=0, colstat=None, ln=None):
@@ -322,8 +272,7 @@ def gemm(A, B, Cout, M, N, K, lda, ldb, ldc, *, bias=None, rowvec=None, rows_per
     _set_ln(g, ln)
     shape = (M, N, K, int(splitk), int(R is not None or int(accumulate) == 1))     # last: the epilogue also READS an [M, N] tensor
     if RECORD is not None:
-        RECORD.append(Rec("gemm", lambda: _launch_gemm(g, macs, shape), g=g, macs=macs,
-                          keep=(A, B, Cout, bias, rowvec, R, colsum_out, C2, colstat, ln)))
+        RECORD.append(Rec(g, macs, keep=(A, B, Cout, bias, rowvec, R, colsum_out, C2, colstat, ln)))
         return
     _launch_gemm(g, macs, shape)
 
@@ -430,7 +379,7 @@ class Comm:
 _ROLE_STREAMS = {}
 
 
-def role_stream(device, role, high_priority=False):
+def role_stream(device, role):
     """The process-wide dedicated HIP stream of a role ("teacher", "opt", "wt", "comm", "capture", ...) on `device`:
     created once through pdmk_stream_create and wrapped for torch - never one of torch's 32 pooled streams, which are handed
     out round-robin and start to alias after a few stepper / graph instances.  Never destroyed (work may be queued on it)."""
@@ -440,7 +389,7 @@ def role_stream(device, role, high_priority=False):
     if s is None:
         h = vp()
         with torch.cuda.device(key[0]):
-            _chk(_lib.pdmk_stream_create(int(high_priority), C.byref(h)), "pdmk_stream_create")
+            _chk(_lib.pdmk_stream_create(0, C.byref(h)), "pdmk_stream_create")
         s = torch.cuda.ExternalStream(h.value, device=torch.device("cuda", key[0]))
         _ROLE_STREAMS[key] = s
     return s
@@ -549,7 +498,6 @@ def gemm_auto(A, B, Cout, M, N, K, lda, ldb, ldc, *, bias=None, rowvec=None, row
     return colstat is not None
 
 
-@_recordable("splitk_finish")
 def splitk_finish(ws, Cout, M, N, ldc, nslab, *, bias=None, rowvec=None, R=None, ldr=0, rows_per_b=0, ldrv=0,
                   accumulate=False, colstat=None):
     """colstat = (accumulator [B, 4, ld] int64, first column): the GroupNorm statistics of the stored output leave with this pass."""
@@ -617,44 +565,39 @@ def wgrad(dy, x, dW, M, N, K, lda, ldb, *, b_mode=B_COLK, conv=None, colsum_out=
 
 _WG_TARGET = int(os.environ.get("PDMK_WG_TARGET", "512"))     # workgroups a block's grouped weight-gradient launch aims for
 _WG_MINK = int(os.environ.get("PDMK_WG_MINK", "32"))           # and the fewest 64-row K-steps a split may be left with
-_WG_CONV_SLABS = os.environ.get("PDMK_WGRAD_SLABS_CONV", "0") == "1"   # grouped 3x3 conv weight gradients: split partials to slabs (1) or fp32 atomics (0)
 
 
 def wgrad_group(items, queue, target_wgs=None):
-    """The weight gradients of one block (blocks.py:705-867 backward: to_q/k/v, to_out, ff.net.0.proj, ff.net.2, proj_in, proj_out
-    of a transformer block; blocks.py:308-381 backward: conv1 / conv2 of a ResBlock; reached from accelerator.backward,
-    trainer.py:2782) as grouped launches (pdmk_gemm_group): every item reduces over the SAME K pixel rows into a small [M, N]
-    output, so one problem alone fills the 256 CUs only by cutting its reduction into 16-32 splits (16 K-steps each behind a cold
-    prologue, 16-32 slabs to add); together the problems have the tiles, so they share ONE split factor chosen for the group
-    (>= _WG_MINK K-steps per split) and one launch.
-    items: (dy, x, dW, M, N, K, lda, ldb, colsum_out, macs[, b_mode, conv]) with dW fp32 [M, N] contiguous; Linear items
-    (b_mode B_COLK) store the slabs of a split reduction for `queue` (a SlabQueue) to add later, 3x3 conv items (B_COLK_CONV) add
-    their splits with atomics as k.wgrad does.  Problems the grouped kernels do not take go out one by one (same results)."""
-    items = [tuple(it) + (B_COLK, None) if len(it) == 10 else tuple(it) for it in items]
+    """The Linear weight gradients of one transformer block (blocks.py:705-867 backward: to_q/k/v, to_out, ff.net.0.proj, ff.net.2,
+    proj_in, proj_out; reached from accelerator.backward, trainer.py:2782) as grouped launches (pdmk_gemm_group): every item
+    reduces over the SAME K pixel rows into a small [M, N] output, so one problem alone fills the 256 CUs only by cutting its
+    reduction into 16-32 splits (16 K-steps each behind a cold prologue, 16-32 slabs to add); together the problems have the
+    tiles, so they share ONE split factor chosen for the group (>= _WG_MINK K-steps per split) and one launch.
+    items: (dy, x, dW, M, N, K, lda, ldb, colsum_out, macs) with dW fp32 [M, N] contiguous; the splits of a reduction store their
+    slabs for `queue` (a SlabQueue) to add later.  Problems the grouped kernels do not take go out one by one (same results)."""
+    items = list(items)
     while items:
-        K, bm = items[0][5], items[0][10]
-        same = [it for it in items if it[5] == K and it[10] == bm][:GROUP_MAX]
+        K = items[0][5]
+        same = [it for it in items if it[5] == K][:GROUP_MAX]
         items = [it for it in items if not any(it is s_ for s_ in same)]
-        conv_g = bm == B_COLK_CONV
         tiles = sum(((it[3] + 127) // 128) * ((it[4] + 127) // 128) for it in same)
         nk = max(1, K // 64)
         sk = max(1, min((target_wgs or _WG_TARGET) // max(tiles, 1), nk // _WG_MINK, 64))
-        if len(same) == 1 or (queue is None and not conv_g):
-            for dy, x, dW, M, N, K_, lda, ldb, cs, macs, bm_, conv in same:
-                wgrad(dy, x, dW, M, N, K_, lda, ldb, b_mode=bm_, conv=conv, colsum_out=cs, macs=macs, queue=None if conv_g else queue)
+        if len(same) == 1 or queue is None:
+            for dy, x, dW, M, N, K_, lda, ldb, cs, macs in same:
+                wgrad(dy, x, dW, M, N, K_, lda, ldb, colsum_out=cs, macs=macs, queue=queue)
             continue
         with Recorder() as r:
             slabs = []
-            for dy, x, dW, M, N, K_, lda, ldb, cs, macs, bm_, conv in same:
-                if (not conv_g or _WG_CONV_SLABS) and queue is not None and sk > 1 and (M * N) % 4 == 0 and dW.is_contiguous():
+            for dy, x, dW, M, N, K_, lda, ldb, cs, macs in same:
+                if sk > 1 and (M * N) % 4 == 0 and dW.is_contiguous():
                     ws = torch.empty(sk * M * N, device=dy.device, dtype=torch.float32)
-                    gemm(dy, x, ws, M, N, K_, lda, ldb, N, a_mode=A_COLK, b_mode=bm_, conv=conv, out_f32=True, splitk=sk, accumulate=2,
+                    gemm(dy, x, ws, M, N, K_, lda, ldb, N, a_mode=A_COLK, b_mode=B_COLK, out_f32=True, splitk=sk, accumulate=2,
                          dtype=dt(x), macs=macs, colsum_out=cs)
                     slabs.append((ws, dW, M * N, sk))
-                else:       # unsplit: added into the gradient in the epilogue; conv splits: fp32 atomics into it
-                    ska = sk if conv_g else 1
-                    gemm(dy, x, dW, M, N, K_, lda, ldb, N, a_mode=A_COLK, b_mode=bm_, conv=conv, out_f32=True, splitk=ska,
-                         accumulate=(ska == 1), dtype=dt(x), macs=macs, colsum_out=cs)
+                else:       # unsplit: added into the gradient in the epilogue
+                    gemm(dy, x, dW, M, N, K_, lda, ldb, N, a_mode=A_COLK, b_mode=B_COLK, out_f32=True, splitk=1,
+                         accumulate=True, dtype=dt(x), macs=macs, colsum_out=cs)
         gemm_group(r.recs)
         for ws, dW, n, nslab in slabs:
             if queue.full():
@@ -662,7 +605,6 @@ def wgrad_group(items, queue, target_wgs=None):
             queue.add(ws, dW, n, nslab)
 
 
-@_recordable("groupnorm_apply_colstat")
 def groupnorm_apply_colstat(x, y, gamma, beta, stats, colstat, col0, B, HW, Cc, ldx, ldy, G, gs, eps, silu):
     """GroupNorm(+SiLU) forward with the statistics taken from a producing GEMM's epilogue sums (colstat [B, 4, cs_ld] int64 limbs)."""
     _chk(_lib.pdmk_groupnorm_apply_colstat(_p(x), _p(y), _p(gamma), _p(beta), _p(stats), _p(colstat), colstat.shape[2], int(col0),
@@ -670,7 +612,6 @@ def groupnorm_apply_colstat(x, y, gamma, beta, stats, colstat, col0, B, HW, Cc, 
          "pdmk_groupnorm_apply_colstat")
 
 
-@_recordable("groupnorm_fwd")
 def groupnorm_fwd(x, y, gamma, beta, stats, ws, B, HW, Cc, ldx, ldy, G, gs, eps, silu):
     _chk(_lib.pdmk_groupnorm_fwd(_p(x), _p(y), _p(gamma), _p(beta), _p(stats), _p(ws), B, HW, Cc, ldx, ldy, G, gs,
                                  eps, int(silu), dt(x), _st()), "pdmk_groupnorm_fwd")
@@ -739,7 +680,6 @@ def groupnorm_bwd(x, dy, dx, gamma, beta, stats, dgamma, dbeta, ws, B, HW, Cc, l
                                  0 if add is None else add.stride(0), dt(x), _st()), "pdmk_groupnorm_bwd")
 
 
-@_recordable("layernorm_fwd")
 def layernorm_fwd(x, y, gamma, beta, stats, M, Cc, ldx, ldy, eps):
     _chk(_lib.pdmk_layernorm_fwd(_p(x), _p(y), _p(gamma), _p(beta), _p(stats), M, Cc, ldx, ldy, eps, dt(x), _st()),
          "pdmk_layernorm_fwd")
@@ -758,7 +698,6 @@ def layernorm_bwd(x, dy, dx, gamma, stats, dgamma, dbeta, M, Cc, ldx, lddy, lddx
                                  dt(x), _st()), "pdmk_layernorm_bwd")
 
 
-@_recordable("attn_fwd")
 def attn_fwd(q, k, v, o, lse, B, H, Nq, Nk, qs, ks, vs, os_, scale):
     """qs/ks/vs/os_ = (batch_stride, row_stride) in elements."""
     _chk(_lib.pdmk_attn_fwd(_p(q), _p(k), _p(v), _p(o), _p(lse), B, H, Nq, Nk, qs[0], qs[1], ks[0], ks[1], vs[0],
@@ -777,7 +716,6 @@ def attn_bwd(q, k, v, o, do, lse, delta, dq, dk, dv, B, H, Nq, Nk, qs, ks, vs, o
          "pdmk_attn_bwd")
 
 
-@_recordable("geglu_fwd")
 def geglu_fwd(x, y, M, Fd, ldx, ldy, layout=0):
     """layout 0: x = [h | g] halves; 1: (h, g) interleaved in blocks of 8 columns (what EPI_GEGLU consumes)."""
     _chk(_lib.pdmk_geglu_fwd(_p(x), _p(y), M, Fd, ldx, ldy, int(layout), dt(x), _st()), "pdmk_geglu_fwd")
@@ -810,9 +748,7 @@ def _launch_gemm_geglu(g, macs):
 def gemm_geglu(A, B, gl, f, M, N, K, lda, ldb, *, bias=None, macs=None, ln=None):
     """gl[M, N/2] = GEGLU(A @ B^T + bias) in the GEMM's epilogue, (hidden, gate) columns interleaved in blocks of 8; f (or
     None) receives the [M, N] pre-activation for the backward.  Returns False when the library has no fused kernel for
-    the shape (status -2) - the caller then runs the projection and pdmk_geglu_fwd(layout=1) as two passes.
-    While recording (lockstep forward) the answer must be known before the launch: shapes a previous eager call was refused
-    for answer False at once, every other shape is recorded as fused (and raises at launch time if the library refuses)."""
+    the shape (status -2) - the caller then runs the projection and pdmk_geglu_fwd(layout=1) as two passes."""
     if (M, N, K) in _GEGLU_REFUSED:
         return False
     g = GemmArgs()
@@ -823,12 +759,8 @@ def gemm_geglu(A, B, gl, f, M, N, K, lda, ldb, *, bias=None, macs=None, ln=None)
     g.splitk, g.alpha = 1, 1.0
     g.epilogue, g.C2, g.ldc2 = EPI_GEGLU, _p(f), 0 if f is None else f.stride(0)
     _set_ln(g, ln)
-    if RECORD is not None:
-        def run():
-            if not _launch_gemm_geglu(g, macs):
-                raise PdmkError(f"fused GEGLU refused for {(M, N, K)} during a recorded (lockstep) forward; run one eager "
-                                f"forward first so that the shape is known")
-        RECORD.append(Rec("gemm", run, g=g, macs=macs, keep=(A, B, gl, f, bias)))
+    if RECORD is not None:      # a member of a grouped launch: the library answers for the whole group (pdmk_gemm_group)
+        RECORD.append(Rec(g, macs, keep=(A, B, gl, f, bias, ln)))
         return True
     return _launch_gemm_geglu(g, macs)
 
@@ -859,14 +791,12 @@ def gemm_geglu_bwd(dy, wt, pre, dpre, M, N, K, lddy, ldwt, *, macs=None):
     return True
 
 
-@_recordable("quantize_e4m3")
 def quantize_e4m3_(x):
     """In place: every element of the contiguous tensor x rounded to the nearest e4m3fn value (pdmk_quantize_e4m3)."""
     assert x.is_contiguous()
     _chk(_lib.pdmk_quantize_e4m3(_p(x), _p(x), x.numel(), dt(x), _st()), "pdmk_quantize_e4m3")
 
 
-@_recordable("silu_fwd")
 def silu_fwd(x, y):
     _chk(_lib.pdmk_silu_fwd(_p(x), _p(y), x.numel(), dt(x), _st()), "pdmk_silu_fwd")
 
@@ -875,12 +805,10 @@ def silu_bwd(x, dy, dx):
     _chk(_lib.pdmk_silu_bwd(_p(x), _p(dy), _p(dx), x.numel(), dt(x), _st()), "pdmk_silu_bwd")
 
 
-@_recordable("copy2d")
 def copy2d(src, dst, rows, cols, lds, ldd, accumulate=False):
     _chk(_lib.pdmk_copy2d(_p(src), _p(dst), rows, cols, lds, ldd, int(accumulate), dt(src), _st()), "pdmk_copy2d")
 
 
-@_recordable("cast_permute")
 def cast_permute(src, dst, n0, n1, n2, mode):
     _chk(_lib.pdmk_cast_permute(_p(src), _p(dst), n0, n1, n2, mode, dt(dst), _st()), "pdmk_cast_permute")
 
@@ -889,7 +817,6 @@ def colsum(x, out, rows, N, ld, accumulate=False, nbatch=1, ldo=0):
     _chk(_lib.pdmk_colsum(_p(x), _p(out), rows, N, ld, int(accumulate), nbatch, ldo, dt(x), _st()), "pdmk_colsum")
 
 
-@_recordable("skinny_gemm")
 def skinny_gemm(x, w, y, M, N, K, ldx, ldw, ldy, bias=None, accumulate=False):
     """y[M<=16, N] (+)= x @ w[N, K]^T + bias  (w in the compute dtype; x bf16/fp32; y fp32 or the compute dtype)."""
     _chk(_lib.pdmk_skinny_gemm(_p(x), dt(x), _p(w), _p(y), _p(bias), M, N, K, ldx, ldw, ldy, dt(w),
@@ -905,18 +832,15 @@ def pool2x2_sum(src, dst, B, H, W, Cc):
     _chk(_lib.pdmk_pool2x2_sum(_p(src), _p(dst), B, H, W, Cc, dt(src), _st()), "pdmk_pool2x2_sum")
 
 
-@_recordable("timestep_embed")
 def timestep_embed(t, freqs, out, B, dim):
     _chk(_lib.pdmk_timestep_embed(_p(t), _p(freqs), _p(out), B, dim, dt(out), _st()), "pdmk_timestep_embed")
 
 
-@_recordable("add_noise_velocity")
 def add_noise_velocity(x0, noise, t, sa, sb, noisy, target, B, Cc, HW, cpad):
     _chk(_lib.pdmk_add_noise_velocity(_p(x0), _p(noise), _p(t), _p(sa), _p(sb), _p(noisy), _p(target), B, Cc, HW, cpad,
                                       dt(noisy), _st()), "pdmk_add_noise_velocity")
 
 
-@_recordable("nchw_to_nhwc")
 def nchw_to_nhwc(src, dst, B, Cc, HW, cpad):
     _chk(_lib.pdmk_nchw_to_nhwc(_p(src), _p(dst), B, Cc, HW, cpad, dt(dst), _st()), "pdmk_nchw_to_nhwc")
 

@@ -73,12 +73,6 @@ class UNetEngine:
         # skip k (push order) is concatenated behind an h of cat_ch[k] channels (None: its consumer ResBlock is dropped)
         ups = [r for b in blocks if b.kind == "up" for r in b.resnets]
         self.cat_ch = [None if r.dropped else padc(r.cin - r.skip) for r in reversed(ups)]
-        # weight-gradient GEMMs only feed the optimiser, so they could run on a side stream next to the dgrad chain: eager mode
-        # only, opt-in (PDMK_WGRAD_ASYNC=1), measured slower since the ring kernels own the LDS (round 4, eager: 181.9 images/s in
-        # line and grouped, 177.1 in line one by one, 173.9 on the side stream); never under stream capture - captured graphs are
-        # single-stream (bilevel.py GraphedBilevel)
-        self.wgrad_async = os.environ.get("PDMK_WGRAD_ASYNC", "0") == "1"
-        self.wgrad_stream = None          # the dedicated "wgrad" role stream, created on first use
         self.fuse_geglu = os.environ.get("PDMK_FUSE_GEGLU", "1") != "0"     # A/B switch: 0 = projection + GEGLU as two passes
         # LayerNorm in the prologue of the Linear that reads it (linear(ln=...)): 0 = never, 1 = where it measured as a gain (K <= 320,
         # the 128-row register image: +2 ... +13 us per pair at M = 32 768; the 64-row image of K <= 640 loses 0 ... 20 us to the
@@ -88,15 +82,12 @@ class UNetEngine:
         self.attn_fp8 = False
         self.fuse_geglu_bwd = os.environ.get("PDMK_FUSE_GEGLU_BWD", "1") != "0"   # same for the backward (ff.net.2's input gradient)
         self.defer_fanin = os.environ.get("PDMK_DEFER_FANIN", "1") != "0"   # A/B switch: 0 = residual gradients added at once
-        self._keep = []                # operands of in-flight side-stream kernels (freed only after a join)
         # GroupNorm / LayerNorm affine gradients: the second-stage reductions of a whole block run as one launch at the
         # block boundary (PDMK_DEFER_PARTIALS=0: one launch per layer, as before)
         self.partials = k.PartialQueue() if os.environ.get("PDMK_DEFER_PARTIALS", "1") != "0" else None
         # Linear weight gradients: splits store partial slabs, one grouped launch adds them (PDMK_WGRAD_SLABS=0: atomics)
         self.slabs = k.SlabQueue() if os.environ.get("PDMK_WGRAD_SLABS", "1") != "0" else None
-        # ... the 3x3 conv weight gradients too (PDMK_WGRAD_SLABS_CONV=1): measured, no gain (43.3 vs 43.6 ms per main step:
-        # their slabs are sk x 4-60 MB each), so they keep the atomics
-        self.conv_slabs = os.environ.get("PDMK_WGRAD_SLABS_CONV", "0") == "1"
+        # (the 3x3 conv weight gradients keep the atomics: their slabs are sk x 4-60 MB each, measured 43.3 vs 43.6 ms per main step)
         # upsampler convs as four 2x2 phase convs on the low-resolution image (PDMK_CONV_UP2=0: nearest x2 fused into the
         # 3x3 gather, 2.25 x the multiply-accumulates)
         self.up2 = os.environ.get("PDMK_CONV_UP2", "1") != "0"
@@ -106,11 +97,7 @@ class UNetEngine:
         # Linear weight gradients of a transformer block: collected during the block's backward and issued as grouped launches at
         # its start marker (k.wgrad_group; PDMK_WGRAD_GROUP=0: one launch per weight, as they are produced)
         self.group_wgrad = os.environ.get("PDMK_WGRAD_GROUP", "1") != "0" and dtype == torch.bfloat16 and self.slabs is not None
-        # ... and conv1 / conv2 of a ResBlock the same way: built, measured -0.3 ... +0.2 % for the step in three A/Bs (the grouped conv
-        # launches are no faster than the two they replace - 4.13 vs 3.94 ms for the class - and GroupNorm's backward statistics
-        # pass, which used to run behind a weight-gradient kernel, pays the dgrad's write-back itself: 0.63 -> 1.0 ms), so it is
-        # OFF by default (PDMK_WGRAD_GROUP_CONV=1 turns it on)
-        self.group_conv_wgrad = self.group_wgrad and os.environ.get("PDMK_WGRAD_GROUP_CONV", "0") == "1"
+        # (conv1 / conv2 of a ResBlock grouped the same way measured -0.3 ... +0.2 % for the step in three A/Bs and was removed)
         self._wg_items = None
         self._cs_arena, self._cs_off, self._cs_need, self._cs_old = None, 0, 0, []
         self._cs_views, self._cs_cats = {}, {}
@@ -162,31 +149,6 @@ class UNetEngine:
         else:
             k.copy2d(dy, act._g, dy.shape[0], dy.shape[1], _ld(dy), _ld(act._g), accumulate=True)
 
-    def _wgrad(self, fn, *operands):
-        """Launch a weight-gradient kernel.  Side stream: it starts once everything queued on the main stream so far
-        (in particular dy) is done; its operands stay referenced until the next join."""
-        if not self.wgrad_async or torch.cuda.is_current_stream_capturing():
-            fn()
-            return
-        main = torch.cuda.current_stream()
-        if self.wgrad_stream is None:
-            self.wgrad_stream = k.role_stream(self.dev, "wgrad")
-        self.wgrad_stream.wait_stream(main)
-        with torch.cuda.stream(self.wgrad_stream):
-            fn()
-        self._keep.extend(operands)
-
-    def _join_wgrad(self):
-        if self.wgrad_async and self._keep and self.wgrad_stream is not None:
-            torch.cuda.current_stream().wait_stream(self.wgrad_stream)
-            self._keep.clear()
-
-    def _wgrad_fence(self):
-        """The gradient buffer a side-stream wgrad is reading is about to be handed on (aliased) and accumulated into
-        in place by later main-stream kernels: make the main stream wait for the side stream first."""
-        if self.wgrad_async and self.wgrad_stream is not None:
-            torch.cuda.current_stream().wait_stream(self.wgrad_stream)
-
     def flush_pending(self):
         """Deferred norm-affine gradient reductions (PartialQueue): after this every gradient the tape has produced so far is
         final in the arena.  Called by whoever consumes gradients mid-backward (bucketed all-reduce, streamed AdamW, graph
@@ -216,7 +178,6 @@ class UNetEngine:
         hidden * gelu(gate) [M, N/2], computed in the GEMM's epilogue where the library has the fused kernel (bf16 ring
         kernels; the pre-activation is then only written when a backward pass will need it), else as a second pass."""
         P = self.P
-        k.TAG = key                    # lockstep recording: the same layer op of two models carries the same tag
         e = P.by_key[key + ".weight"]
         Np, Kp = e.shape
         M = x.t.shape[0]
@@ -310,17 +271,15 @@ class UNetEngine:
                     k.cast_permute(dy, dyc, M * Np, 1, 1, 0)
                     dy = dyc
                 xt = x.t
-                collect = self._wg_items is not None and not self.wgrad_async
+                collect = self._wg_items is not None
                 if collect:      # inside a transformer block: the weight gradient joins the block's grouped launch (dy and xt
                     # stay referenced - and unmodified, see _give(park=True) - until _wg_flush)
                     self._wg_items.append((dy, xt, P.g(key + ".weight"), Np, Kp, M, _ld(dy), _ld(xt),
                                            P.g(bias) if bias else None, lmacs))
                 else:
-                    # wgrad first (side stream if enabled), dgrad second: the two GEMMs of one layer can run side by side
-                    self._wgrad(lambda: k.wgrad(dy, xt, P.g(key + ".weight"), Np, Kp, M, _ld(dy), _ld(xt), macs=lmacs,
-                                                colsum_out=P.g(bias) if bias else None,   # bias gradient fused in
-                                                queue=None if self.wgrad_async else self.slabs),
-                                dy, xt)
+                    k.wgrad(dy, xt, P.g(key + ".weight"), Np, Kp, M, _ld(dy), _ld(xt), macs=lmacs,
+                            colsum_out=P.g(bias) if bias else None,   # bias gradient fused in
+                            queue=self.slabs)
                 fused_g = False
                 if (x.rg and x.src is not None and x._g is None and self.fuse_geglu_bwd and self.dtype == torch.bfloat16 and
                         k.splitk_plan(dy, P.wtv(key + ".weight"), M, Kp, Np, _ld(dy), Np) == 1):
@@ -334,7 +293,6 @@ class UNetEngine:
                     k.gemm_auto(dy, P.wtv(key + ".weight"), dx, M, Kp, Np, _ld(dy), Np, _ld(dx), accumulate=acc,
                                 macs=lmacs)
                 if residual is not None:
-                    self._wgrad_fence()
                     self._give(residual, out.g, park=collect)
             self.tape.append(bwd)
         if geglu:
@@ -357,7 +315,6 @@ class UNetEngine:
         rowvec (+ rv_cols = (first column, width)): per-image row added to every pixel = this ResBlock's column slice of
         the batched time-embedding projection [B, sum of widths] (fp32)."""
         P = self.P
-        k.TAG = key
         e = P.by_key[key + ".weight"]
         Cop, _, Cip = e.shape
         assert x.t.shape[1] == Cip, f"{key}: input has {x.t.shape[1]} channels, weight expects {Cip}"
@@ -386,16 +343,9 @@ class UNetEngine:
                 dy = out.g
                 ldy = _ld(dy)
                 xt = x.t
-                collect = self._wg_items is not None and self.group_conv_wgrad and not self.wgrad_async and mode == 0
-                if collect:      # conv1 / conv2 of a ResBlock: one grouped launch at the block's start marker
-                    self._wg_items.append((dy, xt, P.g(key + ".weight"), Cop, 9 * Cip, M, ldy, 0, P.g(bias), lmacs, k.B_COLK_CONV,
-                                           (B, Hi, Wi, Cip, Ho, Wo, mode, _ld(xt))))
-                else:
-                    self._wgrad(lambda: k.wgrad(dy, xt, P.g(key + ".weight"), Cop, 9 * Cip, M, ldy, 0, b_mode=k.B_COLK_CONV,
-                                                conv=(B, Hi, Wi, Cip, Ho, Wo, mode, _ld(xt)), macs=lmacs,
-                                                colsum_out=P.g(bias),       # bias gradient fused into the weight gradient
-                                                queue=None if (self.wgrad_async or not self.conv_slabs) else self.slabs),
-                                dy, xt)
+                k.wgrad(dy, xt, P.g(key + ".weight"), Cop, 9 * Cip, M, ldy, 0, b_mode=k.B_COLK_CONV,
+                        conv=(B, Hi, Wi, Cip, Ho, Wo, mode, _ld(xt)), macs=lmacs,
+                        colsum_out=P.g(bias))       # bias gradient fused into the weight gradient; splits add with atomics
                 if x.rg:
                     if mode == 2:
                         tmp = self._empty(M, Cip)
@@ -421,8 +371,7 @@ class UNetEngine:
                     # zero-fill launch per ResBlock)
                     k.colsum(dy, dtp, hw, Cop, ldy, accumulate=True, nbatch=B, ldo=_ld(rowvec.g))
                 if residual is not None:
-                    self._wgrad_fence()
-                    self._give(residual, dy, park=collect)
+                    self._give(residual, dy)
             self.tape.append(bwd)
         return out, Ho, Wo
 
@@ -444,7 +393,7 @@ class UNetEngine:
             for p_ in range(4):
                 k.gemm(x.t, wp[p_], y, Ml, Cop, 4 * Cip, 0, 4 * Cip, _ld(y), a_mode=k.A_CONV, conv=geo(5 + p_, Cip, _ld(x.t)),
                        bias=P.p(bias), macs=lmacs // 4, colstat=acc, rows_per_b=Hi * Wi if acc is not None else 0)
-        self._issue(r.recs)
+        k.gemm_group(r.recs)
         if self.count_macs:
             self.macs += 4 * Ml * e.logical[0] * e.logical[1] * 9  # model MACs are counted as the reference executes them
         out = Act(y)
@@ -470,7 +419,7 @@ class UNetEngine:
                             k.gemm(dy, xt, dwp[p_], Cop, 4 * Cip, Ml, ldy, 0, 4 * Cip, a_mode=k.A_COLK, b_mode=k.B_COLK_CONV,
                                    conv=geo(5 + p_, Cip, _ld(xt)), out_f32=True, splitk=sk, accumulate=(sk == 1),
                                    dtype=k.dt(xt), colsum_out=P.g(bias), macs=lmacs // 4)
-                    self._issue(rw.recs)
+                    k.gemm_group(rw.recs)
                     k.up2_combine_wgrad(dwp, P.g(key + ".weight"), Cop, Cip)
                 else:
                     k.wgrad(dy, xt, P.g(key + ".weight"), Cop, 9 * Cip, 4 * Ml, ldy, 0, b_mode=k.B_COLK_CONV,
@@ -489,14 +438,6 @@ class UNetEngine:
                     self._give(x, pooled)
             self.tape.append(bwd)
         return out
-
-    def _issue(self, recs):
-        """Independent GEMM records of one shape: one grouped launch (or, while an outer lockstep recording is active, handed
-        on to it one by one)."""
-        if k.RECORD is not None:
-            k.RECORD.extend(recs)
-        else:
-            k.gemm_group(recs)
 
     def _cs_begin(self):
         """Start of a forward pass: one zero fill for every GroupNorm accumulator of the pass."""
@@ -551,7 +492,6 @@ class UNetEngine:
 
     def groupnorm(self, x, key, B, HW, G, gs, eps, silu):
         P = self.P
-        k.TAG = key
         C = x.t.shape[1]
         y = self._empty(B * HW, C)
         stats = torch.empty((B, G, 2), device=self.dev, dtype=torch.float32)
@@ -578,7 +518,6 @@ class UNetEngine:
 
     def layernorm(self, x, key):
         P = self.P
-        k.TAG = key
         M, C = x.t.shape
         y = self._empty(M, C)
         stats = torch.empty((M, 2), device=self.dev, dtype=torch.float32)
@@ -593,10 +532,9 @@ class UNetEngine:
             self.tape.append(bwd)
         return out
 
-    def attention(self, q, kk, v, B, H, Nq, Nk, q_act, kv_act, q_cols, kv_cols, tag="attn"):
+    def attention(self, q, kk, v, B, H, Nq, Nk, q_act, kv_act, q_cols, kv_cols):
         """q/kk/v: 2-D views [B*N, H*64] (column slices of the projection outputs); *_act own the gradients;
         q_cols / kv_cols = (lo, hi) column ranges of q in q_act and of (k, v) in kv_act."""
-        k.TAG = tag
         d = H * 64
         o = self._empty(B * Nq, d)
         lse = torch.empty((B, H, Nq), device=self.dev, dtype=torch.float32)
@@ -712,7 +650,6 @@ class UNetEngine:
             off = self.P.by_key[first_key].off
 
             def mark():
-                self._join_wgrad()         # block boundary: side-stream wgrads of this block are done, operands freed
                 if self.grad_ready_cb:     # a consumer that acts on [off, total) calls flush_pending() first
                     self.grad_ready_cb(off)
             self.tape.append(mark)
@@ -722,15 +659,11 @@ class UNetEngine:
         G = self.cfg.norm_num_groups
         p = r.name
         self._mark(p + ".norm1.weight")
-        if self.train and self.group_conv_wgrad:
-            self.tape.append(self._wg_flush)
         n1 = self.groupnorm(x, p + ".norm1", B, H * W, G, r.cin // G, 1e-5, True)
         h1, _, _ = self.conv3(n1, p + ".conv1", B, H, W, 0, p + ".conv1.bias", rowvec=st, rv_cols=self.temb_lay[p][:2], cs=True)
         n2 = self.groupnorm(h1, p + ".norm2", B, H * W, r.groups2(G), r.cout // G, 1e-5, True)
         res = x if r.cin == r.cout else self.linear(x, p + ".conv_shortcut", bias=p + ".conv_shortcut.bias")
         y, _, _ = self.conv3(n2, p + ".conv2", B, H, W, 0, p + ".conv2.bias", residual=res, out=out, cs=cs)
-        if self.train and self.group_conv_wgrad:
-            self.tape.append(self._wg_open)
         return y
 
     def transformer(self, x, a, ehs, B, H, W, T, out=None, cs=True):
@@ -747,14 +680,14 @@ class UNetEngine:
         if self.attn_fp8:            # in place: the backward pass recomputes the scores from the same rounded operands
             k.quantize_e4m3_(qkv.t)
         o = self.attention(qkv.t[:, :d1], qkv.t[:, d1:2 * d1], qkv.t[:, 2 * d1:3 * d1], B, a.h1(), N, N, qkv, qkv,
-                           (0, d1), ((d1, 2 * d1), (2 * d1, 3 * d1)), tag=t + ".attn1")
+                           (0, d1), ((d1, 2 * d1), (2 * d1, 3 * d1)))
         h = self.linear(o, t + ".attn1.to_out.0", bias=t + ".attn1.to_out.0.bias", residual=h)
         q = self.linear(h, t + ".attn2.to_q", ln=t + ".norm2")
         if self.attn_fp8:
             k.quantize_e4m3_(q.t)
         kv, ko = ehs, self.kv_lay[p][0]      # `ehs` = the batched K/V projection of all transformers; this one's columns
         o = self.attention(q.t[:, :d2], kv.t[:, ko:ko + d2], kv.t[:, ko + d2:ko + 2 * d2], B, a.h2(), N, T, q, kv, (0, d2),
-                           ((ko, ko + d2), (ko + d2, ko + 2 * d2)), tag=t + ".attn2")
+                           ((ko, ko + d2), (ko + d2, ko + 2 * d2)))
         h = self.linear(o, t + ".attn2.to_out.0", bias=t + ".attn2.to_out.0.bias", residual=h)
         gl = self.linear(h, t + ".ff.net.0.proj", bias=t + ".ff.net.0.proj.bias", geglu=True, ln=t + ".norm3")
         h = self.linear(gl, t + ".ff.net.2", bias=t + ".ff.net.2.bias", residual=h)
@@ -781,7 +714,6 @@ class UNetEngine:
         self._cs_begin()
         T = ehs.shape[0] // B
         c0 = cfg.block_out_channels[0]
-        k.TAG = "time_embedding"
         te = self._empty(B, c0)
         k.timestep_embed(timesteps, self.freqs, te, B, c0)
         e1 = self.linear(Act(te, rg=False), "time_embedding.linear_1", bias="time_embedding.linear_1.bias")
@@ -863,5 +795,4 @@ class UNetEngine:
         tape, self.tape = self.tape, []
         for fn in reversed(tape):
             fn()
-        self._join_wgrad()
         self.flush_pending()

@@ -288,20 +288,16 @@ class BilevelStepper:
         self.accum = 1                 # training.gradient_accumulation_steps: accelerate's backward divides every loss by it (Trainer.train)
         self.segment_cb = None
         self.in_graph = False          # GraphedBilevel: the pieces run under stream capture, on ONE stream
-        # lockstep forward (PDMK_LOCKSTEP=1; OFF by default): the frozen teacher and the student run the same layer sequence
-        # on independent data (trainer.py:2446-2459, 2951-2954); both forwards are recorded and issued side by side on ONE
-        # stream, layer l of both as one grouped launch where the library has a kernel for the pair (pdmk_gemm_group).
-        # Measured on one MI355X at B = 8 (same-box A/B): 45.8 ms per main step against 42.9 ms with the two
-        # streams - the grouped GEMM launches (121 of them) win less than the two-stream overlap of everything else loses.
-        self.lockstep = os.environ.get("PDMK_LOCKSTEP", "0") == "1" and student.dtype == torch.bfloat16
+        # always False: the lockstep forward (teacher and student recorded and issued side by side on one stream) measured 45.8 ms
+        # against 42.9 ms per main step and was removed; the attribute stays because bench.py reports it
+        self.lockstep = False
         self._gscale = 1.0 / world
         # the frozen teacher pass and the student forward are independent until the loss heads: two HIP streams, so that the
         # small-grid layers of one fill the CUs the other leaves idle (PDMK_TEACHER_STREAM=0 runs the teacher in line).
         # Every role has ONE dedicated stream per process (k.role_stream): never a pooled torch stream, which would alias
         # another role after a few stepper instances.
         cuda = self.dev.type == "cuda"
-        t_hi = os.environ.get("PDMK_TEACHER_PRIO", "0") == "1"     # (A/B knob: the role streams are low-priority streams by default)
-        self.teacher_stream = (k.role_stream(self.dev, "teacher_hi" if t_hi else "teacher", high_priority=t_hi)
+        self.teacher_stream = (k.role_stream(self.dev, "teacher")
                                if cuda and os.environ.get("PDMK_TEACHER_STREAM", "1") != "0" else None)
         self.losses = torch.zeros(4, device=self.dev, dtype=torch.float64)   # diff, dist, block, (unused); zeroed by k.zero_
         # transposed (dgrad) weight copies are refreshed at the START of the next training step, beside its forward, instead
@@ -398,12 +394,10 @@ class BilevelStepper:
         """Teacher cond + uncond predictions of the upper step as ONE batch of 2B (trainer.py:2951-2954)."""
         B, C, H, W = latents.shape
         with phase("fwd_teacher"):
-            # (the doubled batch is formed from the INPUTS: nothing here may read the output of a kernel of this pass on the
-            # host side of the stream - under lockstep recording the kernels are issued later)
+            # (the doubled batch is formed from the INPUTS: one forward diffusion of 2B images)
             t2 = torch.cat([timesteps, timesteps], 0)
             noisy2, _ = self._diffuse(torch.cat([latents, latents], 0), torch.cat([noise, noise], 0), t2, False)
-            # (... which is why the two prompt batches are concatenated BEFORE the cast: _ehs2d's cast is a recorded kernel, and a
-            # torch.cat of its two outputs would run at once, on memory the cast has not written yet)
+            # (... and the two prompt batches are concatenated BEFORE the cast: one cast kernel for both)
             ehs2 = self._ehs2d(torch.cat([prompt_embeds.to(self.dev), empty_prompt_embeds.to(self.dev)], 0))
             return self.teacher.forward_nhwc(noisy2, t2, ehs2, 2 * B, H, W, train=False)
 
@@ -462,17 +456,6 @@ class BilevelStepper:
     def need_teacher(self):
         return self.w["block"] > 0 or self.w["dist"] > 0
 
-    def forward_pair(self, teacher_fn, student_fn):
-        """Teacher pass and student forward in lockstep on the CURRENT stream: both are recorded (launch wrappers of
-        pdm._pdmk defer themselves), then issued side by side with pdm._pdmk.run_lockstep.  Returns (teacher_out, ctx)."""
-        with k.Recorder() as rt:
-            tout = teacher_fn()
-        with k.Recorder() as rs:
-            ctx = student_fn()
-        with phase("fwd_pair"):
-            k.run_lockstep(rt.recs, rs.recs)
-        return tout, ctx
-
     # ------------------------------------------------------------------ eager steps
     def _beside(self, fn):
         """Runs fn() on the teacher stream beside what the caller queues next; returns (result, join)."""
@@ -494,14 +477,9 @@ class BilevelStepper:
         if backward:
             self.begin_wt_refresh()
         join = lambda: None
-        sfwd = lambda: self.student_forward(latents, noise, timesteps, prompt_embeds, train=backward, input_noise=input_noise)
-        if teacher_out is None and self.need_teacher and self.lockstep:
-            teacher_out, ctx = self.forward_pair(
-                lambda: self.teacher_pass(latents, noise, timesteps, prompt_embeds, input_noise), sfwd)
-        else:
-            if teacher_out is None and self.need_teacher:
-                teacher_out, join = self._beside(lambda: self.teacher_pass(latents, noise, timesteps, prompt_embeds, input_noise))
-            ctx = sfwd()
+        if teacher_out is None and self.need_teacher:
+            teacher_out, join = self._beside(lambda: self.teacher_pass(latents, noise, timesteps, prompt_embeds, input_noise))
+        ctx = self.student_forward(latents, noise, timesteps, prompt_embeds, train=backward, input_noise=input_noise)
         join()
         self.main_loss_heads(ctx, teacher_out, backward)
         if backward:
@@ -514,14 +492,9 @@ class BilevelStepper:
         predictions computed as ONE batch of 2B."""
         if backward:
             self.begin_wt_refresh()
-        tfwd = lambda: self.upper_teacher_pass(latents, noise, timesteps, prompt_embeds, empty_prompt_embeds)
-        sfwd = lambda: self.student_forward(latents, noise, timesteps, prompt_embeds, train=backward, want_target=False)
-        if self.lockstep:
-            tout, ctx = self.forward_pair(tfwd, sfwd)
-        else:
-            tout, join = self._beside(tfwd)
-            ctx = sfwd()
-            join()
+        tout, join = self._beside(lambda: self.upper_teacher_pass(latents, noise, timesteps, prompt_embeds, empty_prompt_embeds))
+        ctx = self.student_forward(latents, noise, timesteps, prompt_embeds, train=backward, want_target=False)
+        join()
         self.upper_loss_heads(ctx, tout, backward)
         if backward:
             with phase("bwd"):
@@ -590,8 +563,7 @@ class GraphedBilevel:
         # AdamW of every finished share of the arena runs beside the rest of the backward (valid without gradient-norm
         # clipping, which needs all gradients first; the shipped configs do not clip: trainer.py:2784-2786)
         self.stream_opt = stream_opt and os.environ.get("PDMK_STREAM_OPT", "1") != "0"     # (0: A/B switch - AdamW after the backward)
-        opt_hi = os.environ.get("PDMK_OPT_PRIO", "0") == "1"      # (A/B knob: the streamed AdamW on a high-priority stream)
-        self.opt_stream = k.role_stream(dev, "opt_hi" if opt_hi else "opt", high_priority=opt_hi)
+        self.opt_stream = k.role_stream(dev, "opt")
         self.cap_stream = k.role_stream(dev, "capture")
         self.closed = False
         # Cross-step teacher prefetch (PDMK_TEACHER_PREFETCH=1, or prefetch=True): the frozen teacher's pass of the NEXT step in
@@ -602,7 +574,7 @@ class GraphedBilevel:
         # names the batch again (`batch_id`), else the teacher runs in line as before.  Measured (same box, B = 8):
         # 185.6 -> 190.3 images/s with the main pass alone; queued behind later backward graphs it is worth less and less.
         self.prefetch = ((prefetch if prefetch is not None else os.environ.get("PDMK_TEACHER_PREFETCH", "0") == "1")
-                         and stepper.teacher_stream is not None and not stepper.lockstep and stepper.need_teacher)
+                         and stepper.teacher_stream is not None and stepper.need_teacher)
         self.t_in = ([torch.zeros_like(b) for b in (self.lat, self.noise, self.t, self.ehs)] if self.prefetch else None)
         self.u_in = ([torch.zeros_like(b) for b in (self.lat, self.noise, self.t, self.ehs, self.empty)] if self.prefetch else None)
         self._ahead = {"main": None, "upper": None}      # id of the batch whose teacher outputs are queued / done on the teacher stream
@@ -722,18 +694,14 @@ class GraphedBilevel:
                 tin = ((self.u_in if upper else self.t_in) if self.prefetch else
                        (self.lat, self.noise, self.t, self.ehs) + ((self.empty,) if upper else ()))
                 tfwd = (lambda: st.upper_teacher_pass(*tin)) if upper else (lambda: st.teacher_pass(*tin))
-                sfwd = lambda: st.student_forward(self.lat, self.noise, self.t, self.ehs, train=True, want_target=not upper)
-                if need_t and not st.lockstep:             # teacher as its own graph, replayed on the teacher stream
+                if need_t:                                 # teacher as its own graph, replayed on the teacher stream
                     cs.teacher = torch.cuda.CUDAGraph()
                     cs.teacher.capture_begin(capture_error_mode="thread_local")
                     tout = tfwd()
                     cs.teacher.capture_end()
                 cs.fwd = torch.cuda.CUDAGraph()
                 cs.fwd.capture_begin(capture_error_mode="thread_local")
-                if need_t and st.lockstep:                 # teacher || student in lockstep inside ONE graph
-                    tout, ctx = st.forward_pair(tfwd, sfwd)
-                else:
-                    ctx = sfwd()
+                ctx = st.student_forward(self.lat, self.noise, self.t, self.ehs, train=True, want_target=not upper)
                 cs.fwd.capture_end()
                 heads = st.upper_loss_heads if upper else st.main_loss_heads
                 if self.prefetch and cs.teacher is not None:          # the loss heads as a graph of their own (class docstring)
