@@ -9,7 +9,6 @@ CLIPTextModel up to its last layer, then the row at the first argmax of the ids 
 text_projection.  Features come out in fp32.  Any ViT CLIP whose heads are 64 wide (B/32, B/16, L/14); inference only.
 Each (tower, batch shape) is captured once as a single-stream hipGraph and replayed (PDMK_CLIP_GRAPH=0: eager).
 """
-import gc
 import math
 import os
 from dataclasses import dataclass
@@ -17,11 +16,11 @@ from dataclasses import dataclass
 import torch
 
 from ... import _pdmk as k
-from ..unet.engine import Act, _ld
-from ..unet.params import ParamStore, _lin, _vec
-from ..vae.autoencoder_kl import _Ops
+from ...utils.replay import ReplayCache
+from ..ops import Act, Ops
+from ..unet.params import ParamStore, _lin, _vec, assign_offsets, norm_pair
 from . import convert
-from .text_encoder import CLIPTextConfig, CLIPTextModel
+from .text_encoder import CLIPTextConfig, CLIPTextModel, encoder_layer, encoder_layer_entries
 
 
 @dataclass(frozen=True)
@@ -41,51 +40,17 @@ class CLIPVisionConfig:
 
 
 def build_vision_entries(cfg: CLIPVisionConfig, projection_dim=0):
-    E, F, p = cfg.hidden_size, cfg.intermediate_size, cfg.patch_size
+    E, p = cfg.hidden_size, cfg.patch_size
     out = [_vec("embeddings.class_embedding", [("embeddings.class_embedding", E)]),
            _lin("embeddings.patch_embedding", [("embeddings.patch_embedding.weight", E)], 3 * p * p),
            _lin("embeddings.position_embedding", [("embeddings.position_embedding.weight", cfg.num_positions)], E)]
-
-    def norm(key):
-        out.extend([_vec(key + ".weight", [(key + ".weight", E)]), _vec(key + ".bias", [(key + ".bias", E)])])
-
-    def lin(key, srcs, kin):
-        out.extend([_lin(key, [(n + ".weight", r) for n, r in srcs], kin), _vec(key + ".bias", [(n + ".bias", r) for n, r in srcs])])
-
-    norm("pre_layrnorm")
+    out += norm_pair("pre_layrnorm", E)
     for i in range(cfg.num_hidden_layers):
-        q = f"encoder.layers.{i}"
-        norm(q + ".layer_norm1")
-        lin(q + ".self_attn.qkv_proj", [(f"{q}.self_attn.{n}_proj", E) for n in ("q", "k", "v")], E)
-        lin(q + ".self_attn.out_proj", [(q + ".self_attn.out_proj", E)], E)
-        norm(q + ".layer_norm2")
-        lin(q + ".mlp.fc1", [(q + ".mlp.fc1", F)], E)
-        lin(q + ".mlp.fc2", [(q + ".mlp.fc2", E)], F)
-    norm("post_layernorm")
+        out += encoder_layer_entries(f"encoder.layers.{i}", E, cfg.intermediate_size)
+    out += norm_pair("post_layernorm", E)
     if projection_dim:
         out.append(_lin("visual_projection", [("visual_projection.weight", projection_dim)], E))
-    off = 0
-    for e in out:
-        e.off = off
-        off += (e.numel + 127) // 128 * 128
-    return out
-
-
-def _encoder_layer(o, x, q, B, H, N, E, dtype, dev, act, causal=False):
-    """One pre-LN transformer layer of CLIP's text / vision encoders on the 2-D activation x [B*N, E]."""
-    h = o.layernorm(x, q + ".layer_norm1")
-    qkv = o.linear(h, q + ".self_attn.qkv_proj", bias=q + ".self_attn.qkv_proj.bias").t
-    att = torch.empty((B * N, E), device=dev, dtype=dtype)
-    lse = torch.empty((B, H, N), device=dev, dtype=torch.float32)
-    st = (N * _ld(qkv), _ld(qkv))
-    fn = k.attn_fwd_causal if causal else (lambda *a: k.attn_fwd(*a[:8], N, *a[8:]))
-    fn(qkv[:, :E], qkv[:, E:2 * E], qkv[:, 2 * E:3 * E], att, lse, B, H, N, st, st, st, (N * E, E), 64 ** -0.5)
-    x = o.linear(Act(att), q + ".self_attn.out_proj", bias=q + ".self_attn.out_proj.bias", residual=x)
-    h = o.layernorm(x, q + ".layer_norm2")
-    f = o.linear(h, q + ".mlp.fc1", bias=q + ".mlp.fc1.bias").t
-    a = torch.empty_like(f)
-    (k.quick_gelu_fwd if act == "quick_gelu" else k.gelu_fwd)(f, a)
-    return o.linear(Act(a), q + ".mlp.fc2", bias=q + ".mlp.fc2.bias", residual=x)
+    return assign_offsets(out)
 
 
 class CLIPVisionModel:
@@ -103,7 +68,7 @@ class CLIPVisionModel:
             raise NotImplementedError(f"hidden_act {c.hidden_act!r}")
         self.device, self.dtype, self.projection_dim = torch.device(device or "cuda:0"), dtype, projection_dim
         self.store = ParamStore(build_vision_entries(c, projection_dim), self.device, dtype, train=False)
-        self.ops = _Ops(self.store, dtype)
+        self.ops = Ops(self.store, dtype)
         if init:
             self.store.init_random(seed)
 
@@ -128,8 +93,9 @@ class CLIPVisionModel:
         x = torch.empty((B * N, E), device=dev, dtype=self.dtype)
         k.vit_tokens(pe, P.wv("embeddings.class_embedding"), P.wv("embeddings.position_embedding.weight"), E, x, B, G2, E)
         x = o.layernorm(Act(x, rg=False), "pre_layrnorm")
+        lse = torch.empty((B, H, N), device=dev, dtype=torch.float32)
         for i in range(cfg.num_hidden_layers):
-            x = _encoder_layer(o, x, f"encoder.layers.{i}", B, H, N, E, self.dtype, dev, cfg.hidden_act)
+            x = encoder_layer(o, x, f"encoder.layers.{i}", B, H, N, cfg.hidden_act, lse, causal=False)
         cls = torch.empty((B, E), device=dev, dtype=self.dtype)
         k.gather_rows(x.t, None, N, cls, B, E)
         return o.layernorm(Act(cls, rg=False), "post_layernorm")
@@ -153,7 +119,7 @@ class CLIPModel:
                                       projection_dim=self.projection_dim)
         self.logit_scale = torch.tensor(math.log(1 / 0.07), dtype=torch.float32)
         self.use_graph = os.environ.get("PDMK_CLIP_GRAPH", "1") != "0"
-        self._graphs = {}
+        self._graphs = ReplayCache(self.device)
 
     @property
     def image_size(self):
@@ -209,25 +175,7 @@ class CLIPModel:
     def _run(self, kind, fn, inp):
         if not self.use_graph or torch.cuda.is_current_stream_capturing():
             return fn(inp).clone()
-        key = (kind, tuple(inp.shape))
-        ent = self._graphs.get(key)
-        if ent is None:
-            static = inp.to(self.device).contiguous().clone()
-            fn(static)                                    # eager warm-up: GEMM plans are tuned outside the capture
-            torch.cuda.synchronize()
-            graph = torch.cuda.CUDAGraph()
-            gc.collect()
-            gc.disable()                                  # a collection during capture would free graph-pool tensors
-            try:
-                with torch.cuda.graph(graph):
-                    out = fn(static)
-            finally:
-                gc.enable()
-            ent = self._graphs[key] = (graph, static, out)
-        graph, static, out = ent
-        static.copy_(inp)
-        graph.replay()
-        return out.clone()
+        return self._graphs.run((kind, tuple(inp.shape)), fn, inp)
 
     def encode_image(self, pixel_values):
         return self._run("image", self._image, pixel_values.to(self.device, torch.float32))

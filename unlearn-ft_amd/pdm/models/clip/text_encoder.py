@@ -9,7 +9,6 @@ libpdmk: fused token+position gather, LayerNorm, one fused q|k|v projection, cau
 U-Net's kernel with a mask), erf-GELU MLP, residuals in the GEMM epilogues.  Inference only (frozen); no CPU path.
 Tokenisation stays on the host (transformers' CLIPTokenizer needs its vocabulary files): callers pass token ids.
 """
-import gc
 import os
 from dataclasses import dataclass
 from types import SimpleNamespace
@@ -17,10 +16,9 @@ from types import SimpleNamespace
 import torch
 
 from ... import _pdmk as k
-from ..unet.engine import Act, _ld
-from ..unet.params import ParamStore, _lin, _vec
-from ..unet.spec import padc
-from ..vae.autoencoder_kl import _Ops
+from ...utils.replay import ReplayCache
+from ..ops import Act, Ops, _ld
+from ..unet.params import ParamStore, _lin, assign_offsets, lin_pair, load_local_or_random, norm_pair
 
 
 @dataclass(frozen=True)
@@ -39,33 +37,48 @@ class CLIPTextConfig:
         return CLIPTextConfig()
 
 
+def encoder_layer_entries(p, E, F):
+    """One encoder layer of either tower (q|k|v fused row-wise): the parameters `encoder_layer` reads."""
+    return (norm_pair(p + ".layer_norm1", E) +
+            lin_pair(p + ".self_attn.qkv_proj", [(f"{p}.self_attn.{n}_proj", E) for n in ("q", "k", "v")], E) +
+            lin_pair(p + ".self_attn.out_proj", [(p + ".self_attn.out_proj", E)], E) +
+            norm_pair(p + ".layer_norm2", E) +
+            lin_pair(p + ".mlp.fc1", [(p + ".mlp.fc1", F)], E) +
+            lin_pair(p + ".mlp.fc2", [(p + ".mlp.fc2", E)], F))
+
+
 def build_entries(cfg: CLIPTextConfig, projection_dim=0):
-    E, F = cfg.hidden_size, cfg.intermediate_size
+    E = cfg.hidden_size
     out = [_lin("embeddings.token_embedding", [("embeddings.token_embedding.weight", cfg.vocab_size)], E),
            _lin("embeddings.position_embedding", [("embeddings.position_embedding.weight", cfg.max_position_embeddings)], E)]
-
-    def norm(key):
-        out.extend([_vec(key + ".weight", [(key + ".weight", E)]), _vec(key + ".bias", [(key + ".bias", E)])])
-
-    def lin(key, srcs, kin):
-        out.extend([_lin(key, [(n + ".weight", r) for n, r in srcs], kin), _vec(key + ".bias", [(n + ".bias", r) for n, r in srcs])])
-
     for i in range(cfg.num_hidden_layers):
-        p = f"encoder.layers.{i}"
-        norm(p + ".layer_norm1")
-        lin(p + ".self_attn.qkv_proj", [(f"{p}.self_attn.{n}_proj", E) for n in ("q", "k", "v")], E)
-        lin(p + ".self_attn.out_proj", [(p + ".self_attn.out_proj", E)], E)
-        norm(p + ".layer_norm2")
-        lin(p + ".mlp.fc1", [(p + ".mlp.fc1", F)], E)
-        lin(p + ".mlp.fc2", [(p + ".mlp.fc2", E)], F)
-    norm("final_layer_norm")
+        out += encoder_layer_entries(f"encoder.layers.{i}", E, cfg.intermediate_size)
+    out += norm_pair("final_layer_norm", E)
     if projection_dim:                  # CLIPModel's text_projection (no bias)
         out.append(_lin("text_projection", [("text_projection.weight", projection_dim)], E))
-    off = 0
-    for e in out:
-        e.off = off
-        off += (e.numel + 127) // 128 * 128
-    return out
+    return assign_offsets(out)
+
+
+def encoder_layer(o, x, p, B, H, N, act, lse, causal):
+    """One pre-LN transformer layer of CLIP's text (causal) / vision encoders on the 2-D activation x [B*N, E]; o: the Ops over
+    the tower's parameters, p: the layer's key prefix, lse: the [B, H, N] fp32 buffer the attention kernel writes its row
+    statistics to (one per forward pass, handed to every layer: inference never reads it back)."""
+    E = x.t.shape[1]
+    h = o.layernorm(x, p + ".layer_norm1")
+    qkv = o.linear(h, p + ".self_attn.qkv_proj", bias=p + ".self_attn.qkv_proj.bias").t
+    att = torch.empty((B * N, E), device=o.dev, dtype=o.dtype)
+    q, kk, v = qkv[:, :E], qkv[:, E:2 * E], qkv[:, 2 * E:3 * E]
+    st = (N * _ld(qkv), _ld(qkv))
+    if causal:
+        k.attn_fwd_causal(q, kk, v, att, lse, B, H, N, st, st, st, (N * E, E), 64 ** -0.5)
+    else:
+        k.attn_fwd(q, kk, v, att, lse, B, H, N, N, st, st, st, (N * E, E), 64 ** -0.5)
+    x = o.linear(Act(att), p + ".self_attn.out_proj", bias=p + ".self_attn.out_proj.bias", residual=x)
+    h = o.layernorm(x, p + ".layer_norm2")
+    f = o.linear(h, p + ".mlp.fc1", bias=p + ".mlp.fc1.bias").t
+    a = torch.empty_like(f)
+    (k.quick_gelu_fwd if act == "quick_gelu" else k.gelu_fwd)(f, a)
+    return o.linear(Act(a), p + ".mlp.fc2", bias=p + ".mlp.fc2.bias", residual=x)
 
 
 class _Output(tuple):
@@ -88,35 +101,21 @@ class CLIPTextModel:
         self.device = torch.device(device or "cuda:0")
         self.dtype = dtype
         self.store = ParamStore(build_entries(self.cfg, projection_dim), self.device, dtype, train=False)
-        self.ops = _Ops(self.store, dtype)
+        self.ops = Ops(self.store, dtype)
         self.config = SimpleNamespace(**self.cfg.__dict__)
         # ~10 launches per layer on 77-token inputs are launch-bound from Python (3.2 ms eager for 23 layers): each
         # (B, T) shape is captured once as a hipGraph and replayed on a static id buffer
         self.use_graph = os.environ.get("PDMK_CLIP_GRAPH", "1") != "0"
-        self._graphs = {}
+        self._graphs = ReplayCache(self.device)
         if init:
             self.store.init_random(seed)
 
     @classmethod
     def from_pretrained(cls, pretrained_model_name_or_path=None, subfolder=None, revision=None, random_init=False,
                         text_config=None, torch_dtype=torch.bfloat16, device=None, seed=0, **unused):
-        path = pretrained_model_name_or_path
-        if path and subfolder:
-            path = os.path.join(path, subfolder)
-        have_local = bool(path) and os.path.isdir(path)
-        model = cls(text_config, device, torch_dtype, seed=seed, init=random_init or not have_local)
-        if have_local and not random_init:
-            f = os.path.join(path, "model.safetensors")
-            if os.path.exists(f):
-                from safetensors.torch import load_file
-                sd = load_file(f)
-            else:
-                sd = torch.load(os.path.join(path, "pytorch_model.bin"), map_location="cpu")
-            model.load_state_dict(sd)
-        elif not random_init:
-            raise FileNotFoundError(f"{pretrained_model_name_or_path!r} is not a local directory and hub downloads are "
-                                    f"not available here; pass random_init=True or a local checkpoint directory")
-        return model
+        return load_local_or_random(lambda init: cls(text_config, device, torch_dtype, seed=seed, init=init),
+                                    pretrained_model_name_or_path, subfolder, random_init,
+                                    ("model.safetensors", "pytorch_model.bin"))
 
     def load_state_dict(self, sd, strict=True):
         own = {}
@@ -158,46 +157,16 @@ class CLIPTextModel:
         x = Act(x, rg=False)
         lse = torch.empty((B, H, T), device=self.device, dtype=torch.float32)
         for i in range(cfg.num_hidden_layers):
-            p = f"encoder.layers.{i}"
-            h = o.layernorm(x, p + ".layer_norm1")
-            qkv = o.linear(h, p + ".self_attn.qkv_proj", bias=p + ".self_attn.qkv_proj.bias").t
-            att = torch.empty((B * T, E), device=self.device, dtype=self.dtype)
-            q, kk, v = qkv[:, :E], qkv[:, E:2 * E], qkv[:, 2 * E:3 * E]
-            st = (T * _ld(qkv), _ld(qkv))
-            k.attn_fwd_causal(q, kk, v, att, lse, B, H, T, st, st, st, (T * E, E), 64 ** -0.5)
-            x = o.linear(Act(att), p + ".self_attn.out_proj", bias=p + ".self_attn.out_proj.bias", residual=x)
-            h = o.layernorm(x, p + ".layer_norm2")
-            f = o.linear(h, p + ".mlp.fc1", bias=p + ".mlp.fc1.bias").t
-            a = torch.empty_like(f)
-            (k.quick_gelu_fwd if cfg.hidden_act == "quick_gelu" else k.gelu_fwd)(f, a)
-            x = o.linear(Act(a), p + ".mlp.fc2", bias=p + ".mlp.fc2.bias", residual=x)
+            x = encoder_layer(o, x, f"encoder.layers.{i}", B, H, T, cfg.hidden_act, lse, causal=True)
         return o.layernorm(x, "final_layer_norm").t if final_norm else x.t
-
-    def _replay(self, input_ids):
-        key = tuple(input_ids.shape)
-        ent = self._graphs.get(key)
-        if ent is None:
-            static_ids = input_ids.to(self.device, torch.int64).contiguous().clone()
-            self.encode_2d(static_ids)                    # eager warm-up: GEMM plans are tuned outside the capture
-            torch.cuda.synchronize()
-            graph = torch.cuda.CUDAGraph()
-            gc.collect()
-            gc.disable()                                  # a collection during capture would free graph-pool tensors
-            try:
-                with torch.cuda.graph(graph):
-                    out = self.encode_2d(static_ids)
-            finally:
-                gc.enable()
-            ent = self._graphs[key] = (graph, static_ids, out)
-        graph, static_ids, out = ent
-        static_ids.copy_(input_ids)
-        graph.replay()
-        return out.clone()
 
     def __call__(self, input_ids, output_hidden_states=False, **unused):
         B, T = input_ids.shape
         capturing = torch.cuda.is_current_stream_capturing()
-        y = self._replay(input_ids) if self.use_graph and not capturing else self.encode_2d(input_ids)
+        if self.use_graph and not capturing:
+            y = self._graphs.run((B, T), self.encode_2d, input_ids, torch.int64)
+        else:
+            y = self.encode_2d(input_ids)
         return _Output((y.view(B, T, self.cfg.hidden_size),))
 
 

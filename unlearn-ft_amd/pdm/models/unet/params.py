@@ -11,6 +11,7 @@ training step (padded rows/cols receive zero gradients), so the packed model is 
 State-dict import/export uses the diffusers SD U-Net key names with the *pruned* shapes, i.e. the checkpoint format of
 trainer.py:314-346 (safetensors written by save_pretrained / read by load_state_dict).
 """
+import os
 from dataclasses import dataclass
 from typing import List, Tuple
 
@@ -60,6 +61,25 @@ def _lin(key, srcs, k_in, suffix=".weight", rows_p=None):
 def _vec(key, srcs, rows_p=None):
     n = sum(t[1] for t in srcs)
     return Entry(key, "vec", (rows_p or padc(n),), srcs, (n,))
+
+
+def norm_pair(key, c):
+    """Affine weight and bias of a norm over c channels."""
+    return [_vec(key + ".weight", [(key + ".weight", c)]), _vec(key + ".bias", [(key + ".bias", c)])]
+
+
+def lin_pair(key, srcs, k_in):
+    """Weight and bias of a Linear whose rows are the row blocks `srcs` = [(state-dict prefix, rows)] (fused projections)."""
+    return [_lin(key, [(n + ".weight", r) for n, r in srcs], k_in), _vec(key + ".bias", [(n + ".bias", r) for n, r in srcs])]
+
+
+def assign_offsets(entries):
+    """Lays the entries out back to back in list order; every entry starts on a 256-byte (bf16) / 512-byte (fp32) boundary."""
+    off = 0
+    for e in entries:
+        e.off = off
+        off += (e.numel + 127) // 128 * 128
+    return entries
 
 
 def _geglu_rows(name, ff):
@@ -180,11 +200,7 @@ def build_entries(cfg: UNetConfig, blocks) -> List[Entry]:
     E += [_vec("conv_norm_out.weight", [("conv_norm_out.weight", c0)]),
           _vec("conv_norm_out.bias", [("conv_norm_out.bias", c0)]),
           _conv("conv_out", cfg.out_channels, c0), _vec("conv_out.bias", [("conv_out.bias", cfg.out_channels)])]
-    off = 0
-    for e in E:
-        e.off = off
-        off += (e.numel + 127) // 128 * 128          # every entry starts on a 256-byte (bf16) / 512-byte (fp32) boundary
-    return E
+    return assign_offsets(E)
 
 
 def reference_param_order(names):
@@ -225,6 +241,27 @@ def reference_param_order(names):
                 in_tb = True
         return out
     return sorted(names, key=key)
+
+
+def load_local_or_random(make, name_or_path, subfolder, random_init, files, strict=True):
+    """`from_pretrained` of the frozen models: `make(init)` builds the model; its weights come from the local directory
+    `name_or_path[/subfolder]` (files = (safetensors name, torch.save name), the first that exists) or, with random_init,
+    from the seeded initialiser.  There are no hub downloads: anything else raises FileNotFoundError."""
+    path = os.path.join(name_or_path, subfolder) if name_or_path and subfolder else name_or_path
+    have_local = bool(path) and os.path.isdir(path)
+    model = make(random_init or not have_local)
+    if have_local and not random_init:
+        f = os.path.join(path, files[0])
+        if os.path.exists(f):
+            from safetensors.torch import load_file
+            sd = load_file(f)
+        else:
+            sd = torch.load(os.path.join(path, files[1]), map_location="cpu")
+        model.load_state_dict(sd, strict=strict)
+    elif not random_init:
+        raise FileNotFoundError(f"{name_or_path!r} is not a local directory and hub downloads are "
+                                f"not available here; pass random_init=True or a local checkpoint directory")
+    return model
 
 
 class ParamStore:
@@ -298,7 +335,7 @@ class ParamStore:
         tab = np.where(tab >= 2 ** 31, tab - 2 ** 32, tab).astype(np.int32)
         return torch.from_numpy(tab).to(self.master.device), tab.shape[0]
 
-    # ---- upsampler convs as four 2x2 phase convs (engine.conv3 mode 2, pdmk.h conv_mode 5..12): the phase weights are
+    # ---- upsampler convs as four 2x2 phase convs (Ops.conv3 mode 2, pdmk.h conv_mode 5..12): the phase weights are
     # derived copies like w / wt, re-packed from the fp32 master after every optimiser step
     def up2_weights(self, key):
         """(wp [4, Co, 4 Ci], wpt [Ci, 16 Co] (phase-major inside a row) or None) of the 3x3 conv `key`, packed on first use."""

@@ -16,7 +16,8 @@ from types import SimpleNamespace
 import torch
 
 from ... import _pdmk as k
-from .engine import UNetEngine, Act
+from ..ops import Act
+from .engine import UNetEngine
 from .params import ParamStore, build_entries
 from .spec import UNetConfig, apply_arch_vector, gate_structure, padc
 

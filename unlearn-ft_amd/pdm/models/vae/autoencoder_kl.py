@@ -12,7 +12,6 @@ Leaf semantics follow the CompVis encoder the diffusers class was converted from
 against (oracle/pdm_ref/vae.py): ldm/modules/diffusionmodules/model.py:60-81, 82-143, 150-204, 368-460 and
 ldm/modules/distributions/distributions.py:24-37.
 """
-import os
 from dataclasses import dataclass
 from types import SimpleNamespace
 from typing import Tuple
@@ -20,8 +19,8 @@ from typing import Tuple
 import torch
 
 from ... import _pdmk as k
-from ..unet.engine import UNetEngine, Act, _ld
-from ..unet.params import ParamStore, _conv, _lin, _vec
+from ..ops import Act, Ops, _ld
+from ..unet.params import ParamStore, _conv, _vec, assign_offsets, lin_pair, load_local_or_random, norm_pair
 from ..unet.spec import padc
 
 
@@ -46,19 +45,13 @@ def build_entries(cfg: VAEConfig, decoder=True):
     def conv(key, co, ci):
         E.extend([_conv(key, co, ci), _vec(key + ".bias", [(key + ".bias", co)])])
 
-    def norm(key, c):
-        E.extend([_vec(key + ".weight", [(key + ".weight", c)]), _vec(key + ".bias", [(key + ".bias", c)])])
-
-    def lin(key, srcs, kin):
-        E.extend([_lin(key, [(n + ".weight", r) for n, r in srcs], kin), _vec(key + ".bias", [(n + ".bias", r) for n, r in srcs])])
-
     def res(p, ci, co):
-        norm(p + ".norm1", ci)
+        E.extend(norm_pair(p + ".norm1", ci))
         conv(p + ".conv1", co, ci)
-        norm(p + ".norm2", co)
+        E.extend(norm_pair(p + ".norm2", co))
         conv(p + ".conv2", co, co)
         if ci != co:
-            lin(p + ".conv_shortcut", [(p + ".conv_shortcut", co)], ci)
+            E.extend(lin_pair(p + ".conv_shortcut", [(p + ".conv_shortcut", co)], ci))
 
     ch = cfg.block_out_channels
     conv("encoder.conv_in", ch[0], cfg.in_channels)
@@ -71,24 +64,24 @@ def build_entries(cfg: VAEConfig, decoder=True):
             conv(f"encoder.down_blocks.{i}.downsamplers.0.conv", co, co)
     res("encoder.mid_block.resnets.0", cin, cin)
     a = "encoder.mid_block.attentions.0"
-    norm(a + ".group_norm", cin)
-    lin(a + ".to_qk", [(a + ".to_q", cin), (a + ".to_k", cin)], cin)
-    lin(a + ".to_v", [(a + ".to_v", cin)], cin)
-    lin(a + ".to_out.0", [(a + ".to_out.0", cin)], cin)
+    E.extend(norm_pair(a + ".group_norm", cin))
+    E.extend(lin_pair(a + ".to_qk", [(a + ".to_q", cin), (a + ".to_k", cin)], cin))
+    E.extend(lin_pair(a + ".to_v", [(a + ".to_v", cin)], cin))
+    E.extend(lin_pair(a + ".to_out.0", [(a + ".to_out.0", cin)], cin))
     res("encoder.mid_block.resnets.1", cin, cin)
-    norm("encoder.conv_norm_out", cin)
+    E.extend(norm_pair("encoder.conv_norm_out", cin))
     conv("encoder.conv_out", 2 * cfg.latent_channels, cin)
-    lin("quant_conv", [("quant_conv", 2 * cfg.latent_channels)], 2 * cfg.latent_channels)
+    E.extend(lin_pair("quant_conv", [("quant_conv", 2 * cfg.latent_channels)], 2 * cfg.latent_channels))
     if decoder:        # diffusers Decoder: mid block first, then up_blocks over reversed(block_out_channels), 3 ResBlocks each
-        lin("post_quant_conv", [("post_quant_conv", cfg.latent_channels)], cfg.latent_channels)
+        E.extend(lin_pair("post_quant_conv", [("post_quant_conv", cfg.latent_channels)], cfg.latent_channels))
         rev = tuple(reversed(ch))
         conv("decoder.conv_in", rev[0], cfg.latent_channels)
         res("decoder.mid_block.resnets.0", rev[0], rev[0])
         a = "decoder.mid_block.attentions.0"
-        norm(a + ".group_norm", rev[0])
-        lin(a + ".to_qk", [(a + ".to_q", rev[0]), (a + ".to_k", rev[0])], rev[0])
-        lin(a + ".to_v", [(a + ".to_v", rev[0])], rev[0])
-        lin(a + ".to_out.0", [(a + ".to_out.0", rev[0])], rev[0])
+        E.extend(norm_pair(a + ".group_norm", rev[0]))
+        E.extend(lin_pair(a + ".to_qk", [(a + ".to_q", rev[0]), (a + ".to_k", rev[0])], rev[0]))
+        E.extend(lin_pair(a + ".to_v", [(a + ".to_v", rev[0])], rev[0]))
+        E.extend(lin_pair(a + ".to_out.0", [(a + ".to_out.0", rev[0])], rev[0]))
         res("decoder.mid_block.resnets.1", rev[0], rev[0])
         cin = rev[0]
         for i, co in enumerate(rev):
@@ -97,25 +90,9 @@ def build_entries(cfg: VAEConfig, decoder=True):
                 cin = co
             if i != len(rev) - 1:
                 conv(f"decoder.up_blocks.{i}.upsamplers.0.conv", co, co)
-        norm("decoder.conv_norm_out", cin)
+        E.extend(norm_pair("decoder.conv_norm_out", cin))
         conv("decoder.conv_out", cfg.in_channels, cin)
-    off = 0
-    for e in E:
-        e.off = off
-        off += (e.numel + 127) // 128 * 128
-    return E
-
-
-class _Ops(UNetEngine):
-    """The U-Net executor's op layer (conv3 / linear / groupnorm launch wrappers) over the VAE's parameter arena."""
-
-    def __init__(self, store, dtype):
-        self.cfg, self.blocks, self.P, self.dtype = None, None, store, dtype
-        self.dev = store.master.device
-        self.ws = k.groupnorm_ws(self.dev, 64, 32)
-        self.tape, self.train, self.macs, self.count_macs = [], False, 0, False
-        self.grad_ready_cb, self.fuse_geglu, self.defer_fanin = None, True, False
-        self.gn_epi, self.gn_count, self.gn_miss = False, [0, 0], None     # (GroupNorm statistics from GEMM epilogues: U-Net only)
+    return assign_offsets(E)
 
 
 class _LatentDist:
@@ -159,7 +136,7 @@ class AutoencoderKL:
         self.dtype = dtype
         self.has_decoder = decoder
         self.store = ParamStore(build_entries(self.cfg, decoder), self.device, dtype, train=False)
-        self.ops = _Ops(self.store, dtype)
+        self.ops = Ops(self.store, dtype)
         self.config = SimpleNamespace(scaling_factor=self.cfg.scaling_factor, latent_channels=self.cfg.latent_channels,
                                       block_out_channels=self.cfg.block_out_channels, in_channels=self.cfg.in_channels)
         if init:
@@ -169,23 +146,9 @@ class AutoencoderKL:
     @classmethod
     def from_pretrained(cls, pretrained_model_name_or_path=None, subfolder=None, revision=None, random_init=False,
                         vae_config=None, torch_dtype=torch.bfloat16, device=None, seed=0, **unused):
-        path = pretrained_model_name_or_path
-        if path and subfolder:
-            path = os.path.join(path, subfolder)
-        have_local = bool(path) and os.path.isdir(path)
-        model = cls(vae_config, device, torch_dtype, seed=seed, init=random_init or not have_local)
-        if have_local and not random_init:
-            f = os.path.join(path, "diffusion_pytorch_model.safetensors")
-            if os.path.exists(f):
-                from safetensors.torch import load_file
-                sd = load_file(f)
-            else:
-                sd = torch.load(os.path.join(path, "diffusion_pytorch_model.bin"), map_location="cpu")
-            model.load_state_dict(sd, strict=False)
-        elif not random_init:
-            raise FileNotFoundError(f"{pretrained_model_name_or_path!r} is not a local directory and hub downloads are "
-                                    f"not available here; pass random_init=True or a local checkpoint directory")
-        return model
+        return load_local_or_random(lambda init: cls(vae_config, device, torch_dtype, seed=seed, init=init),
+                                    pretrained_model_name_or_path, subfolder, random_init,
+                                    ("diffusion_pytorch_model.safetensors", "diffusion_pytorch_model.bin"), strict=False)
 
     def load_state_dict(self, sd, strict=True):
         """diffusers AutoencoderKL keys (decoder / post_quant_conv keys are ignored when built with decoder=False); the pre-0.14

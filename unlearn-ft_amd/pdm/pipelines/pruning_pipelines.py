@@ -211,7 +211,7 @@ class _CapturedLoop:
         torch.cuda.current_stream().wait_stream(cap)
         torch.cuda.synchronize()
         eng = self.unet.engine          # what the graph reads or writes beyond its own pool stays allocated
-        self.keep = [pred, eng.ws, getattr(eng, "_cs_arena", None)]
+        self.keep = [pred, eng.ws, eng._cs_arena]
 
     def run(self, latents, ehs, rows):
         """latents: fp32 [B, C, h, w] (contiguous, on the device); ehs: [R, T, ctx] text embeddings (unconditional half
