@@ -491,6 +491,12 @@ int pdmk_gather_rows(const void* x, int ldx, const int64_t* ids, int T, void* ou
                      pdmk_stream stream);
 int pdmk_clip_score_head(const float* a, int lda, const float* b, int ldb, float* an, float* bn, double* acc, int B, int D,
                          pdmk_stream stream);
+/* Head of the artist-erasure score (scripts/metrics/artist_erasure.py): per row r of fp32 t / a / b [B, D] (row strides ldt,
+ * lda, ldb >= D), sim_a[r] = cos(t_r, a_r), sim_b[r] = cos(t_r, b_r) with torch.nn.functional.cosine_similarity's meaning
+ * (every norm clamped below at 1e-8: a zero row gives 0, never NaN) and b_lt_a[r] = sim_b[r] < sim_a[r] on the stored fp32
+ * values.  One workgroup per row, fixed reduction order, no atomics: a row's results do not depend on its batch.  B <= 65535. */
+int pdmk_cosine_pairs(const float* t, int ldt, const float* a, int lda, const float* b, int ldb, float* sim_a, float* sim_b,
+                      int32_t* b_lt_a, int B, int D, pdmk_stream stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Sampler (csrc/sampler.hip): what the eager denoising loop of StableDiffusionPruningPipeline.generate_samples does
@@ -529,6 +535,9 @@ int pdmk_plms_step(const void* pred, int ld, float g_u, float g_t, int cfg, floa
  * `.permute(0, 2, 3, 1).cpu().numpy()`, `img * 255`, `img.astype(np.uint8)`): fp32 NCHW [B, C, HW] in, uint8 NHWC out,
  * truncated (not rounded); NaN gives 0. */
 int pdmk_image_to_u8(const float* src, uint8_t* dst, int B, int C, int HW, pdmk_stream stream);
+/* The same with the last step chosen: rounding 0 = pdmk_image_to_u8 (truncation); rounding 1 = rintf (half to even) first,
+ * diffusers' numpy_to_pil `(img * 255).round().astype("uint8")`.  Any other value: -1. */
+int pdmk_image_to_u8_ex(const float* src, uint8_t* dst, int B, int C, int HW, int rounding, pdmk_stream stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * FID (pdm/utils/fid_utils.py, pdm/models/inception): clean-fid's `legacy_pytorch` mode = pytorch-fid's InceptionV3 pool3

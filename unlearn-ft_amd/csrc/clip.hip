@@ -114,6 +114,40 @@ __global__ __launch_bounds__(NT) void score_head_kernel(const float* __restrict_
     if (threadIdx.x == 0 && acc) atomicAdd(acc, (double)dot);
 }
 
+// one workgroup per row: sim_a = cos(t, a), sim_b = cos(t, b) with every norm clamped below at 1e-8 (a zero row gives 0),
+// b_lt_a = the comparison of the two stored fp32 values.  Fixed reduction order, no atomics: a row's result does not depend on
+// the batch it is in.
+__global__ __launch_bounds__(NT) void cosine_pairs_kernel(const float* __restrict__ t, int ldt, const float* __restrict__ a,
+                                                          int lda, const float* __restrict__ b, int ldb,
+                                                          float* __restrict__ sim_a, float* __restrict__ sim_b,
+                                                          int32_t* __restrict__ b_lt_a, int D) {
+    __shared__ float red[NT / 64];
+    const long r = blockIdx.x;
+    const float *tr = t + r * ldt, *ar = a + r * lda, *br = b + r * ldb;
+    float tt = 0.f, aa = 0.f, bb = 0.f, ta = 0.f, tb = 0.f;
+    for (int c = threadIdx.x; c < D; c += NT) {
+        const float x = tr[c], u = ar[c], v = br[c];
+        tt += x * x;
+        aa += u * u;
+        bb += v * v;
+        ta += x * u;
+        tb += x * v;
+    }
+    tt = block_sum(tt, red);
+    aa = block_sum(aa, red);
+    bb = block_sum(bb, red);
+    ta = block_sum(ta, red);
+    tb = block_sum(tb, red);
+    if (threadIdx.x == 0) {
+        const float eps = 1e-8f;
+        const float nt = fmaxf(sqrtf(tt), eps), na = fmaxf(sqrtf(aa), eps), nb = fmaxf(sqrtf(bb), eps);
+        const float sa = ta / nt / na, sb = tb / nt / nb;
+        sim_a[r] = sa;
+        sim_b[r] = sb;
+        b_lt_a[r] = sb < sa ? 1 : 0;
+    }
+}
+
 unsigned grid_for(long n) {
     const long g = (n + NT - 1) / NT;
     return (unsigned)(g < 8192 ? g : 8192);
@@ -176,6 +210,16 @@ extern "C" int pdmk_clip_score_head(const float* a, int lda, const float* b, int
                                     int B, int D, pdmk_stream stream) {
     if (!a || B <= 0 || B > 65535 || D <= 0 || lda < D || (b && ldb < D) || (!b && (bn || acc)) || (!an && !b)) return -1;
     hipLaunchKernelGGL(score_head_kernel, dim3(B), dim3(NT), 0, (hipStream_t)stream, a, lda, b, ldb, an, bn, acc, D);
+    PDMK_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int pdmk_cosine_pairs(const float* t, int ldt, const float* a, int lda, const float* b, int ldb, float* sim_a,
+                                 float* sim_b, int32_t* b_lt_a, int B, int D, pdmk_stream stream) {
+    if (!t || !a || !b || !sim_a || !sim_b || !b_lt_a || B <= 0 || B > 65535 || D <= 0 || ldt < D || lda < D || ldb < D)
+        return -1;
+    hipLaunchKernelGGL(cosine_pairs_kernel, dim3(B), dim3(NT), 0, (hipStream_t)stream, t, ldt, a, lda, b, ldb, sim_a, sim_b,
+                       b_lt_a, D);
     PDMK_CHECK_LAUNCH();
     return 0;
 }

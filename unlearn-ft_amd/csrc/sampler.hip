@@ -84,6 +84,8 @@ __global__ void plms_step_kernel(const T* __restrict__ pred, int ld, float g_u, 
     }
 }
 
+// ROUND: diffusers' numpy_to_pil, `(img * 255).round().astype("uint8")` (rintf: half to even, as np.round)
+template <bool ROUND>
 __global__ void image_to_u8_kernel(const float* __restrict__ src, uint8_t* __restrict__ dst, int B, int C, int HW) {
     const long npix = (long)B * HW;
     for (long p = blockIdx.x * (long)NT + threadIdx.x; p < npix; p += (long)gridDim.x * NT) {
@@ -94,6 +96,7 @@ __global__ void image_to_u8_kernel(const float* __restrict__ src, uint8_t* __res
             v = v + 0.5f;
             v = fminf(fmaxf(v, 0.f), 1.f);                            // clamp(0, 1); NaN -> 0
             v = v * 255.f;                                            // numpy float32 * 255
+            if (ROUND) v = rintf(v);
             dst[p * C + c] = (uint8_t)(int)v;                         // astype(np.uint8) truncates
         }
     }
@@ -119,10 +122,17 @@ extern "C" int pdmk_plms_step(const void* pred, int ld, float g_u, float g_t, in
     return 0;
 }
 
-extern "C" int pdmk_image_to_u8(const float* src, uint8_t* dst, int B, int C, int HW, pdmk_stream s) {
-    if (!src || !dst || B <= 0 || C <= 0 || HW <= 0) return -1;
-    hipLaunchKernelGGL(image_to_u8_kernel, dim3(grid_for((long)B * HW, 4096)), dim3(NT), 0, (hipStream_t)s, src, dst, B, C,
-                       HW);
+extern "C" int pdmk_image_to_u8_ex(const float* src, uint8_t* dst, int B, int C, int HW, int rounding, pdmk_stream s) {
+    if (!src || !dst || B <= 0 || C <= 0 || HW <= 0 || (rounding != 0 && rounding != 1)) return -1;
+    const dim3 grid(grid_for((long)B * HW, 4096));
+    if (rounding)
+        hipLaunchKernelGGL(image_to_u8_kernel<true>, grid, dim3(NT), 0, (hipStream_t)s, src, dst, B, C, HW);
+    else
+        hipLaunchKernelGGL(image_to_u8_kernel<false>, grid, dim3(NT), 0, (hipStream_t)s, src, dst, B, C, HW);
     PDMK_CHECK_LAUNCH();
     return 0;
+}
+
+extern "C" int pdmk_image_to_u8(const float* src, uint8_t* dst, int B, int C, int HW, pdmk_stream s) {
+    return pdmk_image_to_u8_ex(src, dst, B, C, HW, 0, s);
 }

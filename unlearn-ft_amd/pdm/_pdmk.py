@@ -113,8 +113,10 @@ _SIGS = {
     "pdmk_quick_gelu_fwd": ([vp, vp, i64, i32, vp], i32),
     "pdmk_gather_rows": ([vp, i32, vp, i32, vp, i32, i32, i32, i32, vp], i32),
     "pdmk_clip_score_head": ([vp, i32, vp, i32, vp, vp, vp, i32, i32, vp], i32),
+    "pdmk_cosine_pairs": ([vp, i32, vp, i32, vp, i32, vp, vp, vp, i32, i32, vp], i32),
     "pdmk_plms_step": ([vp, i32, f32, f32, i32, vp, vp, vp, vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, vp], i32),
     "pdmk_image_to_u8": ([vp, vp, i32, i32, i32, vp], i32),
+    "pdmk_image_to_u8_ex": ([vp, vp, i32, i32, i32, i32, vp], i32),
     "pdmk_resize_bilinear_u8": ([vp, i64, vp, vp, i32, i32, vp, vp], i32),
     "pdmk_image_resize_u8": ([vp, i64, vp, vp, i32, i32, i32, vp, vp], i32),
     "pdmk_conv2d_fwd": ([vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp], i32),
@@ -916,6 +918,20 @@ def clip_score_head(a, b, an, bn, acc, B, D):
                                    D, _st()), "pdmk_clip_score_head")
 
 
+def cosine_pairs(t, a, b, sim_a, sim_b, b_lt_a):
+    """fp32 rows t / a / b [B, D] (unit column stride): sim_a[r] = cos(t_r, a_r), sim_b[r] = cos(t_r, b_r) (norms clamped at
+    1e-8), b_lt_a[r] = sim_b[r] < sim_a[r].  sim_a / sim_b fp32 [B], b_lt_a int32 [B], contiguous."""
+    B, D = t.shape
+    for x in (t, a, b):
+        if x.dtype != torch.float32 or x.dim() != 2 or tuple(x.shape) != (B, D) or x.stride(1) != 1 or x.stride(0) < D:
+            raise PdmkError("cosine_pairs: t, a, b fp32 [B, D] of one shape with unit column stride")
+    for x, d in ((sim_a, torch.float32), (sim_b, torch.float32), (b_lt_a, torch.int32)):
+        if x.dtype != d or tuple(x.shape) != (B,) or not x.is_contiguous():
+            raise PdmkError("cosine_pairs: sim_a, sim_b fp32 [B] and b_lt_a int32 [B], contiguous")
+    _chk(_lib.pdmk_cosine_pairs(_p(t), t.stride(0), _p(a), a.stride(0), _p(b), b.stride(0), _p(sim_a), _p(sim_b),
+                                _p(b_lt_a), B, D, _st()), "pdmk_cosine_pairs")
+
+
 def plms_table(rows, device):
     """A list of PlmsRow -> the uint8 device tensor pdmk_plms_step reads (one host-to-device copy)."""
     arr = (PlmsRow * len(rows))(*rows)
@@ -938,13 +954,24 @@ def plms_step(pred, ld, g_u, g_t, cfg, sample, cur, ets, table, nsteps, state, t
                              nsteps, _p(state), _p(t_out), _p(x_next), cpad, B, Cc, HW, dt(pred), _st()), "pdmk_plms_step")
 
 
-def image_to_u8(src, dst):
-    """uint8 NHWC dst [B, H, W, C] = trunc(255 * clamp(src / 2 + 0.5, 0, 1)) of the fp32 NCHW decoder output src."""
+def _u8_shape(src, dst, name):
     B, Cc, H, W = src.shape
     if (src.dtype != torch.float32 or not src.is_contiguous() or dst.dtype != torch.uint8 or not dst.is_contiguous()
             or tuple(dst.shape) != (B, H, W, Cc)):
-        raise PdmkError("image_to_u8: src fp32 contiguous [B, C, H, W], dst uint8 contiguous [B, H, W, C]")
-    _chk(_lib.pdmk_image_to_u8(_p(src), _p(dst), B, Cc, H * W, _st()), "pdmk_image_to_u8")
+        raise PdmkError(f"{name}: src fp32 contiguous [B, C, H, W], dst uint8 contiguous [B, H, W, C]")
+    return B, Cc, H * W
+
+
+def image_to_u8(src, dst):
+    """uint8 NHWC dst [B, H, W, C] = trunc(255 * clamp(src / 2 + 0.5, 0, 1)) of the fp32 NCHW decoder output src."""
+    _chk(_lib.pdmk_image_to_u8(_p(src), _p(dst), *_u8_shape(src, dst, "image_to_u8"), _st()), "pdmk_image_to_u8")
+
+
+def image_to_u8_ex(src, dst, rounding):
+    """image_to_u8 with the last step chosen: rounding 0 truncates (image_to_u8), 1 rounds half to even first (diffusers'
+    numpy_to_pil)."""
+    _chk(_lib.pdmk_image_to_u8_ex(_p(src), _p(dst), *_u8_shape(src, dst, "image_to_u8_ex"), int(rounding), _st()),
+         "pdmk_image_to_u8_ex")
 
 
 def _avail(t):

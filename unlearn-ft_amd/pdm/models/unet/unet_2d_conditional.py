@@ -10,6 +10,7 @@ but the arch vector is resolved to a static packed shape table up front and all 
 There is no CPU path: constructing the model without a GPU + libpdmk.so raises.
 """
 import json
+import logging
 import os
 from types import SimpleNamespace
 
@@ -20,6 +21,8 @@ from ..ops import Act
 from .engine import UNetEngine
 from .params import ParamStore, build_entries
 from .spec import UNetConfig, apply_arch_vector, gate_structure, padc
+
+logger = logging.getLogger("pdm.unet")
 
 # Block-type STRINGS the YAML recipes carry (`model.prediction_model.unet_down_blocks / unet_up_blocks`) are the factory names
 # of get_down_block / get_up_block (pdm/models/unet/unet_2d_conditional.py:90-243, 382-502): "...HalfGated" selects the
@@ -158,6 +161,22 @@ class UNet2DConditionModelPruned:
 
     def load_state_dict(self, sd, strict=True):
         self.store.load_state_dict(sd, strict=strict)
+
+    def overlay_state_dict(self, sd):
+        """Replaces the tensors `sd` names and keeps every other one (a partial checkpoint, the reference's
+        `load_state_dict(sd, strict=False)`): state_dict() -> update -> load_state_dict().  Names the model does not have are
+        ignored and counted in a log line; a shape mismatch raises ValueError.  Returns (replaced, ignored) names."""
+        own = self.state_dict()
+        known = [n for n in sd if n in own]
+        unknown = [n for n in sd if n not in own]
+        for n in known:
+            if tuple(sd[n].shape) != tuple(own[n].shape):
+                raise ValueError(f"{n}: got {tuple(sd[n].shape)}, expected {tuple(own[n].shape)}")
+            own[n] = sd[n]
+        logger.info("overlay_state_dict: %d tensors replaced, %d unknown keys ignored%s", len(known), len(unknown),
+                    f" (first: {unknown[:3]})" if unknown else "")
+        self.load_state_dict(own)
+        return known, unknown
 
     def train(self, mode=True):
         self.training = mode

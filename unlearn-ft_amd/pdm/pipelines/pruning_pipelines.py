@@ -291,8 +291,9 @@ class StableDiffusionPruningPipeline:
                          negative_prompt_embeds=None, output_type="np", return_dict=True, callback=None, callback_steps=1,
                          prompt=None, negative_prompt=None, graph=None):
         """prompt / negative_prompt: strings or lists of strings (needs the tokenizer; with guidance and no negative prompt
-        the empty prompt).  output_type "latent", "pt", "np" (float32 NHWC in [0, 1]) or "u8" (uint8 NHWC numpy, the FID
-        script's `(img * 255).astype(np.uint8)`, formed on the device).  graph: None = the captured loop when possible
+        the empty prompt).  output_type "latent", "pt", "np" (float32 NHWC in [0, 1]), "u8" (uint8 NHWC numpy, the FID
+        script's `(img * 255).astype(np.uint8)`, formed on the device) or "u8_round" (the same with diffusers' numpy_to_pil
+        rounding, `(img * 255).round().astype("uint8")`: the pixels of `pipeline(prompt).images`).  graph: None = the captured loop when possible
         (PDMK_SAMPLER_GRAPH=0 turns it off), False = the eager loop, True = captured whenever possible."""
         cfg_on = guidance_scale > 1.0
         if isinstance(prompt_ids, (str, list, tuple)):            # the reference's positional `prompt`
@@ -313,8 +314,9 @@ class StableDiffusionPruningPipeline:
         height, width = height or 64 * f, width or 64 * f     # unet.config.sample_size * vae_scale_factor at 512 px
         if height % f or width % f:
             raise ValueError(f"`height` and `width` have to be divisible by {f} but are {height} and {width}.")
-        if output_type not in ("latent", "pt", "np", "u8"):
-            raise ValueError("output_type must be 'latent', 'pt', 'np' or 'u8' (PIL conversion is left to the caller)")
+        if output_type not in ("latent", "pt", "np", "u8", "u8_round"):
+            raise ValueError("output_type must be 'latent', 'pt', 'np', 'u8' or 'u8_round' (PIL conversion is left to the "
+                             "caller)")
         dev = self.device
         ehs = torch.cat([negative_prompt_embeds.to(dev), prompt_embeds.to(dev)]) if cfg_on else prompt_embeds.to(dev)
         sch = self.scheduler
@@ -333,10 +335,13 @@ class StableDiffusionPruningPipeline:
             image = latents
         else:
             image = self.vae.decode(latents / self.vae.cfg.scaling_factor, return_dict=False)[0]
-            if output_type == "u8":
+            if output_type in ("u8", "u8_round"):
                 b, c, hh, ww = image.shape
                 u8 = torch.empty((b, hh, ww, c), device=image.device, dtype=torch.uint8)
-                k.image_to_u8(image.contiguous(), u8)
+                if output_type == "u8":
+                    k.image_to_u8(image.contiguous(), u8)
+                else:
+                    k.image_to_u8_ex(image.contiguous(), u8, 1)
                 image = u8.cpu().numpy()
             else:
                 image = (image / 2 + 0.5).clamp(0, 1)                     # VaeImageProcessor.postprocess (denormalize)

@@ -19,6 +19,10 @@ caption row of the validation split, sampled by a fine-tuned student, for FID / 
   name being the last path component with a trailing ".jpg" removed; [R, R, 3] uint8 (R = --image_resolution, default 512)
   from pdmk_image_to_u8 (truncation, as `img * 255; img.astype(np.uint8)`).  Rows that share an image overwrite each other in
   row order.
+* --erasure_ckpt_path FILE (generate_fid_images.py:97-111): an erasure baseline's checkpoint laid over the student's weights
+  (pdm/utils/erasure_utils.py load_erasure_checkpoint: 'esd' in the path = ESD's nested {module: {weight, bias}} form,
+  non-strict; otherwise a full state dict, strict).  The images then go to the reference's directory,
+  <finetuning_ckpt_dir>/<path with '/' and '.' replaced by '_'>/<data.dataset_name>_fid_images/.
 * Ranks come from RANK / WORLD_SIZE / LOCAL_RANK; nothing collective runs on the GPU (a gloo barrier at the end), so
   several ranks may share one device.
 """
@@ -56,6 +60,9 @@ def image_file_name(image):
 
 def output_dir(config):
     name = config.get_path("data.dataset_name")
+    if config.get("erasure_ckpt_path") is not None:
+        from pdm.utils.erasure_utils import erasure_dir_name
+        return os.path.join(config.finetuning_ckpt_dir, erasure_dir_name(config.erasure_ckpt_path), f"{name}_fid_images")
     return os.path.join(config.finetuning_ckpt_dir, f"{name}_fid_images_{config.get_path('training.num_inference_steps', 50)}")
 
 
@@ -88,6 +95,9 @@ def load_pipeline(config, device):
         down_block_types=pm.get("unet_down_blocks"), up_block_types=pm.get("unet_up_blocks"),
         mid_block_type=pm.get("unet_mid_block"), gated_ff=pm.get("gated_ff", True), ff_gate_width=pm.get("ff_gate_width", 32),
         attention_precision=pm.get("attention_precision"), train=False)
+    if config.get("erasure_ckpt_path") is not None:
+        from pdm.utils.erasure_utils import load_erasure_checkpoint
+        load_erasure_checkpoint(unet, config.erasure_ckpt_path)
     tok = load_tokenizer(config.get_path("pretrained_model_name_or_path"))
     return StableDiffusionPruningPipeline(models.vae, models.text_encoder, unet, load_scheduler(config), tok)
 
@@ -113,8 +123,6 @@ def main():
     config = load_config(args.base_config_path)
     config.update(vars(args))                       # flat CLI overlay at the root, like the reference
     logging.basicConfig(level=logging.INFO, format="%(asctime)s %(name)s %(levelname)s %(message)s")
-    if args.erasure_ckpt_path is not None:
-        raise NotImplementedError("--erasure_ckpt_path: erasure checkpoints are not supported by this build")
     assert config.finetuning_ckpt_dir is not None, "finetuning checkpoint directory must be provided"
     rank, world = int(os.environ.get("RANK", 0)), int(os.environ.get("WORLD_SIZE", 1))
     local = int(os.environ.get("LOCAL_RANK", 0))
