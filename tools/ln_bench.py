@@ -24,5 +24,11 @@ for M, C in [(32768, 320), (8192, 640), (2048, 1280), (65536, 320), (512, 1280)]
     dg = torch.zeros(C, device=dev); db = torch.zeros(C, device=dev)
     tf = gtime(lambda: k.layernorm_fwd(x, y, gamma, beta, stats, M, C, C, C, 1e-5))
     tb = gtime(lambda: k.layernorm_bwd(x, dy, dx, gamma, stats, dg, db, M, C, C, C, C, False))
+    # the forms the step runs: the residual stream's gradient arrives through `add` (a strided view), and dx often accumulates
+    add = torch.randn(M, C + 16, device=dev).to(dt)[:, 8:8 + C]
+    ta = gtime(lambda: k.layernorm_bwd(x, dy, dx, gamma, stats, dg, db, M, C, C, C, C, False, add=add))
+    tc = gtime(lambda: k.layernorm_bwd(x, dy, dx, gamma, stats, dg, db, M, C, C, C, C, True, add=add))
     nb = M * C * 2
-    print(f"M{M} C{C}: fwd {tf:6.1f} us ({2 * nb / tf / 1e6:5.2f} TB/s of 1R+1W)   bwd {tb:6.1f} us ({3 * nb / tb / 1e6:5.2f} TB/s of 2R+1W)   copy {gtime(lambda: y.copy_(x)):5.1f}", flush=True)
+    print(f"M{M} C{C}: fwd {tf:6.1f} us ({2 * nb / tf / 1e6:5.2f} TB/s of 1R+1W)   bwd {tb:6.1f} us ({3 * nb / tb / 1e6:5.2f} TB/s of 2R+1W)   "
+          f"bwd+add {ta:6.1f} us ({4 * nb / ta / 1e6:5.2f} TB/s of 3R+1W)   bwd+add+acc {tc:6.1f} us ({5 * nb / tc / 1e6:5.2f} TB/s of 4R+1W)   "
+          f"copy {gtime(lambda: y.copy_(x)):5.1f}", flush=True)

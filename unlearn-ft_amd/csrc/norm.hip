@@ -781,135 +781,200 @@ __global__ __launch_bounds__(NT) void ln_fwd_kernel(const T* __restrict__ x, T* 
     }
 }
 
-// backward: each wave walks its rows R at a time (R independent row loads in flight: the row reductions make a single
-// row latency-bound); SLOTS = 16-byte chunks per lane is a template parameter so small C does not pay registers for 1280.
-template <typename T, int SLOTS, int R>
+// backward: a row is owned by a group of L lanes (L = 8 / 16 / 32 / 64 chosen from C so that a lane holds S <= 5 16-byte chunks,
+// ln_bwd_form), so a wave works on G = 64 / L rows per pass and the four waves of a block on 4 * G consecutive rows: lane
+// (grp, li) of wave w holds chunks li, li + L, ... of row r0 + (pass * 4 + w) * G + grp - each wave load instruction covers G
+// pieces of L * 16 contiguous bytes (>= one 128-byte segment).  One wave per row (the previous form) left 24 of 64 lanes without
+// a chunk at C = 320, paid two 6-step wave reductions per row and two broadcast dword loads of the row statistics per lane and
+// row, and read gamma element by element.  Here
+//  - the two row sums are log2(L) exchange steps that serve all G rows of the wave at once, (mean, rstd) is one 8-byte load;
+//  - gamma is read once per block (coalesced dwords, issued before the rows) into LDS and taken from there as float4 at each
+//    use: S * V registers less than a register copy, which is what lets the S = 3 forms run two waves per SIMD;
+//  - x, dy and the statistics of the next pass are requested before the current pass is reduced (register double buffer);
+//    the `add` and accumulate_dx operands, when present, go out with the first pass's rows and after that as soon as the
+//    pass that used their registers has stored (a second register set for them costs the second wave per SIMD);
+//  - x and dy stay packed between their two uses (row sums, then dx): unpacking twice is cheaper than S * V * 2 live floats;
+//  - dgamma / dbeta: per lane over all its rows, then across the wave's G row groups in registers, then across the four waves
+//    in LDS in a fixed order, one slab row per block written by all 256 threads (no atomics: the slab is bit-reproducible).
+// S = 5 (which C = 320 / 640 / 1280 would fit with L = 8 / 16 / 32) takes 357 registers - one wave per SIMD - and measured slower
+// than S = 3 on twice the lanes at every step shape (32 768 x 320: 34.7 against 24.7 us in one session), so S = 5 is left to C > 1536 (bf16);
+// profiles/ln_bwd_bench.txt has the A/B against the one-wave-per-row kernel.
+// the packed chunk is used twice (row sums, then dx); without this the compiler keeps the unpacked floats of the first use alive
+template <typename R> __device__ __forceinline__ void keep_packed(R& r) {
+    f32x4 t = __builtin_bit_cast(f32x4, r);
+    asm volatile("" : "+v"(t));
+    r = __builtin_bit_cast(R, t);
+}
+template <typename T, int L, int S>
 __global__ __launch_bounds__(NT) void ln_bwd_kernel(const T* __restrict__ x, const T* __restrict__ dy,
                                                     T* __restrict__ dx, const float* __restrict__ gamma,
                                                     const float* __restrict__ stats, float* __restrict__ part,
                                                     int M, int C, int ldx, int lddy,
-                                                    int lddx, int accumulate, int rows_per_wave,
+                                                    int lddx, int accumulate, int rows_per_blk,
                                                     const T* __restrict__ add, int ldadd) {
     // add (optional): a second finished gradient of the same tensor (the residual branch's, blocks.py:705-867) added in this
     // store - dx = (accumulate ? dx : 0) + add + this layer's input gradient - so that the fan-in needs neither a pass of its
     // own nor an in-place update of a buffer another kernel still reads (a deferred weight gradient's dY)
-    constexpr int V = Vec<T>::N;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int nchunks = C / V;
-    float gm[SLOTS][V], ag[SLOTS][V], ab[SLOTS][V];
-#pragma unroll
-    for (int sl = 0; sl < SLOTS; ++sl) {
-        const int c = lane + 64 * sl;
-#pragma unroll
-        for (int e = 0; e < V; ++e) {
-            ag[sl][e] = ab[sl][e] = 0.f;
-            gm[sl][e] = (c < nchunks) ? gamma[c * V + e] : 0.f;
-        }
-    }
-    const int mbase = (blockIdx.x * 4 + wave) * rows_per_wave;
-    const int mend = min(M, mbase + rows_per_wave);
-    const float invC = 1.0f / C;
-    // register ping-pong: the next R rows (x, dy, their statistics) are requested before the current R rows are reduced - the two
-    // wave reductions per row otherwise leave the memory pipe idle (36.9 us for 32 768 x 320 against 6.7 for a copy)
+    constexpr int V = Vec<T>::N, G = 64 / L, LV = L * V;
     typedef typename Vec<T>::raw Raw;
-    Raw px[R][SLOTS], pd[R][SLOTS];
-    float pm[R], pr[R];
-    auto fetch = [&](int m0) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int li = lane % L, grp = lane / L;
+    const int nchunks = C / V;
+    const int r0 = blockIdx.x * rows_per_blk, r1 = min(M, r0 + rows_per_blk);      // r0 < M: the grid is ceil(M / rows_per_blk)
+    __shared__ __attribute__((aligned(16))) float sgm[S * LV];     // gamma, zero past C
+    __shared__ float red[2][4][LV];
+    float gst[(S * LV + NT - 1) / NT];
 #pragma unroll
-        for (int q = 0; q < R; ++q) {
-            const int m = min(m0 + q, mend - 1);          // clamp: duplicates of the last row are discarded below
-            pm[q] = stats[2 * (long)m];
-            pr[q] = stats[2 * (long)m + 1];
+    for (int i = 0; i < (S * LV + NT - 1) / NT; ++i) {             // (first: loads return in issue order, and the rows follow)
+        const int col = threadIdx.x + i * NT;
+        gst[i] = col < C ? gamma[col] : 0.f;
+    }
+    // loads carry no lane condition (a branch around each one serialises them): a chunk slot past the row re-reads the row's
+    // first chunk, and its gamma is zero, so it adds nothing to the row sums; its column sums and its dx are never stored
+    int coff[S];
 #pragma unroll
-            for (int sl = 0; sl < SLOTS; ++sl) {
-                const int c = lane + 64 * sl;
-                if (c < nchunks) {
-                    px[q][sl] = Vec<T>::load_raw(x + (long)m * ldx + c * V);
-                    pd[q][sl] = Vec<T>::load_raw(dy + (long)m * lddy + c * V);
-                }
-            }
+    for (int sl = 0; sl < S; ++sl) coff[sl] = (li + L * sl < nchunks ? li + L * sl : 0) * V;
+    Raw px[S], pd[S], pa[S], po[S];
+    float2 pst;
+#pragma unroll
+    for (int sl = 0; sl < S; ++sl) pa[sl] = po[sl] = Raw{};
+    auto fetch_xd = [&](int m0) {
+        const long m = min(m0 + grp, r1 - 1);             // clamp: duplicates of the block's last row are discarded below
+        pst = *reinterpret_cast<const float2*>(stats + 2 * m);
+        const T *xr = x + m * ldx, *dr = dy + m * lddy;
+#pragma unroll
+        for (int sl = 0; sl < S; ++sl) {
+            px[sl] = Vec<T>::load_raw(xr + coff[sl]);
+            pd[sl] = Vec<T>::load_raw(dr + coff[sl]);
         }
     };
-    if (mbase < mend) fetch(mbase);
-    for (int m0 = mbase; m0 < mend; m0 += R) {
-        float xh[R][SLOTS][V], d[R][SLOTS][V], mean[R], rstd[R];
+    auto fetch_ao = [&](int m0) {
+        const long m = min(m0 + grp, r1 - 1);
+        if (add) {
+            const T* ar = add + m * ldadd;
 #pragma unroll
-        for (int q = 0; q < R; ++q) {
-            mean[q] = pm[q];
-            rstd[q] = pr[q];
-#pragma unroll
-            for (int sl = 0; sl < SLOTS; ++sl) {
-                const int c = lane + 64 * sl;
-                if (c < nchunks) {
-                    Vec<T>::unpack(px[q][sl], xh[q][sl]);
-                    Vec<T>::unpack(pd[q][sl], d[q][sl]);
-                } else {
-#pragma unroll
-                    for (int e = 0; e < V; ++e) xh[q][sl][e] = d[q][sl][e] = 0.f;
-                }
-            }
+            for (int sl = 0; sl < S; ++sl) pa[sl] = Vec<T>::load_raw(ar + coff[sl]);
         }
-        if (m0 + R < mend) fetch(m0 + R);
+        if (accumulate) {
+            const T* orow = dx + m * lddx;
 #pragma unroll
-        for (int q = 0; q < R; ++q) {
-            const bool live = m0 + q < mend;
-            float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-            for (int sl = 0; sl < SLOTS; ++sl) {
-                const int c = lane + 64 * sl;
-#pragma unroll
-                for (int e = 0; e < V; ++e) {
-                    const float h = (c < nchunks) ? (xh[q][sl][e] - mean[q]) * rstd[q] : 0.f;
-                    xh[q][sl][e] = h;
-                    if (live) { ab[sl][e] += d[q][sl][e]; ag[sl][e] += d[q][sl][e] * h; }
-                    const float g = d[q][sl][e] * gm[sl][e];
-                    s1 += g;
-                    s2 += g * h;
-                }
-            }
-            s1 = wave_sum(s1) * invC;
-            s2 = wave_sum(s2) * invC;
-            if (live) {
-                const int m = m0 + q;
-#pragma unroll
-                for (int sl = 0; sl < SLOTS; ++sl) {
-                    const int c = lane + 64 * sl;
-                    if (c < nchunks) {
-                        float o[V], a2[V];
-                        if (accumulate) Vec<T>::load(dx + (long)m * lddx + c * V, o);
-                        if (add) Vec<T>::load(add + (long)m * ldadd + c * V, a2);
-#pragma unroll
-                        for (int e = 0; e < V; ++e) {
-                            float v = rstd[q] * (d[q][sl][e] * gm[sl][e] - s1 - xh[q][sl][e] * s2);
-                            if (add) v += a2[e];
-                            o[e] = accumulate ? o[e] + v : v;
-                        }
-                        Vec<T>::store(dx + (long)m * lddx + c * V, o);
-                    }
-                }
-            }
+            for (int sl = 0; sl < S; ++sl) po[sl] = Vec<T>::load_raw(orow + coff[sl]);
         }
+    };
+    int m0 = r0 + wave * G;
+    if (m0 < r1) { fetch_xd(m0); fetch_ao(m0); }
+    else {
+#pragma unroll
+        for (int sl = 0; sl < S; ++sl) px[sl] = pd[sl] = Raw{};
+        pst = float2{0.f, 0.f};
     }
-    // combine the 4 waves in LDS, then one slab row per block (second stage: reduce_partials_kernel)
-    __shared__ float red[2][3][64 * V];
 #pragma unroll
-    for (int sl = 0; sl < SLOTS; ++sl) {
-        const int c = lane + 64 * sl;
-        __syncthreads();
-        if (wave > 0) {
+    for (int i = 0; i < (S * LV + NT - 1) / NT; ++i) {
+        const int col = threadIdx.x + i * NT;
+        if (col < S * LV) sgm[col] = gst[i];
+    }
+    __syncthreads();
+    float ag[S][V], ab[S][V];
 #pragma unroll
-            for (int e = 0; e < V; ++e) { red[0][wave - 1][lane * V + e] = ag[sl][e]; red[1][wave - 1][lane * V + e] = ab[sl][e]; }
+    for (int sl = 0; sl < S; ++sl)
+#pragma unroll
+        for (int e = 0; e < V; ++e) ag[sl][e] = ab[sl][e] = 0.f;
+    auto load_gm = [&](int sl, float* gm) {
+#pragma unroll
+        for (int e = 0; e < V; e += 4) {
+            const float4 g4 = *reinterpret_cast<const float4*>(&sgm[(li + L * sl) * V + e]);
+            gm[e] = g4.x; gm[e + 1] = g4.y; gm[e + 2] = g4.z; gm[e + 3] = g4.w;
         }
-        __syncthreads();
-        if (wave == 0 && c < nchunks) {
+    };
+    const float invC = 1.0f / C;
+    for (; m0 < r1; m0 += 4 * G) {                       // (wave-uniform: no barrier inside)
+        Raw cx[S], cd[S];
+#pragma unroll
+        for (int sl = 0; sl < S; ++sl) { cx[sl] = px[sl]; cd[sl] = pd[sl]; }
+        const float mean = pst.x, rstd = pst.y;
+        const bool more = m0 + 4 * G < r1;
+        if (more) fetch_xd(m0 + 4 * G);
+        const bool live = m0 + grp < r1;
+        float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+        for (int sl = 0; sl < S; ++sl) {
+            float f[V], d[V], gm[V];
+            Vec<T>::unpack(cx[sl], f);
+            Vec<T>::unpack(cd[sl], d);
+            load_gm(sl, gm);
 #pragma unroll
             for (int e = 0; e < V; ++e) {
-                const float g2 = ag[sl][e] + red[0][0][lane * V + e] + red[0][1][lane * V + e] + red[0][2][lane * V + e];
-                const float b2 = ab[sl][e] + red[1][0][lane * V + e] + red[1][1][lane * V + e] + red[1][2][lane * V + e];
-                float* slab = part + (long)blockIdx.x * 2 * C;      // [dgamma | dbeta] of this block
-                slab[c * V + e] = g2;
-                slab[C + c * V + e] = b2;
+                const float h = (f[e] - mean) * rstd;
+                if (live) { ab[sl][e] += d[e]; ag[sl][e] += d[e] * h; }
+                const float g = d[e] * gm[e];            // (chunk slots past the row: gm = 0)
+                s1 += g;
+                s2 += g * h;
             }
+        }
+#pragma unroll
+        for (int o = L / 2; o > 0; o >>= 1) {
+            s1 += __shfl_xor(s1, o, 64);
+            s2 += __shfl_xor(s2, o, 64);
+        }
+        s1 *= invC;
+        s2 *= invC;
+        if (live) {
+            const long m = m0 + grp;
+#pragma unroll
+            for (int sl = 0; sl < S; ++sl) {
+                const int c = li + L * sl;
+                if (c < nchunks) {
+                    float f[V], d[V], gm[V], o[V];
+                    keep_packed(cx[sl]);
+                    keep_packed(cd[sl]);
+                    Vec<T>::unpack(cx[sl], f);
+                    Vec<T>::unpack(cd[sl], d);
+                    load_gm(sl, gm);
+#pragma unroll
+                    for (int e = 0; e < V; ++e) {
+                        const float h = (f[e] - mean) * rstd;
+                        o[e] = rstd * (d[e] * gm[e] - s1 - h * s2);
+                    }
+                    if (add) {                           // (uniform branches: the plain form pays nothing for the operands)
+                        float a2[V];
+                        Vec<T>::unpack(pa[sl], a2);
+#pragma unroll
+                        for (int e = 0; e < V; ++e) o[e] += a2[e];
+                    }
+                    if (accumulate) {
+                        float o2[V];
+                        Vec<T>::unpack(po[sl], o2);
+#pragma unroll
+                        for (int e = 0; e < V; ++e) o[e] = o2[e] + o[e];
+                    }
+                    Vec<T>::store(dx + m * lddx + c * V, o);
+                }
+            }
+        }
+        if (more) fetch_ao(m0 + 4 * G);
+    }
+    // column sums: across the wave's G row groups in registers (every lane ends with the same sum), then the four waves in LDS,
+    // a slot at a time, in a fixed order; all 256 threads write the slab row (second stage: reduce_partials_kernel)
+    float* slab = part + (long)blockIdx.x * 2 * C;          // [dgamma | dbeta] of this block
+#pragma unroll
+    for (int sl = 0; sl < S; ++sl) {
+#pragma unroll
+        for (int e = 0; e < V; ++e) {
+#pragma unroll
+            for (int o = L; o < 64; o <<= 1) {
+                ag[sl][e] += __shfl_xor(ag[sl][e], o, 64);
+                ab[sl][e] += __shfl_xor(ab[sl][e], o, 64);
+            }
+        }
+        __syncthreads();
+        if (lane < L) {
+#pragma unroll
+            for (int e = 0; e < V; ++e) { red[0][wave][lane * V + e] = ag[sl][e]; red[1][wave][lane * V + e] = ab[sl][e]; }
+        }
+        __syncthreads();
+        for (int j = threadIdx.x; j < 2 * LV; j += NT) {
+            const int w = j / LV, jj = j - w * LV, col = sl * LV + jj;
+            if (col < C) slab[w * C + col] = (red[w][0][jj] + red[w][1][jj]) + (red[w][2][jj] + red[w][3][jj]);
         }
     }
 }
@@ -933,12 +998,29 @@ int ln_fwd(const void* x, void* y, const float* gamma, const float* beta, float*
     PDMK_CHECK_LAUNCH();
     return 0;
 }
-// rows per wave of the LayerNorm backward (about `blocks` blocks of 4 waves; also fixes the partial-slab count)
-static int ln_bwd_rpw(int M) {
-    // (tools/ln_bench.py, 32 768 x 320: 45 / 32 / 25.5 / 28 us at 2048 / 1024 / 512 / 256 blocks - the block's LDS combine and slab row
-    // are worth ~16 rows of streaming; 8192 x 640: 19 us at 4 rows per wave, 16.6 at 8)
-    int rpw = (M + 512 * 4 - 1) / (512 * 4);
-    return rpw < 8 ? 8 : (rpw > 64 ? 64 : rpw);
+// rows per block of the LayerNorm backward: as many blocks as 16 rows per block allow, up to 512 (also fixes the partial-slab
+// count: pdmk_layernorm_bwd_partial_dims and the launch both call this, and pdmk.h promises M / 16 + 1 slabs are enough).
+// Above 16 the count is a multiple of 32 - whole passes of every lane-group form (a block pass is 4 * 64 / L <= 32 rows) - and at
+// most 256.  8192 x 640 -> 512 blocks, 2048 x 1280 -> 128, 512 x 1280 -> 32, 32 768 x 320 -> 512 of 64 rows, 65 536 x 320 -> 512
+// of 128 rows.  (The one-wave-per-row kernel never went below 32 rows: its LDS combine and slab row cost ~16 rows of streaming
+// and 2048 x 1280 ran on 64 of the 256 CUs; the A/B of this rule and kernel is profiles/ln_bwd_bench.txt.)
+static int ln_bwd_rows_per_blk(int M) {
+    const int rpb = (M + 511) / 512;
+    if (rpb <= 16) return 16;
+    return rpb > 224 ? 256 : (rpb + 31) / 32 * 32;
+}
+// lane-group form from the chunk count alone: L lanes per row, S chunks per lane (L * S >= nchunks, S <= LN_MAXS)
+struct LnBwdForm {
+    int L, S;
+};
+static LnBwdForm ln_bwd_form(int nchunks) {
+    if (nchunks <= 8) return {8, 1};
+    if (nchunks <= 16) return {8, 2};
+    if (nchunks <= 24) return {8, 3};
+    if (nchunks <= 48) return {16, 3};
+    if (nchunks <= 96) return {32, 3};
+    if (nchunks <= 192) return {64, 3};
+    return {64, 5};
 }
 template <typename T>
 int ln_bwd(const void* x, const void* dy, void* dx, const float* gamma, const float* stats, float* dgamma,
@@ -946,17 +1028,20 @@ int ln_bwd(const void* x, const void* dy, void* dx, const float* gamma, const fl
            const void* add, int ldadd, hipStream_t st) {
     constexpr int V = Vec<T>::N;
     if (C % V || ldx % V || lddy % V || lddx % V || C / V > LN_MAXS * 64 || (add && (ldadd % V))) return -1;
-    const int rpw = ln_bwd_rpw(M);
-    const int rows_per_blk = 4 * rpw;
+    const int rows_per_blk = ln_bwd_rows_per_blk(M);
     const dim3 grid((M + rows_per_blk - 1) / rows_per_blk);
     if (!part || (long)grid.x * 2 * C > part_elems) return -1;
-    const int slots = (C / V + 63) / 64;
-#define PDMK_LNB(S, RR) hipLaunchKernelGGL((ln_bwd_kernel<T, S, RR>), grid, dim3(NT), 0, st, (const T*)x, (const T*)dy, \
-                                           (T*)dx, gamma, stats, part, M, C, ldx, lddy, lddx, acc, rpw, (const T*)add, ldadd)
-    if (slots <= 1) PDMK_LNB(1, 4);
-    else if (slots == 2) PDMK_LNB(2, 2);
-    else if (slots == 3) PDMK_LNB(3, 2);
-    else PDMK_LNB(LN_MAXS, 1);
+    const LnBwdForm fm = ln_bwd_form(C / V);
+#define PDMK_LNB(LL, SS) hipLaunchKernelGGL((ln_bwd_kernel<T, LL, SS>), grid, dim3(NT), 0, st, (const T*)x, (const T*)dy, \
+                                            (T*)dx, gamma, stats, part, M, C, ldx, lddy, lddx, acc, rows_per_blk,       \
+                                            (const T*)add, ldadd)
+    if (fm.L == 8 && fm.S == 1) PDMK_LNB(8, 1);
+    else if (fm.L == 8 && fm.S == 2) PDMK_LNB(8, 2);
+    else if (fm.L == 8) PDMK_LNB(8, 3);
+    else if (fm.L == 16) PDMK_LNB(16, 3);
+    else if (fm.L == 32) PDMK_LNB(32, 3);
+    else if (fm.S == 3) PDMK_LNB(64, 3);
+    else PDMK_LNB(64, 5);
 #undef PDMK_LNB
     launch_reduce_partials(part, grid.x, C, dgamma, dbeta, st);
     PDMK_CHECK_LAUNCH();
@@ -1026,8 +1111,8 @@ extern "C" int pdmk_groupnorm_bwd_partial_dims(int B, int HW, int C, int G, int 
 }
 extern "C" int pdmk_layernorm_bwd_partial_dims(int M, int C, int32_t* nblk, int32_t* n) {
     if (!nblk || !n || M <= 0 || C <= 0) return -1;
-    const int rpw = ln_bwd_rpw(M);
-    *nblk = (M + 4 * rpw - 1) / (4 * rpw);
+    const int rpb = ln_bwd_rows_per_blk(M);
+    *nblk = (M + rpb - 1) / rpb;
     *n = C;
     return 0;
 }
