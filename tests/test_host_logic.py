@@ -22,6 +22,90 @@ def test_cabi_library_exports_every_declared_symbol():
     assert _pdmk.version() >= 100
 
 
+def test_ctypes_table_agrees_with_the_header_on_every_argument_type():
+    """_pdmk._SIGS is a hand-written copy of the prototypes of include/pdmk.h: per function the return width and the class of
+    every parameter - pointer (pdmk_stream and pdmk_comm_t are pointers), i32, i64, f32, f64 - must agree, or a launch gets garbage."""
+    import ctypes as C
+    from pdm import _pdmk
+    hdr = open(os.path.join(ROOT, "include", "pdmk.h")).read()
+    hdr = re.sub(r"/\*.*?\*/", " ", hdr, flags=re.S)
+    hdr = re.sub(r"//[^\n]*", " ", hdr)
+    scalar = {"int": "i32", "int32_t": "i32", "int64_t": "i64", "float": "f32", "double": "f64"}
+    ctype = {C.c_int32: "i32", C.c_int64: "i64", C.c_float: "f32", C.c_double: "f64"}
+
+    def param(text):
+        words = text.replace("const", " ").split()
+        if "*" in text or words[0] in ("pdmk_stream", "pdmk_comm_t"):
+            return "ptr"
+        return scalar[words[0]]
+
+    protos = re.findall(r"^(int|int64_t)\s+(pdmk_\w+)\s*\(([^)]*)\)\s*;", hdr, flags=re.M)
+    assert len(protos) >= 90, len(protos)
+    assert {n for _, n, _ in protos} == set(_pdmk._SIGS)
+    for ret, name, args in protos:
+        want = [] if args.strip() in ("", "void") else [param(a) for a in args.split(",")]
+        argtypes, restype = _pdmk._SIGS[name]
+        assert [ctype.get(t, "ptr") for t in argtypes] == want, name
+        assert ctype[restype] == scalar[ret], name
+
+
+def test_gradient_slot_never_writes_a_lent_buffer(monkeypatch):
+    """pdm.models.ops.Act on CPU tensors (pdmk_copy2d replaced by its torch meaning): every arrival at a LENT gradient buffer - a
+    writer without an addend port, a norm backward with one, a second finished gradient, an accumulate after `.g` was read -
+    leaves it untouched and still sums right; after release() it is accumulated into in place; a pending addend goes to the
+    kernel with a port, else into the buffer on the next read."""
+    from pdm import _pdmk as k
+    from pdm.models.ops import Act
+
+    def copy2d(src, dst, rows, cols, lds, ldd, accumulate=False):
+        dst[:rows, :cols] = src[:rows, :cols] + (dst[:rows, :cols] if accumulate else 0)
+    monkeypatch.setattr(k, "copy2d", copy2d)
+    t, ones = torch.zeros(4, 6), torch.ones(4, 6)
+
+    def lent():
+        a, L = Act(t), torch.ones(4, 6)
+        assert a.empty
+        a.give(L, lend=True)
+        assert not a.empty and a.g is L
+        return a, L
+    a, L = lent()                                  # writer without a port: private copy, accumulate
+    dx, acc, add = a.dst()
+    assert acc and add is None and dx is not L and torch.equal(dx, ones)
+    dx += 1
+    assert torch.equal(L, ones) and torch.equal(a.g, 2 * ones)
+    a, L = lent()                                  # writer with a port: the lent buffer is its addend, it stores a fresh one
+    dx, acc, add = a.dst(port=True)
+    assert add is L and not acc and dx is not L
+    for defer in (False, True):
+        a, L = lent()                              # a second finished gradient
+        a.give(3 * ones, defer=defer)
+        assert torch.equal(a.g, 4 * ones) and torch.equal(L, ones)
+        a, L = lent()                              # .g read first, then an accumulate
+        assert a.g is L
+        a.give(3 * ones, defer=defer)
+        assert torch.equal(a.g, 4 * ones) and torch.equal(L, ones)
+    a, L = lent()                                  # released: owned like any handed-over buffer
+    a.release()
+    dx, acc, add = a.dst()
+    assert dx is L and acc and add is None
+    a = Act(t)                                     # owned + pending addend
+    dx, acc, add = a.dst()
+    assert not acc and add is None
+    dx.zero_()
+    P = 2 * torch.ones(4, 6)
+    a.give(P, defer=True)
+    dx2, acc, add = a.dst(port=True)
+    assert dx2 is dx and acc and add is P and torch.equal(dx, torch.zeros(4, 6))
+    a.give(P, defer=True)
+    assert torch.equal(a.g, P) and a.g is dx
+    a.give(P, defer=True)                          # a writer without a port: the pending addend is added before it accumulates
+    dx3, acc, add = a.dst()
+    assert dx3 is dx and acc and add is None and torch.equal(dx, 2 * P)
+    r = Act(t, rg=False)
+    r.give(ones)
+    assert r.empty
+
+
 def test_workspace_queries_and_plan_file_roundtrip(tmp_path):
     """The *_workspace_bytes() queries answer without a GPU; the plan cache round-trips through its file."""
     from pdm import _pdmk as k

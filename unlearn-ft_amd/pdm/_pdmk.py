@@ -5,6 +5,7 @@ torch is used for device memory and streams only (tensors are passed as raw devi
 """
 import ctypes as C
 import os
+from collections import namedtuple
 
 import torch
 
@@ -212,17 +213,31 @@ class Recorder:
         return False
 
 
-def _launch_gemm(g, macs, shape):
-    """pdmk_gemm on a filled argument block (+ the optional HIP-event bracket of bench.py's per-kernel profile)."""
+def _prof_begin():
+    """The HIP-event bracket of bench.py's per-kernel profile: (start, end) with start recorded on the launch stream, or None."""
     if PROFILE is None:
-        _chk(_lib.pdmk_gemm(C.byref(g), _st()), "pdmk_gemm")
-        return
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    _chk(_lib.pdmk_gemm(C.byref(g), _st()), "pdmk_gemm")
-    e1.record()
-    kind = ("bf16" if g.dtype == BF16 else "f32", g.a_mode, g.b_mode, _lib.pdmk_gemm_last_candidate())
-    PROFILE.append((kind, 2.0 * (macs if macs is not None else g.M * g.N * g.K), e0, e1, shape))
+        return None
+    ev = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    ev[0].record()
+    return ev
+
+
+def _prof_end(ev, g, flops, shape, *tail):
+    """Closes the bracket: PROFILE gets (kind, flops, e0, e1, shape), kind = (dtype, a_mode, b_mode, the candidate that ran) + tail."""
+    if ev is not None:
+        ev[1].record()
+        kind = ("bf16" if g.dtype == BF16 else "f32", g.a_mode, g.b_mode, _lib.pdmk_gemm_last_candidate()) + tail
+        PROFILE.append((kind, flops, ev[0], ev[1], shape))
+
+
+def _launch_gemm(g, macs, shape):
+    """pdmk_gemm on a filled argument block, bracketed by HIP events when PROFILE is a list.  Returns the status: what a
+    non-zero one means is the caller's business (-2 = no fused kernel, for the GEGLU forms)."""
+    ev = _prof_begin()
+    rc = _lib.pdmk_gemm(C.byref(g), _st())
+    if rc == 0:
+        _prof_end(ev, g, 2.0 * (macs if macs is not None else g.M * g.N * g.K), shape)
+    return rc
 
 
 def gemm_group(recs):
@@ -233,33 +248,25 @@ def gemm_group(recs):
     for i, r in enumerate(recs):
         arr[i] = r.g
     got = i32(0)
-    prof = PROFILE is not None
-    if prof:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
+    ev = _prof_begin()
     _chk(_lib.pdmk_gemm_group(arr, n, _st(), C.byref(got)), "pdmk_gemm_group")
     STATS["launches"] += 1 if got.value == n else n
     STATS["grouped"] += got.value
-    if prof:
-        e1.record()
-        g0 = recs[0].g
-        kind = ("bf16" if g0.dtype == BF16 else "f32", g0.a_mode, g0.b_mode, _lib.pdmk_gemm_last_candidate(), int(got.value))
-        flops = sum(2.0 * (r.macs if r.macs is not None else r.g.M * r.g.N * r.g.K) for r in recs)
-        PROFILE.append((kind, flops, e0, e1, [(r.g.M, r.g.N, r.g.K, int(r.g.splitk), int(bool(r.g.R) or r.g.accumulate == 1))
-                                               for r in recs]))
+    _prof_end(ev, recs[0].g, sum(2.0 * (r.macs if r.macs is not None else r.g.M * r.g.N * r.g.K) for r in recs),
+              [(r.g.M, r.g.N, r.g.K, int(r.g.splitk), int(bool(r.g.R) or r.g.accumulate == 1)) for r in recs], int(got.value))
     return int(got.value)
 
 
-def gemm(A, B, Cout, M, N, K, lda, ldb, ldc, *, bias=None, rowvec=None, rows_per_b=0, R=None, ldr=0,
-         a_mode=A_ROWK, b_mode=B_ROWK, conv=None, dtype=None, out_f32=False, accumulate=False, splitk=1, alpha=1.0,
-         macs=None, colsum_out=None, ldrv=0, epilogue=EPI_NONE, C2=None, ldc2=0, colstat=None, ln=None):
-    # accumulate: False / True / 2 (= split-K slabs, see pdmk.h)
-    # ln = (gamma, beta, stats or None, out or None, eps): LayerNorm(A) in the GEMM's prologue (pdmk_gemm_args.ln_gamma)
-    """conv = (b, hi, wi, ci, ho, wo, mode, ld) or None.  macs: logical (un-padded) multiply-accumulates, profiling only."""
+def _gemm_args(A, B, Cout, M, N, K, lda, ldb, ldc, *, bias=None, rowvec=None, rows_per_b=0, R=None, ldr=0, a_mode=A_ROWK,
+               b_mode=B_ROWK, conv=None, dtype=None, out_f32=False, accumulate=False, splitk=1, alpha=1.0, colsum_out=None,
+               ldrv=0, epilogue=EPI_NONE, C2=None, ldc2=0, colstat=None, ln=None):
+    """The one place a pdmk_gemm_args block is filled (launches, plan and support queries alike).
+    conv = (b, hi, wi, ci, ho, wo, mode, ld) or None; accumulate: False / True / 2 (= split-K slabs, see pdmk.h);
+    colstat = (accumulator [B, 4, cs_ld] int64 limbs, first accumulator column of this output);
+    ln = (gamma, beta, stats or None, out or None, eps): LayerNorm(A) in the GEMM's prologue (pdmk_gemm_args.ln_gamma)."""
     g = GemmArgs()
-    g.colsum_out = _p(colsum_out)
     g.A, g.B, g.C = _p(A), _p(B), _p(Cout)
-    g.bias, g.rowvec, g.R = _p(bias), _p(rowvec), _p(R)
+    g.bias, g.rowvec, g.R, g.colsum_out = _p(bias), _p(rowvec), _p(R), _p(colsum_out)
     g.M, g.N, g.K = M, N, K
     g.lda, g.ldb, g.ldc, g.ldr = lda, ldb, ldc, ldr
     g.rows_per_b, g.ldrv = rows_per_b, ldrv
@@ -269,38 +276,32 @@ def gemm(A, B, Cout, M, N, K, lda, ldb, ldc, *, bias=None, rowvec=None, rows_per
     g.dtype = dt(A) if dtype is None else dtype
     g.out_f32, g.accumulate, g.splitk, g.alpha = int(out_f32), int(accumulate), int(splitk), float(alpha)
     g.epilogue, g.C2, g.ldc2 = int(epilogue), _p(C2), int(ldc2)
-    if colstat is not None:          # (accumulator [B, 4, cs_ld] int64 limbs, first accumulator column of this output)
+    if colstat is not None:
         g.colstat, g.cs_ld, g.cs_col0 = _p(colstat[0]), colstat[0].shape[2], int(colstat[1])
-    _set_ln(g, ln)
-    shape = (M, N, K, int(splitk), int(R is not None or int(accumulate) == 1))     # last: the epilogue also READS an [M, N] tensor
+    if ln is not None:
+        gamma, beta, stats, out, eps = ln
+        g.ln_gamma, g.ln_beta, g.ln_stats, g.ln_out = _p(gamma), _p(beta), _p(stats), _p(out)
+        g.ld_ln_out, g.ln_eps = (0 if out is None else out.stride(0)), float(eps)
+    return g
+
+
+def gemm(A, B, Cout, M, N, K, lda, ldb, ldc, *, macs=None, **kw):
+    """One pdmk_gemm launch (or, while a Recorder is open, one record of a grouped launch).  kw: every keyword of _gemm_args.
+    macs: logical (un-padded) multiply-accumulates, profiling only."""
+    g = _gemm_args(A, B, Cout, M, N, K, lda, ldb, ldc, **kw)
     if RECORD is not None:
-        RECORD.append(Rec(g, macs, keep=(A, B, Cout, bias, rowvec, R, colsum_out, C2, colstat, ln)))
+        RECORD.append(Rec(g, macs, keep=(A, B, Cout, kw)))        # (kw holds every other operand tensor)
         return
-    _launch_gemm(g, macs, shape)
-
-
-def _set_ln(g, ln):
-    if ln is None:
-        return
-    gamma, beta, stats, out, eps = ln
-    g.ln_gamma, g.ln_beta, g.ln_stats, g.ln_out = _p(gamma), _p(beta), _p(stats), _p(out)
-    g.ld_ln_out, g.ln_eps = (0 if out is None else out.stride(0)), float(eps)
+    shape = (M, N, K, g.splitk, int(bool(g.R) or g.accumulate == 1))         # last: the epilogue also READS an [M, N] tensor
+    _chk(_launch_gemm(g, macs, shape), "pdmk_gemm")
 
 
 def gemm_ln_supported(A, B, M, N, K, lda, ldb, *, geglu=False, residual=False, bias=False):
     """Would pdmk_gemm take this Linear with the LayerNorm of its input fused into the prologue (one launch)?  Shape question only:
     the pointers are placeholders."""
-    g = GemmArgs()
-    g.A, g.B, g.C = _p(A), _p(B), _p(A)
-    g.M, g.N, g.K, g.lda, g.ldb, g.ldc = M, N, K, lda, ldb, (N // 2 if geglu else N)
-    g.a_mode, g.b_mode, g.dtype, g.splitk, g.alpha = A_ROWK, B_ROWK, dt(A), 1, 1.0
-    g.epilogue = EPI_GEGLU if geglu else EPI_NONE
-    if residual:
-        g.R, g.ldr = _p(A), N
-    if bias or geglu:
-        g.bias = _p(B)
-    g.ln_gamma = g.ln_beta = _p(B)
-    g.ln_eps = 1e-5
+    g = _gemm_args(A, B, A, M, N, K, lda, ldb, N // 2 if geglu else N, epilogue=EPI_GEGLU if geglu else EPI_NONE,
+                   R=A if residual else None, ldr=N if residual else 0, bias=B if bias or geglu else None,
+                   ln=(B, B, None, None, 1e-5))
     return bool(_lib.pdmk_gemm_ln_supported(C.byref(g)))
 
 
@@ -447,38 +448,22 @@ def candidate_name(a_mode, b_mode, cand):
     return buf.value.decode()
 
 
-def splitk_plan(A, B, M, N, K, lda, ldb, a_mode=A_ROWK, conv=None):
-    """Split-K factor for a forward/dgrad GEMM, from the library's plan cache (tuned on first sight of the shape)."""
-    g = GemmArgs()
-    g.A, g.B = _p(A), _p(B)
-    g.M, g.N, g.K = M, N, K
-    g.lda, g.ldb, g.ldc = lda, ldb, N
-    g.a_mode, g.b_mode = a_mode, B_ROWK
-    if conv is not None:
-        (g.conv_b, g.conv_hi, g.conv_wi, g.conv_ci, g.conv_ho, g.conv_wo, g.conv_mode, g.conv_ld) = conv
-    g.dtype = dt(A)
-    g.splitk, g.alpha = 1, 1.0
+def _plan(g):
     sk = i32(1)
     _chk(_lib.pdmk_gemm_plan(C.byref(g), _st(), C.byref(sk)), "pdmk_gemm_plan")
     return int(sk.value)
+
+
+def splitk_plan(A, B, M, N, K, lda, ldb, a_mode=A_ROWK, conv=None):
+    """Split-K factor for a forward/dgrad GEMM, from the library's plan cache (tuned on first sight of the shape)."""
+    return _plan(_gemm_args(A, B, None, M, N, K, lda, ldb, N, a_mode=a_mode, conv=conv))
 
 
 def wgrad_plan(dy, x, M, N, K, lda, ldb, b_mode=B_COLK, conv=None, slabs=False):
     """Split-K factor for a weight-gradient GEMM dW[M,N] += dy[K,M]^T x[K,N] (both operands reduction-major).
     slabs: the splits will store partial slabs (accumulate = 2) instead of adding with atomics - planned apart."""
-    g = GemmArgs()
-    g.accumulate = 2 if slabs else 0
-    g.A, g.B = _p(dy), _p(x)
-    g.M, g.N, g.K = M, N, K
-    g.lda, g.ldb, g.ldc = lda, ldb, N
-    g.a_mode, g.b_mode = A_COLK, b_mode
-    if conv is not None:
-        (g.conv_b, g.conv_hi, g.conv_wi, g.conv_ci, g.conv_ho, g.conv_wo, g.conv_mode, g.conv_ld) = conv
-    g.dtype = dt(x)
-    g.out_f32, g.splitk, g.alpha = 1, 1, 1.0
-    sk = i32(1)
-    _chk(_lib.pdmk_gemm_plan(C.byref(g), _st(), C.byref(sk)), "pdmk_gemm_plan")
-    return int(sk.value)
+    return _plan(_gemm_args(dy, x, None, M, N, K, lda, ldb, N, a_mode=A_COLK, b_mode=b_mode, conv=conv, dtype=dt(x),
+                            out_f32=True, accumulate=2 if slabs else 0))
 
 
 def gemm_auto(A, B, Cout, M, N, K, lda, ldb, ldc, *, bias=None, rowvec=None, rows_per_b=0, R=None, ldr=0,
@@ -543,26 +528,40 @@ class SlabQueue:
         self.bytes = 0
 
 
+# one weight gradient dW[M, N] (fp32, row stride N) += dy[K, M]^T x[K, N]; colsum_out (or None) += the column sums of dy (the bias
+# gradient); macs: logical multiply-accumulates, profiling only
+WgradItem = namedtuple("WgradItem", "dy x dW M N K lda ldb colsum_out macs")
+
+
+def _slab_ok(it):
+    return (it.M * it.N) % 4 == 0 and it.dW.is_contiguous()
+
+
+def _wgrad_gemm(it, sk, slab, b_mode=B_COLK, conv=None):
+    """The gemm() of one weight gradient at split factor sk.  slab: the splits store their partials with plain stores into a fresh
+    [sk][M][N] workspace - returned as a SlabQueue entry - else they add into dW (in the epilogue when unsplit, with fp32
+    atomics when split)."""
+    out = torch.empty(sk * it.M * it.N, device=it.dy.device, dtype=torch.float32) if slab else it.dW
+    gemm(it.dy, it.x, out, it.M, it.N, it.K, it.lda, it.ldb, it.N, a_mode=A_COLK, b_mode=b_mode, conv=conv, out_f32=True,
+         splitk=sk, accumulate=2 if slab else sk == 1, dtype=dt(it.x), macs=it.macs, colsum_out=it.colsum_out)
+    return (out, it.dW, it.M * it.N, sk) if slab else None
+
+
 def wgrad(dy, x, dW, M, N, K, lda, ldb, *, b_mode=B_COLK, conv=None, colsum_out=None, macs=None, queue=None):
     """dW[M, N] (fp32, row stride N) += dy[K, M]^T x[K, N] (3x3 gather of x for b_mode = B_COLK_CONV), split over the
     pixel dimension K as the planner says.  Without a queue the splits add into dW with fp32 atomics (a slab + finish pass
     PER WEIGHT was measured 4 % slower for the step: one more launch per weight outweighs the atomics).  queue (a
     SlabQueue): the splits store partial slabs with plain stores and the queue adds them into dW at its next flush, many
     weights per launch - no atomics and no per-weight launch."""
-    if queue is not None and (M * N) % 4 == 0 and dW.is_contiguous():
-        sk = wgrad_plan(dy, x, M, N, K, lda, ldb, b_mode, conv, slabs=True)
-        if sk > 1:
-            if queue.full():
-                queue.flush()
-            ws = torch.empty(sk * M * N, device=dy.device, dtype=torch.float32)
-            gemm(dy, x, ws, M, N, K, lda, ldb, N, a_mode=A_COLK, b_mode=b_mode, conv=conv, out_f32=True, splitk=sk,
-                 accumulate=2, dtype=dt(x), macs=macs, colsum_out=colsum_out)
-            queue.add(ws, dW, M * N, sk)
-            return
+    it = WgradItem(dy, x, dW, M, N, K, lda, ldb, colsum_out, macs)
+    slab = queue is not None and _slab_ok(it)
+    sk = wgrad_plan(dy, x, M, N, K, lda, ldb, b_mode, conv, slabs=slab)
+    if slab and sk > 1:
+        if queue.full():
+            queue.flush()
+        queue.add(*_wgrad_gemm(it, sk, True, b_mode, conv))
     else:
-        sk = wgrad_plan(dy, x, M, N, K, lda, ldb, b_mode, conv)
-    gemm(dy, x, dW, M, N, K, lda, ldb, N, a_mode=A_COLK, b_mode=b_mode, conv=conv, out_f32=True, splitk=sk,
-         accumulate=(sk == 1), dtype=dt(x), macs=macs, colsum_out=colsum_out)
+        _wgrad_gemm(it, sk, False, b_mode, conv)
 
 
 _WG_TARGET = int(os.environ.get("PDMK_WG_TARGET", "512"))     # workgroups a block's grouped weight-gradient launch aims for
@@ -575,36 +574,26 @@ def wgrad_group(items, queue, target_wgs=None):
     reduces over the SAME K pixel rows into a small [M, N] output, so one problem alone fills the 256 CUs only by cutting its
     reduction into 16-32 splits (16 K-steps each behind a cold prologue, 16-32 slabs to add); together the problems have the
     tiles, so they share ONE split factor chosen for the group (>= _WG_MINK K-steps per split) and one launch.
-    items: (dy, x, dW, M, N, K, lda, ldb, colsum_out, macs) with dW fp32 [M, N] contiguous; the splits of a reduction store their
-    slabs for `queue` (a SlabQueue) to add later.  Problems the grouped kernels do not take go out one by one (same results)."""
-    items = list(items)
+    items: WgradItem (or plain tuples in its field order) with dW contiguous; the splits of a reduction store their slabs for
+    `queue` (a SlabQueue) to add later.  Problems the grouped kernels do not take go out one by one (same results)."""
+    items = [WgradItem(*it) for it in items]
     while items:
-        K = items[0][5]
-        same = [it for it in items if it[5] == K][:GROUP_MAX]
+        K = items[0].K
+        same = [it for it in items if it.K == K][:GROUP_MAX]
         items = [it for it in items if not any(it is s_ for s_ in same)]
-        tiles = sum(((it[3] + 127) // 128) * ((it[4] + 127) // 128) for it in same)
-        nk = max(1, K // 64)
-        sk = max(1, min((target_wgs or _WG_TARGET) // max(tiles, 1), nk // _WG_MINK, 64))
         if len(same) == 1 or queue is None:
-            for dy, x, dW, M, N, K_, lda, ldb, cs, macs in same:
-                wgrad(dy, x, dW, M, N, K_, lda, ldb, colsum_out=cs, macs=macs, queue=queue)
+            for it in same:
+                wgrad(*it[:8], colsum_out=it.colsum_out, macs=it.macs, queue=queue)
             continue
+        tiles = sum(((it.M + 127) // 128) * ((it.N + 127) // 128) for it in same)
+        sk = max(1, min((target_wgs or _WG_TARGET) // max(tiles, 1), max(1, K // 64) // _WG_MINK, 64))
         with Recorder() as r:
-            slabs = []
-            for dy, x, dW, M, N, K_, lda, ldb, cs, macs in same:
-                if sk > 1 and (M * N) % 4 == 0 and dW.is_contiguous():
-                    ws = torch.empty(sk * M * N, device=dy.device, dtype=torch.float32)
-                    gemm(dy, x, ws, M, N, K_, lda, ldb, N, a_mode=A_COLK, b_mode=B_COLK, out_f32=True, splitk=sk, accumulate=2,
-                         dtype=dt(x), macs=macs, colsum_out=cs)
-                    slabs.append((ws, dW, M * N, sk))
-                else:       # unsplit: added into the gradient in the epilogue
-                    gemm(dy, x, dW, M, N, K_, lda, ldb, N, a_mode=A_COLK, b_mode=B_COLK, out_f32=True, splitk=1,
-                         accumulate=True, dtype=dt(x), macs=macs, colsum_out=cs)
+            slabs = [_wgrad_gemm(it, sk, True) if sk > 1 and _slab_ok(it) else _wgrad_gemm(it, 1, False) for it in same]
         gemm_group(r.recs)
-        for ws, dW, n, nslab in slabs:
+        for slab in filter(None, slabs):
             if queue.full():
                 queue.flush()
-            queue.add(ws, dW, n, nslab)
+            queue.add(*slab)
 
 
 def groupnorm_apply_colstat(x, y, gamma, beta, stats, colstat, col0, B, HW, Cc, ldx, ldy, G, gs, eps, silu):
@@ -730,41 +719,24 @@ def geglu_bwd(x, dy, dx, M, Fd, ldx, lddy, lddx, layout=0):
 _GEGLU_REFUSED = set()     # (M, N, K) the library has no fused GEGLU kernel for (learnt from eager calls: status -2)
 
 
-def _launch_gemm_geglu(g, macs):
-    if PROFILE is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    rc = _lib.pdmk_gemm(C.byref(g), _st())
-    if rc == -2:
-        if not g.ln_gamma:
-            _GEGLU_REFUSED.add((g.M, g.N, g.K))
-        return False
-    _chk(rc, "pdmk_gemm[geglu]")
-    if PROFILE is not None:
-        e1.record()
-        PROFILE.append((("bf16", A_ROWK, B_ROWK, _lib.pdmk_gemm_last_candidate()), 2.0 * (macs if macs is not None else g.M * g.N * g.K),
-                        e0, e1, (g.M, g.N, g.K, 1)))
-    return True
-
-
 def gemm_geglu(A, B, gl, f, M, N, K, lda, ldb, *, bias=None, macs=None, ln=None):
     """gl[M, N/2] = GEGLU(A @ B^T + bias) in the GEMM's epilogue, (hidden, gate) columns interleaved in blocks of 8; f (or
     None) receives the [M, N] pre-activation for the backward.  Returns False when the library has no fused kernel for
     the shape (status -2) - the caller then runs the projection and pdmk_geglu_fwd(layout=1) as two passes."""
     if (M, N, K) in _GEGLU_REFUSED:
         return False
-    g = GemmArgs()
-    g.A, g.B, g.C, g.bias = _p(A), _p(B), _p(gl), _p(bias)
-    g.M, g.N, g.K = M, N, K
-    g.lda, g.ldb, g.ldc = lda, ldb, gl.stride(0)
-    g.a_mode, g.b_mode, g.dtype = A_ROWK, B_ROWK, dt(A)
-    g.splitk, g.alpha = 1, 1.0
-    g.epilogue, g.C2, g.ldc2 = EPI_GEGLU, _p(f), 0 if f is None else f.stride(0)
-    _set_ln(g, ln)
+    g = _gemm_args(A, B, gl, M, N, K, lda, ldb, gl.stride(0), bias=bias, epilogue=EPI_GEGLU, C2=f,
+                   ldc2=0 if f is None else f.stride(0), ln=ln)
     if RECORD is not None:      # a member of a grouped launch: the library answers for the whole group (pdmk_gemm_group)
         RECORD.append(Rec(g, macs, keep=(A, B, gl, f, bias, ln)))
         return True
-    return _launch_gemm_geglu(g, macs)
+    rc = _launch_gemm(g, macs, (M, N, K, 1))
+    if rc == -2:
+        if ln is None:
+            _GEGLU_REFUSED.add((M, N, K))
+        return False
+    _chk(rc, "pdmk_gemm[geglu]")
+    return True
 
 
 def gemm_geglu_bwd(dy, wt, pre, dpre, M, N, K, lddy, ldwt, *, macs=None):
@@ -772,25 +744,11 @@ def gemm_geglu_bwd(dy, wt, pre, dpre, M, N, K, lddy, ldwt, *, macs=None):
     Linear that consumed hidden * gelu(gate): (dy @ wt^T) pushed through GEGLU's backward in the GEMM's epilogue
     (PDMK_EPI_GEGLU_BWD).  Returns False when the library has no fused kernel for the shape (the caller then runs the plain
     input-gradient GEMM and pdmk_geglu_bwd)."""
-    g = GemmArgs()
-    g.A, g.B, g.C, g.C2 = _p(dy), _p(wt), _p(dpre), _p(pre)
-    g.M, g.N, g.K = M, N, K
-    g.lda, g.ldb, g.ldc, g.ldc2 = lddy, ldwt, dpre.stride(0), pre.stride(0)
-    g.a_mode, g.b_mode, g.dtype = A_ROWK, B_ROWK, dt(dy)
-    g.splitk, g.alpha = 1, 1.0
-    g.epilogue = EPI_GEGLU_BWD
-    if PROFILE is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    rc = _lib.pdmk_gemm(C.byref(g), _st())
-    if rc == -2:
-        return False
-    _chk(rc, "pdmk_gemm[geglu_bwd]")
-    if PROFILE is not None:
-        e1.record()
-        PROFILE.append((("bf16", A_ROWK, B_ROWK, _lib.pdmk_gemm_last_candidate()), 2.0 * (macs if macs is not None else M * N * K),
-                        e0, e1, (M, N, K, 1)))
-    return True
+    g = _gemm_args(dy, wt, dpre, M, N, K, lddy, ldwt, dpre.stride(0), epilogue=EPI_GEGLU_BWD, C2=pre, ldc2=pre.stride(0))
+    rc = _launch_gemm(g, macs, (M, N, K, 1))
+    if rc != -2:
+        _chk(rc, "pdmk_gemm[geglu_bwd]")
+    return rc == 0
 
 
 def quantize_e4m3_(x):

@@ -3,12 +3,14 @@
 Activations are token-major / NHWC 2-D matrices [rows, C] (`Act`), so conv outputs feed Linear GEMMs and back without any
 layout change.  With `train` set every op appends its backward closure to a tape; `backward()` replays the tape in reverse.
 Gradients w.r.t. parameters are ACCUMULATED into the fp32 grad arena (zeroed by the fused AdamW).  Gradient fan-in
-(residuals, skip connections, a shared operand) is done in GEMM / norm epilogues (accumulate flags) or by aliasing a finished
-gradient buffer - there are no standalone "add" passes on the hot path.
+(residuals, skip connections, a shared operand) is owned by the gradient slot of `Act`: a kernel asks `dst()` where to write
+and whether to accumulate, a finished buffer arrives through `give()`; the sums happen in GEMM / norm epilogues (accumulate
+flags, addend ports) or by aliasing a finished buffer - there are no standalone "add" passes on the hot path.
 `Ops(store, dtype)` alone is the inference configuration the VAE and both CLIP towers use; the U-Net's dataflow and its
 training switches are `unet.engine.UNetEngine(Ops)`.  Every attribute a method here reads is set by `Ops.__init__`.
 """
 import os
+from collections import namedtuple
 
 import torch
 
@@ -16,41 +18,96 @@ from .. import _pdmk as k
 
 
 class Act:
-    """A 2-D activation [rows, cols] (row stride = t.stride(0)) and its gradient (same logical shape).
-    pend: a second finished gradient buffer waiting to be added to `g` (the residual branch's, blocks.py:379).  Reading
-    `.g` adds it first (one strided accumulate pass); the GroupNorm backward of the same tensor - the usual next writer -
-    takes it as an extra addend of its own store instead, so the fan-in normally costs no pass at all."""
-    __slots__ = ("t", "_g", "rg", "pend", "src", "cs", "parked")
+    """A 2-D activation [rows, cols] (row stride = t.stride(0)) and the slot of its gradient (same logical shape).  The slot is
+      empty   no gradient yet;
+      owned   a buffer this Act may accumulate into - one a kernel wrote for it, or a finished buffer handed over by give()
+              (ownership moves with it: the ResBlock residual is summed in place, which saves a pass);
+      lent    a finished buffer a deferred weight gradient (Ops._wg_items) still reads: it may be read and passed as a kernel's
+              addend, it is NEVER written - whatever would write it gets a private copy first (one copy2d) - until release();
+      and an owned slot may carry a pending addend: a second finished buffer (the residual branch's, blocks.py:379) that the
+      next GroupNorm / LayerNorm backward of this tensor folds into its own store (dst(port=True)) - so the fan-in normally costs
+      no pass at all - or that the next read of `.g` adds (one strided accumulate pass)."""
+    __slots__ = ("t", "rg", "src", "cs", "_g", "_add", "_lent")
 
     def __init__(self, t, rg=True):
-        self.t, self._g, self.rg, self.pend = t, None, rg, None
-        self.parked = False  # pend is a buffer a deferred (grouped) weight gradient still reads: it must not be updated in place
+        self.t, self.rg, self._g, self._add, self._lent = t, rg, None, None, False
         self.cs = None       # (accumulator [B, 2, ld], first column, columns covered): per-(image, column) sums of this tensor from
                              # its producers' epilogues (pdmk_gemm_args.colstat) - the GroupNorm that reads it skips its statistics pass
         self.src = None      # a GEGLU output: (pre-activation tensor, the projection's Act) - its consumer's input gradient can be
                              # pushed through GEGLU's backward in the GEMM epilogue (PDMK_EPI_GEGLU_BWD)
 
-    def flush(self):
-        if self.pend is not None:
-            p_, self.pend = self.pend, None
-            if self._g is None:          # parked first gradient and nothing else arrived: it IS the gradient (read-only from here on)
-                self._g = p_
-                return
-            k.copy2d(p_, self._g, p_.shape[0], p_.shape[1], p_.stride(0), self._g.stride(0), accumulate=True)
+    @property
+    def empty(self):
+        """No gradient has arrived yet (nothing was written, given or seeded)."""
+        return self._g is None
 
     @property
     def g(self):
-        self.flush()
+        """The gradient, complete as far as the tape has run (a pending addend is added first).  A lent buffer is returned as it
+        is - for reading."""
+        self._fold()
         return self._g
 
     @g.setter
     def g(self, v):
-        assert self.pend is None
+        assert self._add is None and not self._lent
         self._g = v
+
+    def _fold(self):
+        if self._add is not None:
+            a, self._add = self._add, None
+            k.copy2d(a, self._g, a.shape[0], a.shape[1], a.stride(0), self._g.stride(0), accumulate=True)
+
+    def _own(self):
+        """lent -> owned: the private copy a writer needs (the lent buffer stays as the deferred weight gradient reads it)."""
+        if self._lent:
+            src, self._lent = self._g, False
+            self._g = torch.empty(src.shape, device=src.device, dtype=self.t.dtype)
+            k.copy2d(src, self._g, src.shape[0], src.shape[1], src.stride(0), self._g.stride(0))
+
+    def dst(self, port=False):
+        """Where a kernel writes d(self): (buffer, accumulate, addend).  port: the kernel can add a second tensor in the same
+        store - it gets the pending addend, or the lent buffer (then it writes a fresh one); without a port addend is None."""
+        add = None
+        if port:
+            add, self._add = self._add, None
+            if self._lent:
+                add, self._g, self._lent = self._g, None, False
+        else:
+            self._own()
+        if self._g is None:
+            self._g = torch.empty(self.t.shape, device=self.t.device, dtype=self.t.dtype)
+            return self._g, False, add
+        self._fold()
+        return self._g, True, add
+
+    def give(self, dy, lend=False, defer=False):
+        """self.g += dy where dy is a finished gradient buffer: taken over when the slot is empty (lend: as a LENT buffer - dy
+        is also the operand of a deferred weight gradient), else added - as the pending addend (defer) or by one accumulate pass."""
+        if not self.rg:
+            return
+        if self._g is None:
+            self._g, self._lent = dy, lend
+            return
+        self._own()             # a second finished gradient at a lent one: the sum gets a buffer of its own
+        if defer and dy.dtype == self._g.dtype:
+            self._fold()        # (an earlier pending addend goes in first)
+            self._add = dy
+        else:
+            k.copy2d(dy, self._g, dy.shape[0], dy.shape[1], dy.stride(0), self._g.stride(0), accumulate=True)
+
+    def release(self):
+        """The launch that read the lent buffer has been issued: from here on it is owned like any handed-over buffer."""
+        self._lent = False
 
 
 def _ld(t):
     return t.stride(0)
+
+
+# what the backward of one Linear call needs: weight and bias keys, shape, x = the input Act as the GEMM read it, out = the Act of
+# the [M, N] output, the residual Act or None, the logical multiply-accumulates
+_Lin = namedtuple("_Lin", "key bias M N K x out residual macs")
 
 
 class Ops:
@@ -69,6 +126,7 @@ class Ops:
         self.partials, self.slabs = partials, slabs              # k.PartialQueue / k.SlabQueue, or None: nothing deferred
         self.up2, self.gn_epi, self.group_wgrad, self.attn_fp8 = up2, gn_epi, group_wgrad, attn_fp8
         self._wg_items = None          # a list while Linear weight gradients are being collected for one grouped launch
+        self._wg_lent = []             # the Acts that hold a dy of those items as a lent buffer
         self.gn_count, self.gn_miss = [0, 0], None
         self._cs_arena, self._cs_off, self._cs_need, self._cs_max, self._cs_old = None, 0, 0, 0, []
         self._cs_views, self._cs_cats = {}, {}
@@ -77,56 +135,31 @@ class Ops:
     def _empty(self, rows, cols, dtype=None):
         return torch.empty((rows, cols), device=self.dev, dtype=dtype or self.dtype)
 
-    def _grad_into(self, act, rows, cols, absorb=False):
-        """Returns (tensor, accumulate) for writing d(act); with absorb=True (tensor, accumulate, addend): the caller's
-        kernel also adds `addend` (a pending residual gradient, or None) in the same store."""
-        add = None
-        if absorb:
-            add, act.pend = act.pend, None
-        elif act._g is None and act.pend is not None:
-            # a parked gradient met a writer that cannot take an addend: it gets a private copy to accumulate into (the parked
-            # buffer itself stays as the deferred weight gradient reads it)
-            p_, act.pend = act.pend, None
-            act.g = self._empty(rows, cols, act.t.dtype)
-            k.copy2d(p_, act._g, rows, cols, _ld(p_), _ld(act._g))
-            return act._g, True
-        if act._g is None:
-            act.g = self._empty(rows, cols, act.t.dtype)
-            return (act._g, False, add) if absorb else (act._g, False)
-        act.flush()
-        return (act._g, True, add) if absorb else (act._g, True)
+    def _give(self, act, dy, lend=False):
+        """act.g += the finished buffer dy (Act.give); lend: dy is an operand of a weight gradient waiting in _wg_items."""
+        act.give(dy, lend, self.defer_fanin)
+        if lend:
+            self._wg_lent.append(act)
 
-    def _give(self, act, dy, park=False):
-        """act.g += dy where dy is a finished gradient buffer: aliased when act has no gradient yet, else parked as the
-        pending addend (folded in by the next GroupNorm / LayerNorm backward of act, or on the next read of act.g).
-        park: dy is also the operand of a DEFERRED weight gradient (_wg_items): never aliased as a buffer later kernels accumulate
-        into - it waits as the pending addend even when it is the first gradient to arrive."""
-        if not act.rg:
-            return
-        if act._g is None and act.pend is not None:
-            # a parked first gradient and now a second finished one (no topology of the shipped recipes does this): the sum gets a
-            # buffer of its own - neither finished buffer may be written
-            p_, act.pend = act.pend, None
-            act.g = self._empty(p_.shape[0], p_.shape[1], act.t.dtype)
-            k.copy2d(p_, act._g, p_.shape[0], p_.shape[1], _ld(p_), _ld(act._g))
-        if act._g is None and park:
-            act.pend = dy
-            act.parked = True
-        elif act._g is None:
-            act.g = dy
-        elif self.defer_fanin and dy.dtype == act._g.dtype:
-            act.flush()
-            act.pend = dy
-        else:
-            k.copy2d(dy, act._g, dy.shape[0], dy.shape[1], _ld(dy), _ld(act._g), accumulate=True)
+    def _wg_open(self):
+        """From here on the Linear weight gradients are collected (a transformer block's backward starts)."""
+        self._wg_items = []
+
+    def _wg_flush(self, reopen=False):
+        """One grouped launch for what was collected; the buffers it reads are no longer lent."""
+        items, self._wg_items = self._wg_items, [] if reopen else None
+        if items:
+            k.wgrad_group(items, self.slabs)
+        for act in self._wg_lent:
+            act.release()
+        self._wg_lent = []
 
     def flush_pending(self):
         """Deferred norm-affine gradient reductions (PartialQueue): after this every gradient the tape has produced so far is
         final in the arena.  Called by whoever consumes gradients mid-backward (bucketed all-reduce, streamed AdamW, graph
         cut) and at the end of backward()."""
         if self._wg_items:          # (a consumer in the middle of a transformer block: what was collected so far goes out now)
-            items, self._wg_items = self._wg_items, []
-            k.wgrad_group(items, self.slabs)
+            self._wg_flush(reopen=True)
         if self.partials is not None:
             self.partials.flush()
         if self.slabs is not None:
@@ -141,138 +174,148 @@ class Ops:
         out: optional [M, N] view (any row stride) to write into instead of a fresh tensor (concat buffers).
         geglu: the projection is GEGLU's (blocks.py:44-59; weight rows packed (hidden, gate)-interleaved, params.py): returns
         hidden * gelu(gate) [M, N/2], computed in the GEMM's epilogue where the library has the fused kernel (bf16 ring
-        kernels; the pre-activation is then only written when a backward pass will need it), else as a second pass."""
+        kernels; the pre-activation is then only written when a backward pass will need it), else as a second pass.
+        The form is decided here, once: skinny, LayerNorm prologue, fused GEGLU (_lin_geglu) or planned (_lin_planned) forward,
+        and _lin_bwd_skinny or _lin_bwd_tiled on the tape."""
         P = self.P
         e = P.by_key[key + ".weight"]
-        Np, Kp = e.shape
+        N, K = e.shape
         M = x.t.shape[0]
-        assert x.t.shape[1] == Kp, f"{key}: input has {x.t.shape[1]} cols, weight expects {Kp}"
-        y = out if out is not None else self._empty(M, Np, torch.float32 if out_f32 else None)
-        assert tuple(y.shape) == (M, Np)
-        # time-embedding MLP / batched time_emb_proj: M = batch rows -> weight-streaming kernels (skinny operand in LDS)
-        skinny = M <= 16 and residual is None and (8 if M <= 8 else 16) * Kp * 4 + 512 <= 65536
-        skinny_dgrad = skinny and (8 if M <= 8 else 16) * Np * 4 + 512 <= 65536
-        a_t, ln_args, ln_src = x.t, None, None             # forward A operand; the LayerNorm prologue of the GEMM, its input Act
-        if ln is not None:
-            take = (self.fuse_ln and self.dtype == torch.bfloat16 and not skinny and residual is None and out is None and
-                    not out_f32 and cs is None and (self.fuse_ln >= 2 or Kp <= 320) and
-                    k.gemm_ln_supported(x.t, P.wv(key + ".weight"), M, Np, Kp, _ld(x.t), Kp, geglu=geglu, bias=bool(bias)))
-            if not take:
-                x = self.layernorm(x, ln)
-                a_t = x.t
-            else:
-                ln_src = x
-                st_ = torch.empty((M, 2), device=self.dev, dtype=torch.float32) if self.train else None
-                lno = self._empty(M, Kp) if self.train else None
-                ln_args = (P.p(ln + ".weight"), P.p(ln + ".bias"), st_, lno, 1e-5)
-                x = Act(lno)                                 # what the backward pass sees as this Linear's input
-                if self.train:
-                    lnw, src = P.p(ln + ".weight"), ln_src
-
-                    def lnbwd():                             # runs AFTER this Linear's backward (appended before it)
-                        dx, acc_, add = self._grad_into(src, M, Kp, absorb=True)
-                        k.layernorm_bwd(src.t, x.g, dx, lnw, st_, P.g(ln + ".weight"), P.g(ln + ".bias"), M, Kp, _ld(src.t),
-                                        _ld(x.g), _ld(dx), acc_, queue=self.partials, add=add)
-                    self.tape.append(lnbwd)
-        gl = None
-        acc, acc_ok = None, False       # GroupNorm statistics out of this GEMM's epilogue (cs): the accumulator slice, and whether it was fed
-        if geglu:
-            assert residual is None and out is None and not out_f32
-            gl = self._empty(M, Np // 2)
-            fused = (self.fuse_geglu and not skinny and self.dtype == torch.bfloat16 and
-                     (ln_args is not None or k.splitk_plan(a_t, P.wv(key + ".weight"), M, Np, Kp, _ld(a_t), Kp) == 1))
-            if fused:
-                if not self.train:
-                    y = None                    # inference (teacher): the [M, N] pre-activation never reaches memory
-                fused = k.gemm_geglu(a_t, P.wv(key + ".weight"), gl, y, M, Np, Kp, _ld(a_t), Kp,
-                                     bias=P.p(bias) if bias else None, macs=M * e.logical[0] * e.logical[1], ln=ln_args)
-                assert fused or ln_args is None, "pdmk_gemm_ln_supported said yes"
-                if not fused and y is None:
-                    y = self._empty(M, Np)
-        if geglu and fused:
-            pass
-        elif ln_args is not None:      # LayerNorm prologue: one kernel family, no plan to make
-            k.gemm(a_t, P.wv(key + ".weight"), y, M, Np, Kp, _ld(a_t), Kp, _ld(y), bias=P.p(bias) if bias else None,
-                   macs=M * e.logical[0] * e.logical[1], ln=ln_args)
-        elif skinny:
-            k.skinny_gemm(x.t, P.wv(key + ".weight"), y, M, Np, Kp, _ld(x.t), Kp, _ld(y), bias=P.p(bias) if bias else None)
-        else:
-            # cs = (B, rows per image): a GroupNorm reads this output next - its statistics come out of this epilogue
-            acc = self._cs_for(y, cs[0], cs[1], M, Np, view=out is not None) if (cs is not None and not out_f32) else None
-            got = (k.gemm if out_f32 else k.gemm_auto)(
-                x.t, P.wv(key + ".weight"), y, M, Np, Kp, _ld(x.t), Kp, _ld(y), bias=P.p(bias) if bias else None,
-                R=residual.t if residual else None, ldr=_ld(residual.t) if residual else 0,
-                macs=M * e.logical[0] * e.logical[1],
-                **({"out_f32": True} if out_f32 else ({"colstat": acc, "rows_per_b": cs[1]} if acc is not None else {})))
-            acc_ok = acc is not None and bool(got)
-        lmacs = M * e.logical[0] * e.logical[1]
+        assert x.t.shape[1] == K, f"{key}: input has {x.t.shape[1]} cols, weight expects {K}"
+        assert not geglu or (residual is None and out is None and not out_f32)
+        y = out if out is not None else self._empty(M, N, torch.float32 if out_f32 else None)
+        assert tuple(y.shape) == (M, N)
+        w, b = P.wv(key + ".weight"), (P.p(bias) if bias else None)
+        macs = M * e.logical[0] * e.logical[1]          # logical (un-pruned-padding) multiply-accumulates
         if self.count_macs:
-            self.macs += lmacs
-        if geglu and not fused:
-            k.geglu_fwd(y, gl, M, Np // 2, _ld(y), Np // 2, layout=1)
+            self.macs += macs
+        # time-embedding MLP / batched time_emb_proj: M = batch rows -> weight-streaming kernels (skinny operand in LDS)
+        skinny = M <= 16 and residual is None and (8 if M <= 8 else 16) * K * 4 + 512 <= 65536
+        a, ln_args = x.t, None             # forward A operand; the LayerNorm prologue of the GEMM
+        if ln is not None:
+            if (self.fuse_ln and self.dtype == torch.bfloat16 and not skinny and residual is None and out is None and
+                    not out_f32 and cs is None and (self.fuse_ln >= 2 or K <= 320) and
+                    k.gemm_ln_supported(a, w, M, N, K, _ld(a), K, geglu=geglu, bias=bool(bias))):
+                x, ln_args = self._ln_prologue(x, ln)
+            else:
+                x = self.layernorm(x, ln)
+                a = x.t
+        c = _Lin(key, bias, M, N, K, x, None, residual, macs)
+        gl, acc = (self._empty(M, N // 2) if geglu else None), None
+        # fused GEGLU where configuration and plan allow it; the library may still refuse the shape: two passes then
+        if (geglu and self.fuse_geglu and not skinny and self.dtype == torch.bfloat16 and
+                (ln_args is not None or k.splitk_plan(a, w, M, N, K, _ld(a), K) == 1) and self._lin_geglu(c, a, w, b, gl, y, ln_args)):
+            if not self.train:
+                y = None                        # inference (teacher): the [M, N] pre-activation never reached memory
+        else:
+            if ln_args is not None:             # LayerNorm prologue: one kernel family, no plan to make
+                k.gemm(a, w, y, M, N, K, _ld(a), K, _ld(y), bias=b, macs=macs, ln=ln_args)
+            elif skinny:
+                k.skinny_gemm(a, w, y, M, N, K, _ld(a), K, _ld(y), bias=b)
+            else:
+                acc = self._lin_planned(c, a, w, b, y, out_f32, cs, out is not None)
+            if geglu:
+                k.geglu_fwd(y, gl, M, N // 2, _ld(y), N // 2, layout=1)
         out = Act(y)
-        if acc_ok:
-            out.cs = (acc[0], acc[1], Np)
+        c = c._replace(out=out)
+        if acc is not None:
+            out.cs = (acc[0], acc[1], N)
         if self.train:
-            def bwd():
-                dy = out.g
-                if skinny:
-                    xt = x.t
-                    k.skinny_wgrad(dy, xt, P.g(key + ".weight"), P.g(bias) if bias else None, M, Np, Kp, _ld(dy),
-                                   _ld(xt), Kp)
-                    if x.rg and skinny_dgrad:
-                        dx, acc = self._grad_into(x, M, Kp)
-                        k.skinny_gemm(dy, P.wtv(key + ".weight"), dx, M, Kp, Np, _ld(dy), Np, _ld(dx), accumulate=acc)
-                    elif x.rg:            # wide projection (all time_emb_proj at once): dy does not fit LDS -> tiled GEMM
-                        dyc = dy
-                        if dy.dtype != self.dtype:
-                            dyc = self._empty(M, Np)
-                            k.cast_permute(dy, dyc, M * Np, 1, 1, 0)
-                        dx, acc = self._grad_into(x, M, Kp)
-                        k.gemm_auto(dyc, P.wtv(key + ".weight"), dx, M, Kp, Np, Np, Np, _ld(dx), accumulate=acc, macs=lmacs)
-                    return
-                if dy.dtype != self.dtype:        # fp32 output (time-embedding projections): tiny cast for the GEMMs
-                    dyc = self._empty(M, Np)
-                    k.cast_permute(dy, dyc, M * Np, 1, 1, 0)
-                    dy = dyc
-                xt = x.t
-                collect = self._wg_items is not None
-                if collect:      # inside a transformer block: the weight gradient joins the block's grouped launch (dy and xt
-                    # stay referenced - and unmodified, see _give(park=True) - until _wg_flush)
-                    self._wg_items.append((dy, xt, P.g(key + ".weight"), Np, Kp, M, _ld(dy), _ld(xt),
-                                           P.g(bias) if bias else None, lmacs))
-                else:
-                    k.wgrad(dy, xt, P.g(key + ".weight"), Np, Kp, M, _ld(dy), _ld(xt), macs=lmacs,
-                            colsum_out=P.g(bias) if bias else None,   # bias gradient fused in
-                            queue=self.slabs)
-                fused_g = False
-                if (x.rg and x.src is not None and x._g is None and self.fuse_geglu_bwd and self.dtype == torch.bfloat16 and
-                        k.splitk_plan(dy, P.wtv(key + ".weight"), M, Kp, Np, _ld(dy), Np) == 1):
-                    pre, proj = x.src          # gradient of the GEGLU pre-activation straight from this GEMM's epilogue
-                    dpre = self._empty(M, 2 * Kp)
-                    fused_g = k.gemm_geglu_bwd(dy, P.wtv(key + ".weight"), pre, dpre, M, Kp, Np, _ld(dy), Np, macs=lmacs)
-                    if fused_g:
-                        proj.g = dpre
-                if x.rg and not fused_g:
-                    dx, acc = self._grad_into(x, M, Kp)
-                    k.gemm_auto(dy, P.wtv(key + ".weight"), dx, M, Kp, Np, _ld(dy), Np, _ld(dx), accumulate=acc,
-                                macs=lmacs)
-                if residual is not None:
-                    self._give(residual, out.g, park=collect)
-            self.tape.append(bwd)
-        if geglu:
-            act = Act(gl)
-            if self.train:
-                act.src = (y, out)
+            self.tape.append((lambda: self._lin_bwd_skinny(c)) if skinny else (lambda: self._lin_bwd_tiled(c)))
+        if not geglu:
+            return out
+        act = Act(gl)
+        if self.train:
+            act.src = (y, out)
 
-                def gbwd():               # runs BEFORE the projection's own backward: d(pre-activation) from d(gl)
-                    if out._g is not None:        # already produced by the consumer's fused epilogue (PDMK_EPI_GEGLU_BWD)
-                        return
-                    out.g = self._empty(M, Np)
-                    k.geglu_bwd(y, act.g, out.g, M, Np // 2, _ld(y), _ld(act.g), Np, layout=1)
-                self.tape.append(gbwd)
-            return act
-        return out
+            def gbwd():               # runs BEFORE the projection's own backward: d(pre-activation) from d(gl)
+                if out.empty:         # else: already produced by the consumer's fused epilogue (PDMK_EPI_GEGLU_BWD)
+                    out.g = self._empty(M, N)
+                    k.geglu_bwd(y, act.g, out.g, M, N // 2, _ld(y), _ld(act.g), N, layout=1)
+            self.tape.append(gbwd)
+        return act
+
+    def _ln_prologue(self, src, ln):
+        """The LayerNorm `ln` of src leaves with the GEMM that reads it: returns (the Act the Linear's backward sees as its input,
+        the ln tuple of k.gemm).  The normalised rows and the statistics are written only for a backward pass."""
+        P = self.P
+        M, K = src.t.shape
+        st_ = torch.empty((M, 2), device=self.dev, dtype=torch.float32) if self.train else None
+        x = Act(self._empty(M, K) if self.train else None)
+        if self.train:
+            def lnbwd():                             # runs AFTER the Linear's backward (appended before it)
+                dx, acc, add = src.dst(port=True)
+                k.layernorm_bwd(src.t, x.g, dx, P.p(ln + ".weight"), st_, P.g(ln + ".weight"), P.g(ln + ".bias"), M, K, _ld(src.t),
+                                _ld(x.g), _ld(dx), acc, queue=self.partials, add=add)
+            self.tape.append(lnbwd)
+        return x, (P.p(ln + ".weight"), P.p(ln + ".bias"), st_, x.t, 1e-5)
+
+    def _lin_geglu(self, c, a, w, b, gl, y, ln_args):
+        """Fused GEGLU epilogue (with or without the LayerNorm prologue): gl and, when training, the pre-activation y are written
+        by one launch.  False: the library has no fused kernel for the shape, nothing was launched."""
+        fused = k.gemm_geglu(a, w, gl, y if self.train else None, c.M, c.N, c.K, _ld(a), c.K, bias=b, macs=c.macs, ln=ln_args)
+        assert fused or ln_args is None, "pdmk_gemm_ln_supported said yes"
+        return fused
+
+    def _lin_planned(self, c, a, w, b, y, out_f32, cs, view):
+        """Planned GEMM (+ bias, residual).  cs = (B, rows per image): a GroupNorm reads this output next - its statistics come
+        out of this epilogue; returns their (accumulator, first column) when they were fed, else None."""
+        R, ldr = (c.residual.t, _ld(c.residual.t)) if c.residual else (None, 0)
+        if out_f32:
+            k.gemm(a, w, y, c.M, c.N, c.K, _ld(a), c.K, _ld(y), bias=b, R=R, ldr=ldr, macs=c.macs, out_f32=True)
+            return None
+        acc = self._cs_for(y, cs[0], cs[1], c.M, c.N, view=view) if cs is not None else None
+        got = k.gemm_auto(a, w, y, c.M, c.N, c.K, _ld(a), c.K, _ld(y), bias=b, R=R, ldr=ldr, macs=c.macs,
+                          **({"colstat": acc, "rows_per_b": cs[1]} if acc is not None else {}))
+        return acc if got else None
+
+    def _lin_bwd_skinny(self, c):
+        P, M, N, K, x = self.P, c.M, c.N, c.K, c.x
+        dy = c.out.g
+        k.skinny_wgrad(dy, x.t, P.g(c.key + ".weight"), P.g(c.bias) if c.bias else None, M, N, K, _ld(dy), _ld(x.t), K)
+        if not x.rg:
+            return
+        wt = P.wtv(c.key + ".weight")
+        if (8 if M <= 8 else 16) * N * 4 + 512 <= 65536:      # dy fits LDS too
+            dx, acc, _ = x.dst()
+            k.skinny_gemm(dy, wt, dx, M, K, N, _ld(dy), N, _ld(dx), accumulate=acc)
+        else:                     # wide projection (all time_emb_proj at once): dy does not fit LDS -> tiled GEMM
+            dy = self._as_dtype(dy, M, N)
+            dx, acc, _ = x.dst()
+            k.gemm_auto(dy, wt, dx, M, K, N, N, N, _ld(dx), accumulate=acc, macs=c.macs)
+
+    def _as_dtype(self, dy, M, N):
+        """dy in the compute dtype (fp32 outputs - the time-embedding projections: a tiny cast for the GEMMs)."""
+        if dy.dtype == self.dtype:
+            return dy
+        dyc = self._empty(M, N)
+        k.cast_permute(dy, dyc, M * N, 1, 1, 0)
+        return dyc
+
+    def _lin_bwd_tiled(self, c):
+        P, M, N, K, x = self.P, c.M, c.N, c.K, c.x
+        dy = self._as_dtype(c.out.g, M, N)
+        wt = P.wtv(c.key + ".weight")
+        item = k.WgradItem(dy=dy, x=x.t, dW=P.g(c.key + ".weight"), M=N, N=K, K=M, lda=_ld(dy), ldb=_ld(x.t),
+                           colsum_out=P.g(c.bias) if c.bias else None, macs=c.macs)     # (the bias gradient is fused in)
+        collect = self._wg_items is not None
+        if collect:      # inside a transformer block: the weight gradient joins the block's grouped launch (dy and x.t stay
+            self._wg_items.append(item)        # referenced - and unmodified: dy is LENT to the residual below - until _wg_flush)
+        else:
+            k.wgrad(*item[:8], colsum_out=item.colsum_out, macs=item.macs, queue=self.slabs)
+        fused = False
+        if (x.rg and x.src is not None and x.empty and self.fuse_geglu_bwd and self.dtype == torch.bfloat16 and
+                k.splitk_plan(dy, wt, M, K, N, _ld(dy), N) == 1):
+            pre, proj = x.src          # gradient of the GEGLU pre-activation straight from this GEMM's epilogue
+            dpre = self._empty(M, 2 * K)
+            fused = k.gemm_geglu_bwd(dy, wt, pre, dpre, M, K, N, _ld(dy), N, macs=c.macs)
+            if fused:
+                proj.g = dpre
+        if x.rg and not fused:
+            dx, acc, _ = x.dst()
+            k.gemm_auto(dy, wt, dx, M, K, N, _ld(dy), N, _ld(dx), accumulate=acc, macs=c.macs)
+        if c.residual is not None:
+            self._give(c.residual, c.out.g, lend=collect)
 
     def conv3(self, x, key, B, Hi, Wi, mode, bias, rowvec=None, residual=None, rv_cols=None, out=None, cs=False):
         """3x3 conv, pad 1.  mode 0: stride 1; 1: stride 2; 2: nearest-x2 upsample fused into the gather; 4: stride 2
@@ -291,13 +334,12 @@ class Ops:
                 k.conv_up2_supported(B, Hi, Wi, Cip, Cop, self.dtype)):
             return self._conv_up2(x, key, B, Hi, Wi, bias, y, e, cs and ("view" if out is not None else "own")), Ho, Wo
         acc = self._cs_for(y, B, Ho * Wo, M, Cop, view=out is not None) if cs else None   # a GroupNorm reads this output next
+        lmacs = M * e.logical[0] * e.logical[1] * 9
         acc_ok = k.gemm_auto(x.t, P.wv(key + ".weight"), y, M, Cop, 9 * Cip, 0, 9 * Cip, _ld(y), a_mode=k.A_CONV,
                conv=(B, Hi, Wi, Cip, Ho, Wo, mode, _ld(x.t)), bias=P.p(bias),
                rowvec=rowvec.t[:, rv_cols[0]:] if rowvec is not None else None, rows_per_b=Ho * Wo,
                ldrv=_ld(rowvec.t) if rowvec is not None else 0,
-               R=residual.t if residual else None, ldr=_ld(residual.t) if residual else 0,
-               macs=M * e.logical[0] * e.logical[1] * 9, colstat=acc)
-        lmacs = M * e.logical[0] * e.logical[1] * 9
+               R=residual.t if residual else None, ldr=_ld(residual.t) if residual else 0, macs=lmacs, colstat=acc)
         if self.count_macs:
             self.macs += lmacs
         out = Act(y)
@@ -313,14 +355,9 @@ class Ops:
                         colsum_out=P.g(bias))       # bias gradient fused into the weight gradient; splits add with atomics
                 if x.rg:
                     if mode == 2:
-                        tmp = self._empty(M, Cip)
-                        k.gemm_auto(dy, P.wtv(key + ".weight"), tmp, M, Cip, 9 * Cop, 0, 9 * Cop, Cip, a_mode=k.A_CONV,
-                               conv=(B, Ho, Wo, Cop, Ho, Wo, 0, ldy), macs=lmacs)
-                        pooled = self._empty(B * Hi * Wi, Cip)
-                        k.pool2x2_sum(tmp, pooled, B, Hi, Wi, Cip)
-                        self._give(x, pooled)
+                        self._dgrad_up2_pooled(x, dy, key, B, Hi, Wi, Cip, Cop, lmacs)
                     else:
-                        dx, acc = self._grad_into(x, B * Hi * Wi, Cip)
+                        dx, acc, _ = x.dst()
                         k.gemm_auto(dy, P.wtv(key + ".weight"), dx, B * Hi * Wi, Cip, 9 * Cop, 0, 9 * Cop, _ld(dx),
                                     a_mode=k.A_CONV, conv=(B, Ho, Wo, Cop, Hi, Wi, 3 if mode == 1 else 0, ldy),
                                accumulate=acc, macs=lmacs)
@@ -328,7 +365,7 @@ class Ops:
                     # d(rowvec)[b] = column sums of dy over the pixels of image b, written into this block's column slice
                     # of the batched projection's gradient (the conv bias gradient - their sum over b - comes out of the weight
                     # gradient kernel)
-                    if rowvec.g is None:
+                    if rowvec.empty:
                         rowvec.g = k.zeros(tuple(rowvec.t.shape), self.dev, torch.float32)
                     dtp = rowvec.g[:, rv_cols[0]:]
                     hw = Ho * Wo
@@ -340,6 +377,15 @@ class Ops:
             self.tape.append(bwd)
         return out, Ho, Wo
 
+    def _dgrad_up2_pooled(self, x, dy, key, B, Hi, Wi, Ci, Co, macs):
+        """Input gradient of the nearest-x2 + 3x3 conv in its 3x3 form: at the high resolution, then summed 2x2 onto x's grid."""
+        tmp = self._empty(4 * B * Hi * Wi, Ci)
+        k.gemm_auto(dy, self.P.wtv(key + ".weight"), tmp, 4 * B * Hi * Wi, Ci, 9 * Co, 0, 9 * Co, Ci, a_mode=k.A_CONV,
+                    conv=(B, 2 * Hi, 2 * Wi, Co, 2 * Hi, 2 * Wi, 0, _ld(dy)), macs=macs)
+        pooled = self._empty(B * Hi * Wi, Ci)
+        k.pool2x2_sum(tmp, pooled, B, Hi, Wi, Ci)
+        self._give(x, pooled)
+
     def _conv_up2(self, x, key, B, Hi, Wi, bias, y, e, cs=False):
         """Upsample2D (nearest x2 + 3x3 conv; unet_2d_conditional.py up blocks) as four 2x2 phase convs
         on the low-resolution image (pdmk.h conv_mode 5..12): 16 instead of 36 multiply-accumulates per low-resolution pixel,
@@ -349,7 +395,8 @@ class Ops:
         Cop, _, Cip = e.shape
         Ml = B * Hi * Wi
         wp, wpt = P.up2_weights(key)
-        lmacs = 4 * Ml * e.logical[0] * e.logical[1] * 4           # executed multiply-accumulates (the 3x3 form: 9 / 4 of it)
+        lmacs = 4 * Ml * e.logical[0] * e.logical[1] * 4           # executed multiply-accumulates
+        mac9 = lmacs * 9 // 4                                      # (the 3x3 form, which is also how the reference executes and counts it)
         geo = lambda m, ci, ld: (B, Hi, Wi, ci, Hi, Wi, m, ld)
         # cs: False = no GroupNorm reads this output; "own" = y is a fresh tensor; "view" = y is a concat view (the four phases add
         # their column sums to that buffer's GroupNorm accumulator; rows are counted on the low-resolution grid a phase enumerates)
@@ -360,7 +407,7 @@ class Ops:
                        bias=P.p(bias), macs=lmacs // 4, colstat=acc, rows_per_b=Hi * Wi if acc is not None else 0)
         k.gemm_group(r.recs)
         if self.count_macs:
-            self.macs += 4 * Ml * e.logical[0] * e.logical[1] * 9  # model MACs are counted as the reference executes them
+            self.macs += mac9
         out = Act(y)
         if acc is not None:
             out.cs = (acc[0], acc[1], Cop)
@@ -388,19 +435,14 @@ class Ops:
                     k.up2_combine_wgrad(dwp, P.g(key + ".weight"), Cop, Cip)
                 else:
                     k.wgrad(dy, xt, P.g(key + ".weight"), Cop, 9 * Cip, 4 * Ml, ldy, 0, b_mode=k.B_COLK_CONV,
-                            conv=(B, Hi, Wi, Cip, 2 * Hi, 2 * Wi, 2, _ld(xt)), macs=lmacs * 9 // 4, colsum_out=P.g(bias))
+                            conv=(B, Hi, Wi, Cip, 2 * Hi, 2 * Wi, 2, _ld(xt)), macs=mac9, colsum_out=P.g(bias))
                 if x.rg and phase_d:
                     # input gradient: all four phases as ONE problem (conv_mode 13: K = (phase, tap, channel))
-                    dx, acc = self._grad_into(x, Ml, Cip)
+                    dx, acc, _ = x.dst()
                     k.gemm(dy, wpt, dx, Ml, Cip, 16 * Cop, 0, 16 * Cop, _ld(dx), a_mode=k.A_CONV, conv=geo(13, Cop, ldy),
                            accumulate=acc, macs=lmacs)
                 elif x.rg:
-                    tmp = self._empty(4 * Ml, Cip)
-                    k.gemm_auto(dy, P.wtv(key + ".weight"), tmp, 4 * Ml, Cip, 9 * Cop, 0, 9 * Cop, Cip, a_mode=k.A_CONV,
-                                conv=(B, 2 * Hi, 2 * Wi, Cop, 2 * Hi, 2 * Wi, 0, ldy), macs=lmacs * 9 // 4)
-                    pooled = self._empty(Ml, Cip)
-                    k.pool2x2_sum(tmp, pooled, B, Hi, Wi, Cip)
-                    self._give(x, pooled)
+                    self._dgrad_up2_pooled(x, dy, key, B, Hi, Wi, Cip, Cop, mac9)
             self.tape.append(bwd)
         return out
 
@@ -419,7 +461,6 @@ class Ops:
             self._cs_arena = torch.empty(max(self._cs_max, 1 << 16), device=self.dev, dtype=torch.int64)
         self._cs_off, self._cs_need = 0, 0
         self._cs_views, self._cs_cats = {}, {}
-        self.gn_count = [0, 0]          # GroupNorms of this pass, of which with statistics from a producer's epilogue
         if self._cs_arena is not None:
             k.zero_(self._cs_arena)
 
@@ -471,7 +512,7 @@ class Ops:
         if self.train:
             def bwd():
                 dy = out.g
-                dx, acc, add = self._grad_into(x, B * HW, C, absorb=True)
+                dx, acc, add = x.dst(port=True)
                 k.groupnorm_bwd(x.t, dy, dx, gw, gb, stats, P.g(key + ".weight"), P.g(key + ".bias"), self.ws, B,
                                 HW, C, _ld(x.t), _ld(dy), _ld(dx), G, gs, silu, acc, add=add, queue=self.partials)
             self.tape.append(bwd)
@@ -487,7 +528,7 @@ class Ops:
         out = Act(y)
         if self.train:
             def bwd():
-                dx, acc, add = self._grad_into(x, M, C, absorb=True)     # add: the residual branch's finished gradient
+                dx, acc, add = x.dst(port=True)     # add: the residual branch's finished gradient
                 k.layernorm_bwd(x.t, out.g, dx, gw, stats, P.g(key + ".weight"), P.g(key + ".bias"), M, C, _ld(x.t),
                                 _ld(out.g), _ld(dx), acc, queue=self.partials, add=add)
             self.tape.append(bwd)

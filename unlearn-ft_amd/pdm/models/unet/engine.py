@@ -141,14 +141,6 @@ class UNetEngine(Ops):
             self.tape.append(self._wg_open)        # runs first in the block's backward
         return y
 
-    def _wg_open(self):
-        self._wg_items = []
-
-    def _wg_flush(self):
-        items, self._wg_items = self._wg_items, None
-        if items:
-            k.wgrad_group(items, self.slabs)
-
     # ------------------------------------------------------------------ whole model
     def forward(self, x, timesteps, ehs, B, H, W, train):
         """x: [B*H*W, padc(in_channels)] NHWC rows in self.dtype; timesteps int64 [B]; ehs: [B*T, ctx] in self.dtype.
