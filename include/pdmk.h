@@ -573,6 +573,30 @@ int pdmk_global_avgpool(const float* x, int ldx, float* y, int B, int HW, int C,
 int pdmk_fid_accumulate(const float* x, int ldx, int B, int D, double* sum, double* outer, pdmk_stream stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * ConceptPrune (baselines/concept_prune/wanda.py, save_union_over_time.py; pdm/utils/concept_prune.py): Wanda scores of the
+ * second feed-forward Linear (ff.net.2, W [O, F]) against the norms of its input over a set of prompts, per timestep.
+ * No float atomics: the same arguments give the same bits, launch after launch (the masks compare these numbers).
+ * pdmk_rownorm_colsq: acc[f] += sum_m (x[m][f] / max(||x[m, :]||_2, 1e-12))^2 - the squared column norms of F.normalize(x,
+ *   dim=1), added to the fp32 accumulator acc [F].  x [M, F] f32 / bf16 with row stride ld >= F (columns outside [0, F) are not
+ *   read); F % 8 == 0, F >= 8, ld % 8 == 0, x 16-byte aligned, M >= 1.  Row norms and every sum in fp32; an all-zero row adds 0.
+ *   Three launches: row norms (a wave per row), column sums of (column chunk x row block) tiles into partial slabs, the
+ *   slabs added in order; x is read twice.  ws: fp32 scratch of pdmk_rownorm_colsq_workspace_elems(M, F) elements, 16-byte
+ *   aligned, free again when the call's launches have run.
+ * pdmk_wanda_count: for every t < T and row o < O: mt[f] = |W[o][f]| * n_target[t][f], mb[f] = |W[o][f]| * n_base[t][f] (one fp32
+ *   multiply each, of the fp32 value of the weight); S = the k largest mt[f] of the row, equal values in ascending f (torch.sort(
+ *   descending=True, stable=True)); count[o][f] += (f in S) && (mt[f] > mb[f]).  k == 0 selects nothing, k >= F the whole row.
+ *   w f32 / bf16 with row stride ldw >= F; n_base / n_target fp32 [T, F] contiguous, FINITE and >= 0 (NaN / inf have no defined
+ *   order here); count int32 [O, F] contiguous, accumulated into.  One workgroup per row, all T in the one launch.
+ *   F <= PDMK_WANDA_MAX_F (the dense SD-2.1 width), else -2.
+ * pdmk_wanda_apply: W[o][f] = 0 where (float)count[o][f] > threshold; every other element is left as it is. */
+#define PDMK_WANDA_MAX_F 5120
+int64_t pdmk_rownorm_colsq_workspace_elems(int M, int F);
+int pdmk_rownorm_colsq(const void* x, int dtype, int M, int F, int ld, float* acc, float* ws, int64_t ws_elems, pdmk_stream stream);
+int pdmk_wanda_count(const void* w, int dtype, int O, int F, int ldw, const float* n_base, const float* n_target, int T, int k,
+                     int32_t* count, pdmk_stream stream);
+int pdmk_wanda_apply(void* w, int dtype, int O, int F, int ldw, const int32_t* count, float threshold, pdmk_stream stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Data-parallel gradient exchange: DDP's all-reduce inside accelerator.backward
  * (pdm/training/trainer.py:117-129, 2782, 2808) as RCCL all-reduces over xGMI behind an explicit communicator handle.
  * pdmk_comm_unique_id: rank 0 fills 128 bytes (ncclUniqueId) and hands them to the other ranks out of band (the Python

@@ -124,6 +124,10 @@ _SIGS = {
     "pdmk_pool2d": ([vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp], i32),
     "pdmk_global_avgpool": ([vp, i32, vp, i32, i32, i32, vp], i32),
     "pdmk_fid_accumulate": ([vp, i32, i32, i32, vp, vp, vp], i32),
+    "pdmk_rownorm_colsq_workspace_elems": ([i32, i32], i64),
+    "pdmk_rownorm_colsq": ([vp, i32, i32, i32, i32, vp, vp, i64, vp], i32),
+    "pdmk_wanda_count": ([vp, i32, i32, i32, i32, vp, vp, i32, i32, vp, vp], i32),
+    "pdmk_wanda_apply": ([vp, i32, i32, i32, i32, vp, f32, vp], i32),
     "pdmk_gemm_splitk_workspace_bytes": ([i64, i32, i32], i64),
     "pdmk_groupnorm_workspace_bytes": ([i32, i32], i64),
     "pdmk_groupnorm_bwd_part_workspace_bytes": ([i32, i32], i64),
@@ -1069,3 +1073,46 @@ def up2_combine_wgrad(dwp, dw3, Co, Ci):
 
 def sumsq(x, n, out, slot):
     _chk(_lib.pdmk_sumsq(_p(x), n, _p(out), slot, _st()), "pdmk_sumsq")
+
+
+# ---- ConceptPrune (pdmk.h "ConceptPrune")
+WANDA_MAX_F = 5120
+
+
+def rownorm_colsq(x, acc, M=None, F=None, ld=None):
+    """acc[F] (fp32) += the squared column norms of the row-normalised x [M, F] (f32 / bf16, row stride ld)."""
+    M = x.shape[0] if M is None else M
+    F = x.shape[1] if F is None else F
+    ld = x.stride(0) if ld is None else ld
+    if acc.dtype != torch.float32 or acc.numel() < F or not acc.is_contiguous():
+        raise PdmkError(f"rownorm_colsq: acc must be contiguous fp32 with at least F = {F} elements")
+    ws = part_ws(x.device, _lib.pdmk_rownorm_colsq_workspace_elems(M, F))
+    _chk(_lib.pdmk_rownorm_colsq(_p(x), dt(x), M, F, ld, _p(acc), _p(ws), ws.numel(), _st()), "pdmk_rownorm_colsq")
+
+
+def wanda_count(w, n_base, n_target, k, count, O=None, F=None, ldw=None):
+    """count[O, F] (int32) += over the T rows of n_base / n_target (fp32 [T, F]): f among the k largest |w[o]| * n_target[t] of
+    row o (ties in ascending f) and |w[o, f]| * n_target[t, f] > |w[o, f]| * n_base[t, f]."""
+    O = w.shape[0] if O is None else O
+    F = w.shape[1] if F is None else F
+    ldw = w.stride(0) if ldw is None else ldw
+    if F > WANDA_MAX_F:
+        raise PdmkError(f"wanda_count: F = {F} is wider than the {WANDA_MAX_F} columns the selection kernel keeps on chip")
+    T = n_base.shape[0]
+    for n in (n_base, n_target):
+        if n.dtype != torch.float32 or tuple(n.shape) != (T, F) or not n.is_contiguous():
+            raise PdmkError(f"wanda_count: norms must be contiguous fp32 [T, {F}], got {tuple(n.shape)} {n.dtype}")
+    if count.dtype != torch.int32 or tuple(count.shape) != (O, F) or not count.is_contiguous():
+        raise PdmkError(f"wanda_count: count must be contiguous int32 [{O}, {F}]")
+    _chk(_lib.pdmk_wanda_count(_p(w), dt(w), O, F, ldw, _p(n_base), _p(n_target), T, int(k), _p(count), _st()),
+         "pdmk_wanda_count")
+
+
+def wanda_apply(w, count, threshold, O=None, F=None, ldw=None):
+    """w[o, f] = 0 where float(count[o, f]) > threshold (w: f32 / bf16 [O, F] view with row stride ldw)."""
+    O = w.shape[0] if O is None else O
+    F = w.shape[1] if F is None else F
+    ldw = w.stride(0) if ldw is None else ldw
+    if count.dtype != torch.int32 or tuple(count.shape) != (O, F) or not count.is_contiguous():
+        raise PdmkError(f"wanda_apply: count must be contiguous int32 [{O}, {F}]")
+    _chk(_lib.pdmk_wanda_apply(_p(w), dt(w), O, F, ldw, _p(count), float(threshold), _st()), "pdmk_wanda_apply")

@@ -112,9 +112,10 @@ _Lin = namedtuple("_Lin", "key bias M N K x out residual macs")
 
 class Ops:
     def __init__(self, store, dtype, *, norm_groups=32, fuse_geglu=True, fuse_ln=0, fuse_geglu_bwd=False, defer_fanin=False,
-                 partials=None, slabs=None, up2=False, gn_epi=False, group_wgrad=False, attn_fp8=False):
+                 partials=None, slabs=None, up2=False, gn_epi=False, group_wgrad=False, attn_fp8=False, ffn_observer=None):
         """The defaults are inference behaviour; what each switch selects is told where UNetEngine reads it from the
-        environment (unet/engine.py)."""
+        environment (unet/engine.py).  ffn_observer: None, or a callable (layer index, tensor [M, F]) that the model calls with
+        the input of every feed-forward output projection (ConceptPrune: pdm/utils/concept_prune.py)."""
         self.P, self.dtype = store, dtype
         self.dev = store.master.device
         self.ws = k.groupnorm_ws(self.dev, 64, norm_groups)      # GN scratch, regrown by groupnorm() if B asks for more
@@ -125,6 +126,7 @@ class Ops:
         self.fuse_geglu, self.fuse_ln, self.fuse_geglu_bwd, self.defer_fanin = fuse_geglu, fuse_ln, fuse_geglu_bwd, defer_fanin
         self.partials, self.slabs = partials, slabs              # k.PartialQueue / k.SlabQueue, or None: nothing deferred
         self.up2, self.gn_epi, self.group_wgrad, self.attn_fp8 = up2, gn_epi, group_wgrad, attn_fp8
+        self.ffn_observer = ffn_observer
         self._wg_items = None          # a list while Linear weight gradients are being collected for one grouped launch
         self._wg_lent = []             # the Acts that hold a dy of those items as a lent buffer
         self.gn_count, self.gn_miss = [0, 0], None

@@ -55,6 +55,8 @@ class UNetEngine(Ops):
         # skip k (push order) is concatenated behind an h of cat_ch[k] channels (None: its consumer ResBlock is dropped)
         ups = [r for b in blocks if b.kind == "up" for r in b.resnets]
         self.cat_ch = [None if r.dropped else padc(r.cin - r.skip) for r in reversed(ups)]
+        # feed-forward blocks in execution order (down, mid, up): the layer index an ffn_observer is called with
+        self.ffn_index = {a.name: i for i, a in enumerate(a for b in blocks for a in b.attns if not a.dropped)}
 
     # ------------------------------------------------------------------ concat views
     def _skip_view(self, k_, M, C, B=0):
@@ -135,6 +137,8 @@ class UNetEngine(Ops):
                            ((ko, ko + d2), (ko + d2, ko + 2 * d2)))
         h = self.linear(o, t + ".attn2.to_out.0", bias=t + ".attn2.to_out.0.bias", residual=h)
         gl = self.linear(h, t + ".ff.net.0.proj", bias=t + ".ff.net.0.proj.bias", geglu=True, ln=t + ".norm3")
+        if self.ffn_observer is not None:
+            self.ffn_observer(self.ffn_index[p], gl.t)
         h = self.linear(gl, t + ".ff.net.2", bias=t + ".ff.net.2.bias", residual=h)
         y = self.linear(h, p + ".proj_out", bias=p + ".proj_out.bias", residual=x, out=out, cs=(B, N) if cs else None)
         if self.train and self.group_wgrad:

@@ -12,7 +12,8 @@ The denoising loop runs as replays of a captured graph (`_CapturedLoop`) when it
 followed by pdmk_plms_step, which does the guidance, the PLMS update and the next U-Net input in one launch, advances a
 device-side step counter and refreshes the U-Net's timestep buffer from a step table - so one capture serves every step.
 It is bit-identical to the eager loop (the kernel repeats pdmk_axpby's fp32 arithmetic operation by operation; DESIGN.md
-9.1).  `callback=`, block hooks, another scheduler class or PDMK_SAMPLER_GRAPH=0 select the eager loop.
+9.1).  `callback=`, block hooks, an `ffn_observer` on the U-Net's engine, another scheduler class (DDIMScheduler) or
+PDMK_SAMPLER_GRAPH=0 select the eager loop.
 """
 import ctypes
 import gc
@@ -148,6 +149,82 @@ class PNDMScheduler:
         return rows
 
 
+class DDIMScheduler:
+    """diffusers DDIMScheduler with eta = 0 (deterministic, one U-Net call per step - what ConceptPrune's per-timestep
+    accumulators count on) as SD-2.1's DDIM scheduler_config.json sets it, as far as that file can be recalled here:
+    scaled_linear betas 0.00085 ... 0.012, steps_offset 1, clip_sample false, set_alpha_to_one false, leading timestep spacing.
+    Unpinned like PNDMScheduler above (diffusers absent, no vendored twin).  `from_config` is as strict as PNDM's.
+
+    With a_t = alphas_cumprod[t], b_t = 1 - a_t and a_p / b_p those of the previous timestep t - T / N (below 0: alphas_cumprod[0])
+        epsilon:       prev = sqrt(a_p / a_t) x + (sqrt(b_p) - sqrt(a_p b_t / a_t)) e
+        v_prediction:  prev = (sqrt(a_p a_t) + sqrt(b_p b_t)) x + (sqrt(b_p a_t) - sqrt(a_p b_t)) v
+    (x0 and eps substituted into sqrt(a_p) x0 + sqrt(b_p) eps): linear in (sample, model_output), so the coefficients are
+    formed in float64 on the host and the step is one pdmk_axpby launch."""
+    order = 1
+    init_noise_sigma = 1.0
+    _FIXED = {"beta_schedule": "scaled_linear", "set_alpha_to_one": False, "trained_betas": None, "clip_sample": False,
+              "timestep_spacing": "leading", "thresholding": False, "rescale_betas_zero_snr": False}
+    _FREE = ("num_train_timesteps", "beta_start", "beta_end", "steps_offset", "prediction_type")
+    # read only by what _FIXED turns off, or by PNDM (SD-2.1's file carries PNDM's skip_prk_steps beside DDIM's class name)
+    _IGNORED = ("clip_sample_range", "dynamic_thresholding_ratio", "sample_max_value", "skip_prk_steps")
+
+    def __init__(self, num_train_timesteps=1000, beta_start=0.00085, beta_end=0.012, steps_offset=1,
+                 prediction_type="epsilon"):
+        if prediction_type not in ("epsilon", "v_prediction"):
+            raise ValueError(f"DDIMScheduler: prediction_type={prediction_type!r} is not implemented")
+        betas = torch.linspace(beta_start ** 0.5, beta_end ** 0.5, num_train_timesteps, dtype=torch.float32) ** 2
+        self.alphas_cumprod = torch.cumprod(1.0 - betas, dim=0).double()
+        self.final_alpha_cumprod = self.alphas_cumprod[0]
+        self.config = SimpleNamespace(num_train_timesteps=num_train_timesteps, steps_offset=steps_offset,
+                                      prediction_type=prediction_type)
+        self.timesteps = None
+
+    @classmethod
+    def from_config(cls, config):
+        """From a diffusers scheduler_config.json dict (or its path).  Keys starting with "_" are ignored; a value this class
+        does not implement (another beta schedule, clipping, thresholding, trailing spacing, ...) or an unknown key raises."""
+        if isinstance(config, str):
+            with open(config) as f:
+                config = json.load(f)
+        kw = {}
+        for key, v in config.items():
+            if key.startswith("_") or key in cls._IGNORED:
+                continue
+            if key in cls._FIXED:
+                if v != cls._FIXED[key]:
+                    raise ValueError(f"DDIMScheduler: {key}={v!r} is not implemented (only {cls._FIXED[key]!r})")
+            elif key in cls._FREE:
+                kw[key] = v
+            else:
+                raise ValueError(f"DDIMScheduler: config key {key!r} is not implemented")
+        return cls(**kw)
+
+    def set_timesteps(self, num_inference_steps, device=None):
+        self.num_inference_steps = num_inference_steps
+        ratio = self.config.num_train_timesteps // num_inference_steps
+        self.timesteps = ((torch.arange(0, num_inference_steps) * ratio).round().long() + self.config.steps_offset).flip(0)
+
+    def scale_model_input(self, sample, t=None):
+        return sample
+
+    def coefficients(self, t):
+        """(c_x, c_m) with prev = c_x * sample + c_m * model_output, float64 arithmetic, Python floats."""
+        prev_t = t - self.config.num_train_timesteps // self.num_inference_steps
+        a_t = self.alphas_cumprod[t]
+        a_p = self.alphas_cumprod[prev_t] if prev_t >= 0 else self.final_alpha_cumprod
+        b_t, b_p = 1 - a_t, 1 - a_p
+        if self.config.prediction_type == "v_prediction":
+            return float((a_p * a_t).sqrt() + (b_p * b_t).sqrt()), float((b_p * a_t).sqrt() - (a_p * b_t).sqrt())
+        return float((a_p / a_t).sqrt()), float(b_p.sqrt() - (a_p * b_t / a_t).sqrt())
+
+    def step(self, model_output, timestep, sample, return_dict=True):
+        """model_output / sample: contiguous fp32 device tensors of one shape; returns the previous sample (new tensor)."""
+        c_x, c_m = self.coefficients(int(timestep))
+        prev = sample.clone()
+        k.axpby(model_output, prev, c_m, c_x)
+        return SimpleNamespace(prev_sample=prev) if return_dict else (prev,)
+
+
 class _CapturedLoop:
     """The denoising loop of one (batch, H, W, dtype, CFG, steps, text shape, guidance) as replays of ONE single-stream
     captured graph (GraphedBilevel's docstring: graphs with parallel branches are not used): the U-Net forward over static
@@ -271,6 +348,8 @@ class StableDiffusionPruningPipeline:
         u = self.unet
         blocks = list(getattr(u, "down_blocks", [])) + [getattr(u, "mid_block", None)] + list(getattr(u, "up_blocks", []))
         if any(getattr(b, "_hooks", None) for b in blocks):            # block hooks fire in the eager U-Net call only
+            return False
+        if getattr(getattr(u, "engine", None), "ffn_observer", None) is not None:     # so does a feed-forward observer
             return False
         return graph is True or os.environ.get("PDMK_SAMPLER_GRAPH", "1") != "0"
 

@@ -18,8 +18,8 @@ import torch
 
 logger = logging.getLogger("pdm.erasure")
 
-BASELINES = ("pdm", "pruned_baseline", "esd", "uce")
-BASELINES_NOT_BUILT = ("concept-prune", "concept-ablation", "baseline")
+BASELINES = ("pdm", "pruned_baseline", "esd", "uce", "concept-prune")
+BASELINES_NOT_BUILT = ("concept-ablation", "baseline")
 GUIDANCE = 7.5
 
 
@@ -45,9 +45,15 @@ def read_prompts(path):
 
 
 # ---- paths (artist_erasure.py:54-57, :165-166)
-def check_baseline(baseline):
+def check_baseline(baseline, ckpt_name=None):
+    """`concept-prune` takes the checkpoint file scripts/baselines/concept_prune/save_union_over_time.py writes as
+    --ckpt_name; without one the reference looks the target up in its table of checkpoint paths (utils/load_models.py),
+    which is not built here."""
     if baseline in BASELINES_NOT_BUILT:
         raise NotImplementedError(f"--baseline {baseline}: not built here (built: {', '.join(BASELINES)})")
+    if baseline == "concept-prune" and ckpt_name is None:
+        raise NotImplementedError("--baseline concept-prune without --ckpt_name: the reference's table of checkpoint paths is "
+                                  "not built here; pass the .pt file save_union_over_time.py wrote")
     if baseline not in BASELINES:
         raise ValueError(f"--baseline {baseline!r}: expected one of {', '.join(BASELINES + BASELINES_NOT_BUILT)}")
 
@@ -205,16 +211,22 @@ def _load_unet(models, config, ckpt_dir):
         attention_precision=pm.get("attention_precision"), train=False)
 
 
-def load_pipelines(config, args, device):
-    """(original, erased) pipelines sharing VAE, text encoder, tokenizer and scheduler settings."""
+def load_frozen_models(config, device):
+    """VAE, text encoder, weight dtype and U-Net topology by the trainer's rules, without the trainer's set-up."""
     from ..models.unet.spec import UNetConfig
-    from ..pipelines.pruning_pipelines import PNDMScheduler, StableDiffusionPruningPipeline
     from ..training.trainer import Trainer
-    from .data import load_tokenizer
-    models = Trainer.__new__(Trainer)                 # the trainer's rules for dtype, VAE and text encoder, without its set-up
+    models = Trainer.__new__(Trainer)
     models.config, models.device = config, device
     models.init_weight_dtype()
     models.unet_config = UNetConfig.tiny() if config.get_path("tiny", False) else UNetConfig.sd21()
+    return models
+
+
+def load_pipelines(config, args, device):
+    """(original, erased) pipelines sharing VAE, text encoder, tokenizer and scheduler settings."""
+    from ..pipelines.pruning_pipelines import PNDMScheduler, StableDiffusionPruningPipeline
+    from .data import load_tokenizer
+    models = load_frozen_models(config, device)
     original = _load_unet(models, config, args.original_ckpt)
     if args.baseline == "pdm":
         if args.ckpt_name is None:
@@ -222,7 +234,7 @@ def load_pipelines(config, args, device):
         erased = _load_unet(models, config, args.ckpt_name)
     elif args.baseline == "pruned_baseline":
         erased = original
-    else:                                             # esd, uce
+    else:                                             # esd, uce, concept-prune
         if args.ckpt_name is None:
             raise ValueError(f"--baseline {args.baseline} needs --ckpt_name (the erasure checkpoint file)")
         erased = _load_unet(models, config, args.original_ckpt)

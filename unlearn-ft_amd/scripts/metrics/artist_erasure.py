@@ -15,8 +15,10 @@ eval_artish.sh with `--baseline pdm`): did the bilevel fine-tuning erase the art
   after the other.
 * --baseline: `pdm` = <ckpt_name>/arch_vector.pt + unet/diffusion_pytorch_model.safetensors; `pruned_baseline` = the
   original checkpoint itself; `esd` / `uce` = the original checkpoint with the erasure checkpoint --ckpt_name laid over it
-  (ESD: nested {module: {weight, bias}}, non-strict; UCE: a full state dict, strict).  `concept-prune`, `concept-ablation`
-  and `baseline` raise NotImplementedError.
+  (ESD: nested {module: {weight, bias}}, non-strict; UCE: a full state dict, strict); `concept-prune` = the same with the
+  checkpoint scripts/baselines/concept_prune/save_union_over_time.py writes (a full state dict, strict; its masked layers are
+  fp16; without --ckpt_name it raises NotImplementedError: the reference's table of checkpoint paths is not built).
+  `concept-ablation` and `baseline` raise NotImplementedError.
 * Scoring, always, from the files: CLIP ViT-B/32 (--clip_model, resolved like clip_score.py's: a local transformers
   directory or an OpenAI .pt; a hub id raises FileNotFoundError) in fp32 (--mixed_precision is the samplers' dtype) of
   prompt and images, pdmk_cosine_pairs per batch of --batch_size pairs, then
@@ -74,7 +76,7 @@ def main(argv=None):
     print("Arguments: ", args.__dict__)
     if args.target is None or args.baseline is None:
         raise ValueError("--target and --baseline are required")
-    E.check_baseline(args.baseline)
+    E.check_baseline(args.baseline, args.ckpt_name)
     if args.hook_module != "unet":
         raise NotImplementedError(f"--hook_module {args.hook_module}: only `unet` is built")
     if args.ckpt_name is None and args.original_ckpt is None:
