@@ -597,6 +597,42 @@ int pdmk_wanda_count(const void* w, int dtype, int O, int F, int ldw, const floa
 int pdmk_wanda_apply(void* w, int dtype, int O, int F, int ldw, const int32_t* count, float threshold, pdmk_stream stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * UCE (baselines/unified-concept-editing/train-scripts/train_erase.py; pdm/utils/uce.py): the closed-form edit of every
+ * cross-attention to_k / to_v weight, W' = W + s_e D^T Z with Z = E_old (lam I + s_e G_old + s_r G_retain)^-1 and D = V - O.
+ * The K x K system is formed, factored and solved in fp64; the library allocates nothing, waits for nothing on the host and
+ * uses no atomics here, and the same arguments give the same bits.
+ * pdmk_spd_system_f64: A[i][j] = fma(s_b, sym(g_b)[i][j], fma(s_a, sym(g_a)[i][j], i == j ? lam : 0)) (g_b NULL: the inner fma
+ *   alone), A [n, n] fp64 with row stride lda.  g_a / g_b: [n, n] fp64 contiguous as pdmk_fid_accumulate leaves `outer` (only
+ *   the 64 x 64 tiles that touch the upper triangle are valid); sym takes each element from the tile that holds it.
+ * pdmk_spd_factor_f64: Cholesky A = L L^T in place, 1 <= n <= PDMK_SPD_MAX_N (any n), lda >= n: the lower triangle of A is read
+ *   and receives L; the strict upper triangle is not read and is unspecified afterwards; columns >= n of a row are neither read
+ *   nor written.  Right-looking, 64-wide panels, per panel: the diagonal block in LDS by one workgroup, the rows below it by
+ *   forward substitution (a thread per row), the trailing matrix by 64 x 64 tiles - about 3 n / 64 launches.  *info (device, the
+ *   caller zeroes it) stays 0 or becomes j + 1 for the first column j whose pivot is not positive and finite; every launch still
+ *   completes on whatever values there are.  The factor needs no workspace.
+ * pdmk_spd_solve_f64: X = B (L L^T)^-1 row by row: B fp32 [m, n] (row stride ldb, converted exactly), X fp32 [m, n] (the fp64
+ *   result rounded to nearest even), X64 fp64 [m, n] or NULL; m >= 1.  One workgroup per 16 rows: forward then backward block
+ *   substitution against L, diagonal blocks by substitution (no inverse is formed anywhere: Higham Thm 10.3 / 10.4 hold).  A
+ *   row's result does not depend on the rows it shares a block with.  ws: fp64 scratch of pdmk_spd_workspace_elems(n, m)
+ *   elements, free again when the launch has run.
+ * pdmk_uce_delta: O, N, D fp32 [m, ld].  row_seg [P + 1] / col_seg [Q + 1] (DEVICE int32, non-decreasing, row_seg[P] <= m,
+ *   col_seg[Q] <= ld): first rows of the P pairs, first columns of the Q projections.  technique 0: D = N - O.  technique 1,
+ *   per block (p, q): a = sum O N, b = sum O^2 in fp64 in a fixed order, s = fp32(1 + (b > 0 ? a / b : 0)), D = fmaf(-s, O, N) -
+ *   the reference's N - <u, N> u - O with u = O / ||O||; an all-zero block gives D = N where the reference divides by zero.
+ *   Rows [row_seg[P], m) of the column range are written as zeros; columns outside [col_seg[0], col_seg[Q]) are not touched.
+ *   ws: 2 P Q fp64 (technique 1; may be NULL for technique 0).  P <= 65534.
+ * All: -1 on a null / misaligned pointer, a size out of range, a stride smaller than the row, a workspace too small. */
+#define PDMK_SPD_MAX_N 4096
+int64_t pdmk_spd_workspace_elems(int n, int m);
+int pdmk_spd_system_f64(const double* g_a, double s_a, const double* g_b, double s_b, double lam, double* A, int n, int lda,
+                        pdmk_stream stream);
+int pdmk_spd_factor_f64(double* A, int n, int lda, int32_t* info, pdmk_stream stream);
+int pdmk_spd_solve_f64(const double* L, int n, int ldl, const float* B, int m, int ldb, float* X, int ldx, double* X64, int ldx64,
+                       double* ws, int64_t ws_elems, pdmk_stream stream);
+int pdmk_uce_delta(const float* O, const float* N, float* D, int m, int ld, const int32_t* row_seg, int P, const int32_t* col_seg,
+                   int Q, int technique, double* ws, pdmk_stream stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Data-parallel gradient exchange: DDP's all-reduce inside accelerator.backward
  * (pdm/training/trainer.py:117-129, 2782, 2808) as RCCL all-reduces over xGMI behind an explicit communicator handle.
  * pdmk_comm_unique_id: rank 0 fills 128 bytes (ncclUniqueId) and hands them to the other ranks out of band (the Python

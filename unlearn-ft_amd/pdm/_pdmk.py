@@ -128,6 +128,11 @@ _SIGS = {
     "pdmk_rownorm_colsq": ([vp, i32, i32, i32, i32, vp, vp, i64, vp], i32),
     "pdmk_wanda_count": ([vp, i32, i32, i32, i32, vp, vp, i32, i32, vp, vp], i32),
     "pdmk_wanda_apply": ([vp, i32, i32, i32, i32, vp, f32, vp], i32),
+    "pdmk_spd_workspace_elems": ([i32, i32], i64),
+    "pdmk_spd_system_f64": ([vp, f64, vp, f64, f64, vp, i32, i32, vp], i32),
+    "pdmk_spd_factor_f64": ([vp, i32, i32, vp, vp], i32),
+    "pdmk_spd_solve_f64": ([vp, i32, i32, vp, i32, i32, vp, i32, vp, i32, vp, i64, vp], i32),
+    "pdmk_uce_delta": ([vp, vp, vp, i32, i32, vp, i32, vp, i32, i32, vp, vp], i32),
     "pdmk_gemm_splitk_workspace_bytes": ([i64, i32, i32], i64),
     "pdmk_groupnorm_workspace_bytes": ([i32, i32], i64),
     "pdmk_groupnorm_bwd_part_workspace_bytes": ([i32, i32], i64),
@@ -1116,3 +1121,73 @@ def wanda_apply(w, count, threshold, O=None, F=None, ldw=None):
     if count.dtype != torch.int32 or tuple(count.shape) != (O, F) or not count.is_contiguous():
         raise PdmkError(f"wanda_apply: count must be contiguous int32 [{O}, {F}]")
     _chk(_lib.pdmk_wanda_apply(_p(w), dt(w), O, F, ldw, _p(count), float(threshold), _st()), "pdmk_wanda_apply")
+
+
+# ---- UCE (pdmk.h "UCE")
+SPD_MAX_N = 4096
+
+
+def _f64_matrix(t, n, name, what):
+    """t: fp64 [n, >= n] view with unit column stride; returns its row stride."""
+    if t.dtype != torch.float64 or t.dim() != 2 or t.shape[0] != n or t.shape[1] != n or t.stride(1) != 1 or t.stride(0) < n:
+        raise PdmkError(f"{name}: {what} must be an fp64 [{n}, {n}] view with contiguous rows")
+    return t.stride(0)
+
+
+def spd_system(g_a, s_a, g_b, s_b, lam, A):
+    """A = lam I + s_a sym(g_a) + s_b sym(g_b) (g_b may be None); g: the `outer` of fid_accumulate, A fp64 [n, n] (row stride >= n)."""
+    n = g_a.shape[0]
+    for g in (g_a, g_b):
+        if g is not None and (g.dtype != torch.float64 or tuple(g.shape) != (n, n) or not g.is_contiguous()):
+            raise PdmkError(f"spd_system: the Gram matrices must be contiguous fp64 [{n}, {n}]")
+    if not 1 <= n <= SPD_MAX_N:
+        raise PdmkError(f"spd_system: n = {n} outside 1 .. {SPD_MAX_N}")
+    lda = _f64_matrix(A, n, "spd_system", "A")
+    _chk(_lib.pdmk_spd_system_f64(_p(g_a), float(s_a), _p(g_b), float(s_b), float(lam), _p(A), n, lda, _st()),
+         "pdmk_spd_system_f64")
+
+
+def spd_factor(A, info):
+    """Cholesky A = L L^T in place (lower triangle); info: int32 [1] on the device, zeroed by the caller (0, or first bad column + 1)."""
+    n = A.shape[0]
+    if not 1 <= n <= SPD_MAX_N:
+        raise PdmkError(f"spd_factor: n = {n} outside 1 .. {SPD_MAX_N}")
+    lda = _f64_matrix(A, n, "spd_factor", "A")
+    if info.dtype != torch.int32 or info.numel() != 1 or info.device != A.device:
+        raise PdmkError("spd_factor: info must be one int32 on the matrix' device")
+    _chk(_lib.pdmk_spd_factor_f64(_p(A), n, lda, _p(info), _st()), "pdmk_spd_factor_f64")
+
+
+def spd_solve(L, B, X, X64=None):
+    """X = B (L L^T)^-1: B, X fp32 [m, n] and X64 fp64 [m, n] (optional) views with contiguous rows."""
+    n = L.shape[0]
+    ldl = _f64_matrix(L, n, "spd_solve", "L")
+    m = B.shape[0]
+    for t, dtype, name in ((B, torch.float32, "B"), (X, torch.float32, "X"), (X64, torch.float64, "X64")):
+        if t is not None and (t.dtype != dtype or t.dim() != 2 or tuple(t.shape) != (m, n) or t.stride(1) != 1 or t.stride(0) < n):
+            raise PdmkError(f"spd_solve: {name} must be a {dtype} [{m}, {n}] view with contiguous rows")
+    if m < 1:
+        raise PdmkError("spd_solve: m >= 1")
+    ws = torch.empty(_lib.pdmk_spd_workspace_elems(n, m), device=L.device, dtype=torch.float64)
+    _chk(_lib.pdmk_spd_solve_f64(_p(L), n, ldl, _p(B), m, B.stride(0), _p(X), X.stride(0), _p(X64),
+                                 0 if X64 is None else X64.stride(0), _p(ws), ws.numel(), _st()), "pdmk_spd_solve_f64")
+
+
+def uce_delta(O, N, D, row_seg, col_seg, technique):
+    """D = N - O (technique 0) or N - (1 + <O, N> / <O, O>) O per (pair, projection) block (technique 1) on fp32 [m, ld]
+    matrices of one layout; row_seg / col_seg: host lists of P + 1 first rows / Q + 1 first columns.  Rows from row_seg[-1] on
+    are zeroed."""
+    m, ld = O.shape[0], O.stride(0)
+    for t in (O, N, D):
+        if t.dtype != torch.float32 or t.dim() != 2 or t.shape != O.shape or t.stride() != O.stride() or t.stride(1) != 1:
+            raise PdmkError("uce_delta: O, N, D must be fp32 [m, w] views of one shape and row stride")
+    row_seg, col_seg = [int(v) for v in row_seg], [int(v) for v in col_seg]
+    P, Q = len(row_seg) - 1, len(col_seg) - 1
+    if (P < 1 or Q < 1 or P > 65534 or technique not in (0, 1) or any(b < a for a, b in zip(row_seg, row_seg[1:]))
+            or any(b < a for a, b in zip(col_seg, col_seg[1:])) or row_seg[0] < 0 or col_seg[0] < 0 or row_seg[-1] > m
+            or col_seg[-1] > O.shape[1]):
+        raise PdmkError(f"uce_delta: segments must ascend inside [0, {m}] x [0, {O.shape[1]}], technique 0 / 1")
+    seg = torch.tensor(row_seg + col_seg, dtype=torch.int32).to(O.device)
+    ws = torch.empty(2 * P * Q, device=O.device, dtype=torch.float64) if technique == 1 else None
+    _chk(_lib.pdmk_uce_delta(_p(O), _p(N), _p(D), m, ld, _p(seg), P, _p(seg[P + 1:]), Q, int(technique), _p(ws), _st()),
+         "pdmk_uce_delta")
