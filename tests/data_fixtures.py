@@ -1,5 +1,6 @@
 """Data fixtures built at run time for the loader tests (nothing is downloaded): JPEG images written by PIL, COCO caption
-annotations, a `datasets` directory and a small CLIP tokenizer (byte-level vocabulary + a few merges)."""
+annotations, a `datasets` directory, a small CLIP tokenizer (byte-level vocabulary + a few merges) and a pruned checkpoint
+beside a tokenizer-only snapshot."""
 import json
 import os
 
@@ -31,6 +32,29 @@ def write_tokenizer(root):
         json.dump({"tokenizer_class": "CLIPTokenizer", "model_max_length": T, "bos_token": "<|startoftext|>",
                    "eos_token": "<|endoftext|>", "unk_token": "<|endoftext|>", "pad_token": "<|endoftext|>"}, f)
     return root
+
+
+def write_pruned_checkpoint_tree(root, dev, yaml_name):
+    """A snapshot directory (tokenizer only: VAE and text encoder are seeded), a pruned checkpoint directory (tiny U-Net at
+    budget 0.6, fp32, seed 3) and the YAML: dict(root, snap, ck, yaml, sd = the saved state dict)."""
+    import torch
+    import yaml
+    from pdm.models.unet.spec import UNetConfig, arch_vector_for_budget
+    from pdm.models.unet.unet_2d_conditional import UNet2DConditionModelPruned
+    snap = write_tokenizer(os.path.join(root, "snapshot"))
+    cfg = UNetConfig.tiny()
+    av = arch_vector_for_budget(cfg, 0.6, hw=16)[0]
+    unet = UNet2DConditionModelPruned(cfg, av, dev, torch.float32, train=False, seed=3)
+    ck = os.path.join(root, "logs", "checkpoint-2")
+    unet.save_pretrained(os.path.join(ck, "unet"))
+    torch.save(unet.arch_vector, os.path.join(ck, "arch_vector.pt"))
+    path = os.path.join(root, yaml_name)
+    with open(path, "w") as f:
+        yaml.safe_dump({"seed": 43, "tiny": True, "pretrained_model_name_or_path": snap,
+                        "model": {"prediction_model": {"prediction_type": "v_prediction", "resolution": 64, "gated_ff": True,
+                                                       "ff_gate_width": 32, "random_init": True}},
+                        "training": {"mixed_precision": "no"}}, f)
+    return dict(root=root, snap=snap, ck=ck, yaml=path, sd=unet.state_dict())
 
 
 def image(h, w, seed):

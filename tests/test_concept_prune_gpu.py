@@ -11,7 +11,6 @@ import os
 
 import pytest
 import torch
-import yaml
 
 import concept_prune_fixtures as fx
 import data_fixtures
@@ -289,28 +288,13 @@ def _script(name, sub="baselines/concept_prune"):
 
 @pytest.fixture(scope="module")
 def tree(tmp_path_factory, dev):
-    """A snapshot directory (tokenizer only: VAE and text encoder are seeded), a pruned checkpoint directory and the YAML."""
-    from pdm.models.unet.spec import UNetConfig, arch_vector_for_budget
-    from pdm.models.unet.unet_2d_conditional import UNet2DConditionModelPruned
-    root = str(tmp_path_factory.mktemp("concept_prune"))
-    snap = data_fixtures.write_tokenizer(os.path.join(root, "snapshot"))
-    cfg = UNetConfig.tiny()
-    av = arch_vector_for_budget(cfg, 0.6, hw=16)[0]
-    unet = UNet2DConditionModelPruned(cfg, av, dev, torch.float32, train=False, seed=3)
-    ck = os.path.join(root, "logs", "checkpoint-2")
-    unet.save_pretrained(os.path.join(ck, "unet"))
-    torch.save(unet.arch_vector, os.path.join(ck, "arch_vector.pt"))
-    path = os.path.join(root, "cp.yaml")
-    with open(path, "w") as f:
-        yaml.safe_dump({"seed": 43, "tiny": True, "pretrained_model_name_or_path": snap,
-                        "model": {"prediction_model": {"prediction_type": "v_prediction", "resolution": 64, "gated_ff": True,
-                                                       "ff_gate_width": 32, "random_init": True}},
-                        "training": {"mixed_precision": "no"}}, f)
-    words = os.path.join(root, "words")
+    """data_fixtures.write_pruned_checkpoint_tree plus a two-word list."""
+    t = data_fixtures.write_pruned_checkpoint_tree(str(tmp_path_factory.mktemp("concept_prune")), dev, "cp.yaml")
+    words = os.path.join(t["root"], "words")
     os.makedirs(words)
     with open(os.path.join(words, "things.txt"), "w") as f:
         f.write("cat\ndog\n")
-    return dict(root=root, snap=snap, ck=ck, yaml=path, words=words, sd=unet.state_dict())
+    return dict(t, words=words)
 
 
 def test_scripts_on_a_tiny_snapshot(dev, tree):
@@ -364,9 +348,8 @@ def test_scripts_on_a_tiny_snapshot(dev, tree):
     erasure = _script("artist_erasure", "metrics")
     a = erasure.parse_args(["--target", "Monet", "--baseline", "concept-prune", "--base_config_path", tree["yaml"],
                             "--model_id", tree["snap"], "--original_ckpt", tree["ck"] + "/", "--ckpt_name", ckpt, "--tiny"])
-    from pdm.utils.config import load_config
-    config = load_config(tree["yaml"])
-    config.update({"pretrained_model_name_or_path": tree["snap"], "tiny": True})
+    from pdm.utils.load_models import inference_config
+    config = inference_config(tree["yaml"], tree["snap"], tiny=True)
     original, erased = E.load_pipelines(config, a, dev)
     got = erased.unet.state_dict()
     for n, v in sd.items():

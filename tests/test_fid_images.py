@@ -55,18 +55,18 @@ def test_scheduler_config_loaded_and_unsupported_values_raise(tmp_path):
     import torch
     from pdm.pipelines.pruning_pipelines import PNDMScheduler
     from pdm.utils.config import Cfg
-    m = _script()
+    from pdm.utils.load_models import load_scheduler
     d = tmp_path / "snap" / "scheduler"
     d.mkdir(parents=True)
     (d / "scheduler_config.json").write_text(json.dumps({**SD21, "num_train_timesteps": 500, "steps_offset": 0}))
-    s = m.load_scheduler(Cfg.wrap({"pretrained_model_name_or_path": str(tmp_path / "snap")}))
+    s = load_scheduler(Cfg.wrap({"pretrained_model_name_or_path": str(tmp_path / "snap")}))
     assert s.config.prediction_type == "v_prediction" and s.config.num_train_timesteps == 500 and s.config.steps_offset == 0
     assert torch.equal(s.alphas_cumprod, PNDMScheduler(num_train_timesteps=500).alphas_cumprod)
     s.set_timesteps(10)
     assert s.timesteps.tolist()[:3] == [450, 400, 400]
     # no file: SD-2.1 defaults with the config's prediction type
-    s = m.load_scheduler(Cfg.wrap({"pretrained_model_name_or_path": str(tmp_path / "none"),
-                                   "model": {"prediction_model": {"prediction_type": "epsilon"}}}))
+    s = load_scheduler(Cfg.wrap({"pretrained_model_name_or_path": str(tmp_path / "none"),
+                                 "model": {"prediction_model": {"prediction_type": "epsilon"}}}))
     assert s.config.prediction_type == "epsilon" and s.config.steps_offset == 1
     for bad in ({"skip_prk_steps": False}, {"beta_schedule": "linear"}, {"set_alpha_to_one": True},
                 {"prediction_type": "sample"}, {"trained_betas": [0.1]}, {"some_new_option": 1}):

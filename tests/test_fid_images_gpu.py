@@ -75,10 +75,12 @@ def _expected(m, argv, batches, dev):
     """{row: uint8 image} of the eager pipeline over the given batches of rows (numpy truncation of its float output)."""
     from pdm.utils.arg_utils import parse_args
     from pdm.utils.config import load_config
+    from pdm.utils.load_models import FrozenModels
     args = parse_args(argv[1:])
     config = load_config(args.base_config_path)
     config.update(vars(args))
-    pipe = m.load_pipeline(config, dev)
+    models = FrozenModels(config, dev)
+    pipe = models.pipeline(models.load_unet(config.finetuning_ckpt_dir))
     caps, _ = m.validation_rows(config)
     out = {}
     for rows in batches:

@@ -13,7 +13,6 @@ import os
 import numpy as np
 import pytest
 import torch
-import yaml
 
 import data_fixtures
 import uce_fixtures as fx
@@ -235,36 +234,16 @@ def _script(name, sub):
 
 @pytest.fixture(scope="module")
 def tree(tmp_path_factory, dev):
-    """A snapshot directory (tokenizer only: VAE and text encoder are seeded), a pruned checkpoint directory and the YAML."""
-    from pdm.models.unet.spec import UNetConfig, arch_vector_for_budget
-    from pdm.models.unet.unet_2d_conditional import UNet2DConditionModelPruned
-    from pdm.utils import erasure_utils as E
-    from pdm.utils.config import load_config
-    from pdm.utils.data import load_tokenizer
-    root = str(tmp_path_factory.mktemp("uce"))
-    snap = data_fixtures.write_tokenizer(os.path.join(root, "snapshot"))
-    cfg = UNetConfig.tiny()
-    av = arch_vector_for_budget(cfg, 0.6, hw=16)[0]
-    unet = UNet2DConditionModelPruned(cfg, av, dev, torch.float32, train=False, seed=3)
-    ck = os.path.join(root, "logs", "checkpoint-2")
-    unet.save_pretrained(os.path.join(ck, "unet"))
-    torch.save(unet.arch_vector, os.path.join(ck, "arch_vector.pt"))
-    path = os.path.join(root, "uce.yaml")
-    with open(path, "w") as f:
-        yaml.safe_dump({"seed": 43, "tiny": True, "pretrained_model_name_or_path": snap,
-                        "model": {"prediction_model": {"prediction_type": "v_prediction", "resolution": 64, "gated_ff": True,
-                                                       "ff_gate_width": 32, "random_init": True}},
-                        "training": {"mixed_precision": "no"}}, f)
-    config = load_config(path)
-    config.update({"pretrained_model_name_or_path": snap, "tiny": True})
-    models = E.load_frozen_models(config, dev)
-    return dict(root=root, snap=snap, ck=ck, yaml=path, sd=unet.state_dict(), config=config, models=models,
-                tokenizer=load_tokenizer(snap))
+    """data_fixtures.write_pruned_checkpoint_tree plus the script's config and the frozen models over it."""
+    from pdm.utils.load_models import FrozenModels, inference_config
+    t = data_fixtures.write_pruned_checkpoint_tree(str(tmp_path_factory.mktemp("uce")), dev, "uce.yaml")
+    config = inference_config(t["yaml"], t["snap"], tiny=True)
+    models = FrozenModels(config, dev)
+    return dict(t, config=config, models=models, tokenizer=models.tokenizer)
 
 
 def _load(tree):
-    from pdm.utils import erasure_utils as E
-    return E._load_unet(tree["models"], tree["config"], tree["ck"])
+    return tree["models"].load_unet(tree["ck"])
 
 
 def _is_kv(name):

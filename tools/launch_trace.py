@@ -2,12 +2,15 @@
 """Fingerprint of the library-call sequence of the host side: the check that a refactor of the Python above libpdmk did not
 change what is launched.  Every function of `_pdmk._SIGS` is wrapped on `_pdmk._lib`; a call is recorded as its name, every
 non-pointer argument, and for a pointer only whether it is null (pdmk_gemm_args: the same rule over the struct's fields, for
-every problem of a grouped launch).  Four tiny scenarios, per scenario the call count and a sha256 of the record:
+every problem of a grouped launch).  Tiny scenarios, per scenario the call count and a sha256 of the record:
   unet-f32 / unet-bf16  tests/dp_worker.py's recipe: tiny U-Net, arch vector 0.55, B = 2, 16x16 latent, 13x64 text; one eager
                         main step + AdamW, one upper step + its AdamW
   vae-bf16              the tiny VAE of tests/test_vae_gpu.py: encode_latents, decode
   clip-text-bf16        the tiny CLIPTextModel of tests/test_clip_gpu.py, one call
   clip-model-f32        the tiny CLIPModel of tests/test_clip_model_gpu.py: encode_image, encode_text
+  sample-pndm-f32 /     StableDiffusionPruningPipeline over a seeded tiny U-Net (budget 0.6) and VAE: B = 1, 16x16 latent, 13x64
+  sample-ddim-f32       text embeddings, 4 steps, guidance 7.5, the eager loop, latents out - every scheduler step's pdmk_axpby
+                        coefficients are in the record
 GEMM plans come from the untuned decision tree and the CLIP towers run eagerly (PDMK_GEMM_TUNE=0, PDMK_CLIP_GRAPH=0, set
 here), so two runs of one commit print the same digests.  It touches only `_pdmk` and the public model classes: the same file
 runs on an older checkout.  What the digest does not see: anything behind a pointer other than pdmk_gemm_args - the
@@ -111,12 +114,28 @@ def clip_model():
     m.encode_text(_ids())
 
 
+def sample(scheduler):
+    from pdm.models.unet.spec import UNetConfig, arch_vector_for_budget
+    from pdm.models.unet.unet_2d_conditional import UNet2DConditionModelPruned
+    from pdm.models.vae.autoencoder_kl import AutoencoderKL, VAEConfig
+    from pdm.pipelines import pruning_pipelines as P
+    cfg = UNetConfig.tiny()
+    unet = UNet2DConditionModelPruned(cfg, arch_vector_for_budget(cfg, 0.6, hw=16)[0], "cuda:0", torch.float32, train=False, seed=3)
+    vae = AutoencoderKL(VAEConfig(block_out_channels=(32, 64, 64), layers_per_block=1), "cuda:0", torch.float32, seed=7)
+    pipe = P.StableDiffusionPruningPipeline(vae, None, unet, getattr(P, scheduler)(prediction_type="v_prediction"))
+    g = torch.Generator().manual_seed(4)
+    pe, ne, lat = torch.randn(1, 13, 64, generator=g), torch.randn(1, 13, 64, generator=g), torch.randn(1, 4, 16, 16, generator=g)
+    pipe(prompt_embeds=pe.cuda(), negative_prompt_embeds=ne.cuda(), latents=lat.cuda(), num_inference_steps=4, guidance_scale=7.5,
+         graph=False, output_type="latent")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--dump", help="directory for one text file per scenario, one call per line")
     a = ap.parse_args()
     for name, fn in (("unet-f32", lambda: unet(torch.float32)), ("unet-bf16", lambda: unet(torch.bfloat16)), ("vae-bf16", vae),
-                     ("clip-text-bf16", clip_text), ("clip-model-f32", clip_model)):
+                     ("clip-text-bf16", clip_text), ("clip-model-f32", clip_model),
+                     ("sample-pndm-f32", lambda: sample("PNDMScheduler")), ("sample-ddim-f32", lambda: sample("DDIMScheduler"))):
         del CALLS[:]
         fn()
         torch.cuda.synchronize()

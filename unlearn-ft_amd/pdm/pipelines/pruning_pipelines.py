@@ -27,61 +27,78 @@ from .. import _pdmk as k
 from ..models.unet.spec import padc
 
 
-class PNDMScheduler:
-    """diffusers PNDMScheduler as configured by SD-2.1's scheduler_config.json (skip_prk_steps, steps_offset 1,
-    set_alpha_to_one False, scaled_linear betas)."""
+# Adams-Bashforth weights of the linear multistep update by history length, newest model output first (PLMS)
+_PLMS_COEF = {2: (3 / 2, -1 / 2), 3: (23 / 12, -16 / 12, 5 / 12), 4: (55 / 24, -59 / 24, 37 / 24, -9 / 24)}
+
+
+class _Scheduler:
+    """What the two schedulers share: SD-2.1's scaled_linear betas, the `config` namespace, the strict `from_config` and the
+    identity `scale_model_input`.  A subclass sets the key tables and has `set_timesteps` and `step`."""
     order = 1
     init_noise_sigma = 1.0
-    # scheduler_config.json keys whose value this class does not implement otherwise: the value it implements
-    _FIXED = {"beta_schedule": "scaled_linear", "skip_prk_steps": True, "set_alpha_to_one": False, "trained_betas": None,
-              "clip_sample": False, "timestep_spacing": "leading"}
-    _FREE = ("num_train_timesteps", "beta_start", "beta_end", "steps_offset", "prediction_type")
+    _FIXED = {}          # config keys whose value the class does not implement otherwise: the value it implements
+    _FREE = ("num_train_timesteps", "beta_start", "beta_end", "steps_offset", "prediction_type")      # __init__'s arguments
+    _IGNORED = ()        # keys read only by what _FIXED turns off, or by the other class
 
     def __init__(self, num_train_timesteps=1000, beta_start=0.00085, beta_end=0.012, steps_offset=1,
                  prediction_type="epsilon"):
+        if prediction_type not in ("epsilon", "v_prediction"):
+            raise ValueError(f"{type(self).__name__}: prediction_type={prediction_type!r} is not implemented")
         betas = torch.linspace(beta_start ** 0.5, beta_end ** 0.5, num_train_timesteps, dtype=torch.float32) ** 2
         self.alphas_cumprod = torch.cumprod(1.0 - betas, dim=0).double()
         self.final_alpha_cumprod = self.alphas_cumprod[0]
         self.config = SimpleNamespace(num_train_timesteps=num_train_timesteps, steps_offset=steps_offset,
-                                      prediction_type=prediction_type, skip_prk_steps=True)
+                                      prediction_type=prediction_type)
         self.timesteps = None
 
     @classmethod
     def from_config(cls, config):
-        """From a diffusers scheduler_config.json dict (or its path).  Keys starting with "_" are ignored; a value this
-        class does not implement (PRK steps, another beta schedule, set_alpha_to_one, ...) or an unknown key raises."""
+        """From a diffusers scheduler_config.json dict (or its path).  Keys starting with "_" and the class's _IGNORED ones
+        are skipped; a value this class does not implement (PRK steps, another beta schedule, set_alpha_to_one, clipping,
+        thresholding, trailing spacing, ...) or an unknown key raises."""
         if isinstance(config, str):
             with open(config) as f:
                 config = json.load(f)
         kw = {}
         for key, v in config.items():
-            if key.startswith("_"):
+            if key.startswith("_") or key in cls._IGNORED:
                 continue
             if key in cls._FIXED:
                 if v != cls._FIXED[key]:
-                    raise ValueError(f"PNDMScheduler: {key}={v!r} is not implemented (only {cls._FIXED[key]!r})")
+                    raise ValueError(f"{cls.__name__}: {key}={v!r} is not implemented (only {cls._FIXED[key]!r})")
             elif key in cls._FREE:
                 kw[key] = v
             else:
-                raise ValueError(f"PNDMScheduler: config key {key!r} is not implemented")
-        if kw.get("prediction_type", "epsilon") not in ("epsilon", "v_prediction"):
-            raise ValueError(f"PNDMScheduler: prediction_type={kw['prediction_type']!r} is not implemented")
+                raise ValueError(f"{cls.__name__}: config key {key!r} is not implemented")
         return cls(**kw)
 
-    def set_timesteps(self, num_inference_steps, device=None):
-        self.num_inference_steps = num_inference_steps
-        ratio = self.config.num_train_timesteps // num_inference_steps
-        base = (torch.arange(0, num_inference_steps) * ratio).round().long() + self.config.steps_offset
-        self.timesteps = torch.cat([base[:-1], base[-2:-1], base[-1:]]).flip(0)
-        self.ets, self.counter, self.cur_sample = [], 0, None
+    def _ratio(self):
+        return self.config.num_train_timesteps // self.num_inference_steps
 
     def scale_model_input(self, sample, t=None):
         return sample
 
+
+class PNDMScheduler(_Scheduler):
+    """diffusers PNDMScheduler as configured by SD-2.1's scheduler_config.json (skip_prk_steps, steps_offset 1,
+    set_alpha_to_one False, scaled_linear betas)."""
+    _FIXED = {"beta_schedule": "scaled_linear", "skip_prk_steps": True, "set_alpha_to_one": False, "trained_betas": None,
+              "clip_sample": False, "timestep_spacing": "leading"}
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        self.config.skip_prk_steps = True
+
+    def set_timesteps(self, num_inference_steps, device=None):
+        self.num_inference_steps = num_inference_steps
+        base = (torch.arange(0, num_inference_steps) * self._ratio()).round().long() + self.config.steps_offset
+        self.timesteps = torch.cat([base[:-1], base[-2:-1], base[-1:]]).flip(0)
+        self.ets, self.counter, self.cur_sample = [], 0, None
+
     def step(self, model_output, timestep, sample, return_dict=True):
         """model_output / sample: contiguous fp32 device tensors of one shape; returns the previous sample (new tensor)."""
         t = int(timestep)
-        ratio = self.config.num_train_timesteps // self.num_inference_steps
+        ratio = self._ratio()
         prev_t = t - ratio
         if self.counter != 1:
             self.ets = self.ets[-3:] + [model_output]
@@ -95,7 +112,7 @@ class PNDMScheduler:
             k.axpby(e[-1], mo, 0.5, 0.5)                                   # (model_output + ets[-1]) / 2
             sample, self.cur_sample = self.cur_sample, None
         else:
-            coef = {2: (3 / 2, -1 / 2), 3: (23 / 12, -16 / 12, 5 / 12), 4: (55 / 24, -59 / 24, 37 / 24, -9 / 24)}[len(e)]
+            coef = _PLMS_COEF[len(e)]
             mo.copy_(e[-1])
             k.axpby(e[-2], mo, coef[1], coef[0])
             for i in range(2, len(e)):
@@ -111,8 +128,6 @@ class PNDMScheduler:
     def _scalars(self, t, prev_t):
         """The step's coefficients (float64, then Python floats; fp32 where a kernel takes them): the v -> eps conversion
         (sqrt(1 - a_t), sqrt(a_t)) and prev = x_scale * sample + eps_scale * eps."""
-        if self.config.prediction_type not in ("epsilon", "v_prediction"):
-            raise ValueError(f"prediction_type {self.config.prediction_type!r} must be epsilon or v_prediction")
         a_t = self.alphas_cumprod[t]
         a_prev = self.alphas_cumprod[prev_t] if prev_t >= 0 else self.final_alpha_cumprod
         b_t, b_prev = 1 - a_t, 1 - a_prev
@@ -123,8 +138,7 @@ class PNDMScheduler:
     def plms_rows(self):
         """The schedule of set_timesteps() as pdmk_plms_row entries: what step() does at each index, its history (`ets`,
         at most 4 entries) kept in 4 ring slots.  The scalars are step()'s own (_scalars)."""
-        ratio = self.config.num_train_timesteps // self.num_inference_steps
-        coefs = {2: (3 / 2, -1 / 2), 3: (23 / 12, -16 / 12, 5 / 12), 4: (55 / 24, -59 / 24, 37 / 24, -9 / 24)}
+        ratio = self._ratio()
         rows, appended = [], 0                        # appended: entries ever added to ets (step() skips counter 1)
         for i, t in enumerate(self.timesteps.tolist()):
             r = k.PlmsRow(t=int(t), vpred=int(self.config.prediction_type == "v_prediction"))
@@ -142,14 +156,14 @@ class PNDMScheduler:
                 for j in range(3):
                     r.rslot[j] = (appended - 2 - j) % 4
                 if r.mode == 2:
-                    for j, c in enumerate(coefs[r.nterms]):
+                    for j, c in enumerate(_PLMS_COEF[r.nterms]):
                         r.coef[j] = c
             r.v_x, r.v_v, r.eps_scale, r.x_scale = self._scalars(t, prev_t)
             rows.append(r)
         return rows
 
 
-class DDIMScheduler:
+class DDIMScheduler(_Scheduler):
     """diffusers DDIMScheduler with eta = 0 (deterministic, one U-Net call per step - what ConceptPrune's per-timestep
     accumulators count on) as SD-2.1's DDIM scheduler_config.json sets it, as far as that file can be recalled here:
     scaled_linear betas 0.00085 ... 0.012, steps_offset 1, clip_sample false, set_alpha_to_one false, leading timestep spacing.
@@ -160,56 +174,18 @@ class DDIMScheduler:
         v_prediction:  prev = (sqrt(a_p a_t) + sqrt(b_p b_t)) x + (sqrt(b_p a_t) - sqrt(a_p b_t)) v
     (x0 and eps substituted into sqrt(a_p) x0 + sqrt(b_p) eps): linear in (sample, model_output), so the coefficients are
     formed in float64 on the host and the step is one pdmk_axpby launch."""
-    order = 1
-    init_noise_sigma = 1.0
     _FIXED = {"beta_schedule": "scaled_linear", "set_alpha_to_one": False, "trained_betas": None, "clip_sample": False,
               "timestep_spacing": "leading", "thresholding": False, "rescale_betas_zero_snr": False}
-    _FREE = ("num_train_timesteps", "beta_start", "beta_end", "steps_offset", "prediction_type")
-    # read only by what _FIXED turns off, or by PNDM (SD-2.1's file carries PNDM's skip_prk_steps beside DDIM's class name)
+    # SD-2.1's file carries PNDM's skip_prk_steps beside DDIM's class name
     _IGNORED = ("clip_sample_range", "dynamic_thresholding_ratio", "sample_max_value", "skip_prk_steps")
-
-    def __init__(self, num_train_timesteps=1000, beta_start=0.00085, beta_end=0.012, steps_offset=1,
-                 prediction_type="epsilon"):
-        if prediction_type not in ("epsilon", "v_prediction"):
-            raise ValueError(f"DDIMScheduler: prediction_type={prediction_type!r} is not implemented")
-        betas = torch.linspace(beta_start ** 0.5, beta_end ** 0.5, num_train_timesteps, dtype=torch.float32) ** 2
-        self.alphas_cumprod = torch.cumprod(1.0 - betas, dim=0).double()
-        self.final_alpha_cumprod = self.alphas_cumprod[0]
-        self.config = SimpleNamespace(num_train_timesteps=num_train_timesteps, steps_offset=steps_offset,
-                                      prediction_type=prediction_type)
-        self.timesteps = None
-
-    @classmethod
-    def from_config(cls, config):
-        """From a diffusers scheduler_config.json dict (or its path).  Keys starting with "_" are ignored; a value this class
-        does not implement (another beta schedule, clipping, thresholding, trailing spacing, ...) or an unknown key raises."""
-        if isinstance(config, str):
-            with open(config) as f:
-                config = json.load(f)
-        kw = {}
-        for key, v in config.items():
-            if key.startswith("_") or key in cls._IGNORED:
-                continue
-            if key in cls._FIXED:
-                if v != cls._FIXED[key]:
-                    raise ValueError(f"DDIMScheduler: {key}={v!r} is not implemented (only {cls._FIXED[key]!r})")
-            elif key in cls._FREE:
-                kw[key] = v
-            else:
-                raise ValueError(f"DDIMScheduler: config key {key!r} is not implemented")
-        return cls(**kw)
 
     def set_timesteps(self, num_inference_steps, device=None):
         self.num_inference_steps = num_inference_steps
-        ratio = self.config.num_train_timesteps // num_inference_steps
-        self.timesteps = ((torch.arange(0, num_inference_steps) * ratio).round().long() + self.config.steps_offset).flip(0)
-
-    def scale_model_input(self, sample, t=None):
-        return sample
+        self.timesteps = ((torch.arange(0, num_inference_steps) * self._ratio()).round().long() + self.config.steps_offset).flip(0)
 
     def coefficients(self, t):
         """(c_x, c_m) with prev = c_x * sample + c_m * model_output, float64 arithmetic, Python floats."""
-        prev_t = t - self.config.num_train_timesteps // self.num_inference_steps
+        prev_t = t - self._ratio()
         a_t = self.alphas_cumprod[t]
         a_p = self.alphas_cumprod[prev_t] if prev_t >= 0 else self.final_alpha_cumprod
         b_t, b_p = 1 - a_t, 1 - a_p

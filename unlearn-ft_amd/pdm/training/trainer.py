@@ -23,20 +23,13 @@ import time
 import torch
 import torch.distributed as dist
 
-from ..models.unet.spec import UNetConfig, arch_vector_for_budget
+from ..models.unet.spec import arch_vector_for_budget
 from ..models.unet.unet_2d_conditional import UNet2DConditionModelPruned
+from ..utils.config import cfg_get as _cfg
+from ..utils.load_models import FrozenModels, unet_kwargs
 from .bilevel import BilevelStepper
 
 logger = logging.getLogger("pdm.trainer")
-
-
-def _cfg(config, path, default=None):
-    cur = config
-    for part in path.split("."):
-        if cur is None:
-            return default
-        cur = cur.get(part) if isinstance(cur, dict) else getattr(cur, part, None)
-    return default if cur is None else cur
 
 
 class SyntheticBatches:
@@ -76,7 +69,8 @@ class Trainer:
         self.device = torch.device("cuda", local)
         self.logging_dir = _cfg(config, "training.logging.logging_dir", _cfg(config, "logging_dir", "logs"))
         self.global_step = 0
-        self.init_weight_dtype()
+        self.models = FrozenModels(config, self.device)      # weight dtype, topology, frozen VAE / text encoder / tokenizer
+        self._empty_cache = {}                               # empty-prompt embeddings by token row (_prompt_embeds)
         self.init_models()
         self.init_optimizer()
         self.train_dataloader = train_dataloader or self.init_dataloader(upper=False)
@@ -100,52 +94,16 @@ class Trainer:
             if self.max_grad_norm is not None or pert:
                 raise ValueError("training.hip_graphs does not support clip_grad_norm / input_perturbation (use eager mode)")
 
-    # ---- frozen VAE (trainer.py:2128-2131, cast to the weight dtype :516-527); built on first use
     @property
     def vae_factor(self):
         return 4 if _cfg(self.config, "tiny", False) else 8
 
-    def _allow_random(self, what, path):
-        """Random weights / a random arch vector stand in for missing files only when asked for (`--synthetic`, or
-        `model.prediction_model.random_init` like the reference's random_init path, unet_2d_conditional.py:2406-2408).
-        Otherwise a missing checkpoint is an error, as in the reference (every from_pretrained there raises)."""
-        if bool(_cfg(self.config, "synthetic", False)) or bool(_cfg(self.config, "model.prediction_model.random_init", False)):
-            return True
-        raise FileNotFoundError(
-            f"{what}: {path!r} is not a local directory / file (hub downloads are not available to this build); pass a local "
-            f"snapshot laid out like the hub's, or run with --synthetic / model.prediction_model.random_init for random weights")
-
-    @property
-    def vae(self):
-        if getattr(self, "_vae", None) is None:
-            from ..models.vae.autoencoder_kl import AutoencoderKL, VAEConfig
-            root = _cfg(self.config, "pretrained_model_name_or_path")
-            local = bool(root) and os.path.isdir(os.path.join(root, "vae"))
-            if not local:
-                self._allow_random("VAE", os.path.join(str(root), "vae"))
-            vcfg = VAEConfig(block_out_channels=(32, 64, 64), layers_per_block=1) if _cfg(self.config, "tiny", False) else None
-            self._vae = AutoencoderKL.from_pretrained(root if local else None, subfolder="vae", random_init=not local,
-                                                      vae_config=vcfg, torch_dtype=self.weight_dtype, device=self.device)
-        return self._vae
-
-    # ---- frozen CLIP text encoder (trainer.py:2126-2131); built on first use
-    @property
-    def text_encoder(self):
-        if getattr(self, "_text_encoder", None) is None:
-            from ..models.clip.text_encoder import CLIPTextModel, CLIPTextConfig
-            root = _cfg(self.config, "pretrained_model_name_or_path")
-            local = bool(root) and os.path.isdir(os.path.join(root, "text_encoder"))
-            if not local:
-                self._allow_random("text encoder", os.path.join(str(root), "text_encoder"))
-            tcfg = None
-            if _cfg(self.config, "tiny", False):
-                tcfg = CLIPTextConfig(vocab_size=1000, hidden_size=self.unet_config.cross_attention_dim, intermediate_size=256,
-                                      num_hidden_layers=2, num_attention_heads=self.unet_config.cross_attention_dim // 64)
-            self._text_encoder = CLIPTextModel.from_pretrained(root if local else None, subfolder="text_encoder",
-                                                               random_init=not local, text_config=tcfg,
-                                                               torch_dtype=self.weight_dtype, device=self.device)
-            self._empty_cache = {}
-        return self._text_encoder
+    # ---- what `models` holds, under the names the trainer has always had
+    vae = property(lambda self: self.models.vae)
+    text_encoder = property(lambda self: self.models.text_encoder)
+    tokenizer = property(lambda self: self.models.tokenizer)
+    weight_dtype = property(lambda self: self.models.weight_dtype)
+    unet_config = property(lambda self: self.models.unet_config)
 
     @staticmethod
     def _is_empty(batch):
@@ -175,18 +133,10 @@ class Trainer:
             self._empty_cache[row] = enc(ids[:1])[0]
         return self._empty_cache[row].expand(ids.shape[0], -1, -1).contiguous()
 
-    # ---- trainer.py:516-527: student master weights fp32; bf16 compute under mixed precision
-    def init_weight_dtype(self):
-        mp = _cfg(self.config, "mixed_precision", None) or _cfg(self.config, "training.mixed_precision", None)
-        self.weight_dtype = {"bf16": torch.bfloat16, "no": torch.float32, None: torch.float32}.get(mp)
-        if self.weight_dtype is None:
-            raise ValueError(f"mixed_precision={mp!r} is not supported on this build (use bf16 or no)")
-
     # ---- trainer.py:2122-2198
     def init_models(self):
         c = self.config
-        ucfg = UNetConfig.tiny() if _cfg(c, "tiny", False) else UNetConfig.sd21()
-        self.unet_config = ucfg
+        ucfg = self.unet_config
         ckpt = _cfg(c, "pruning_ckpt_dir")
         arch = None
         if ckpt and os.path.exists(os.path.join(ckpt, "quantizer_embeddings.pt")):
@@ -195,7 +145,7 @@ class Trainer:
         elif ckpt and os.path.exists(os.path.join(ckpt, "arch_vector.pt")):
             arch = torch.load(os.path.join(ckpt, "arch_vector.pt"), map_location="cpu")
         else:
-            self._allow_random("pruning checkpoint (quantizer_embeddings.pt / arch_vector.pt)", ckpt)
+            self.models.allow_random("pruning checkpoint (quantizer_embeddings.pt / arch_vector.pt)", ckpt)
             res = int(_cfg(c, "model.prediction_model.resolution", 512)) // 8
             arch, ratio, _ = arch_vector_for_budget(ucfg, float(_cfg(c, "keep_ratio", 0.55)), hw=res)
             logger.info("no pruning checkpoint: random arch vector at MAC budget %.3f", ratio)
@@ -204,12 +154,10 @@ class Trainer:
         root = _cfg(c, "pretrained_model_name_or_path")
         local = bool(root) and os.path.isdir(os.path.join(root, "unet"))
         if not local:
-            self._allow_random("U-Net", os.path.join(str(root), "unet"))
-        kw = dict(unet_config=ucfg, torch_dtype=self.weight_dtype, device=self.device,
-                  down_block_types=pm.get("unet_down_blocks"), up_block_types=pm.get("unet_up_blocks"),
-                  mid_block_type=pm.get("unet_mid_block"),
-                  attention_precision=pm.get("attention_precision", _cfg(c, "attention_precision")),
-                  gated_ff=pm.get("gated_ff", True), ff_gate_width=pm.get("ff_gate_width", 32))
+            self.models.allow_random("U-Net", os.path.join(str(root), "unet"))
+        kw = dict(unet_config=ucfg, torch_dtype=self.weight_dtype, device=self.device, **unet_kwargs(c))
+        if "attention_precision" not in pm:          # the trainer's own fallback: a root-level `attention_precision`
+            kw["attention_precision"] = _cfg(c, "attention_precision")
         self.teacher_model = UNet2DConditionModelPruned.from_pretrained(root if local else None, subfolder="unet",
                                                                         arch_vector=None, random_init=not local,
                                                                         train=False, seed=0, **kw)
@@ -273,8 +221,6 @@ class Trainer:
         transformed to `resolution // 8 * vae_factor` pixels, so the latents are resolution // 8 wide as with --synthetic."""
         from ..utils import data as D
         c = self.config
-        if getattr(self, "tokenizer", None) is None:
-            self.tokenizer = D.load_tokenizer(_cfg(c, "pretrained_model_name_or_path"))
         dl = lambda key, d=None: _cfg(c, "data.dataloader." + key, d)
         res = int(_cfg(c, "model.prediction_model.resolution", 512)) // 8 * self.vae_factor
         bs = int(dl("train_batch_size", 8))
@@ -413,10 +359,10 @@ class Trainer:
 
     # ---- image logging (trainer.py:2543-2575 generate_samples_from_prompts; called every image_logging_steps, :2851-2859)
     def get_pipeline(self):
-        from ..pipelines.pruning_pipelines import PNDMScheduler, StableDiffusionPruningPipeline
+        from ..pipelines.pruning_pipelines import PNDMScheduler
         pt = _cfg(self.config, "model.prediction_model.prediction_type", "v_prediction")
-        return StableDiffusionPruningPipeline(self.vae, self.text_encoder, self.prediction_model,
-                                              PNDMScheduler(prediction_type=pt))
+        # the SD-2.1 defaults, not the snapshot's scheduler file; prompts arrive as token ids or embeddings
+        return self.models.pipeline(self.prediction_model, scheduler=PNDMScheduler(prediction_type=pt), tokenizer=False)
 
     def generate_samples_from_prompts(self):
         """Samples every prompt batch with the current student (PNDM, `training.num_inference_steps`, guidance 7.5, the

@@ -16,6 +16,8 @@ from types import SimpleNamespace
 
 import torch
 
+from .load_models import golden_path
+
 HOOK_MODULES = ("unet",)
 HOOK_MODULES_NOT_BUILT = ("text", "unet-ffn-1", "attn_key", "attn_val")
 ART_TARGETS = ("painting", "Van Gogh", "Monet", "Pablo Picasso", "Salvador Dali", "Leonardo Da Vinci")
@@ -50,8 +52,7 @@ def target_type(target):
 
 
 def default_words_dir():
-    root = os.path.dirname(os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
-    return os.path.join(root, "tests", "golden", "concept_prune")
+    return golden_path("concept_prune")
 
 
 def read_words(path):
@@ -223,24 +224,7 @@ class observing:
         self.engine.ffn_observer = self.before
 
 
-# ---- pipeline and observation (GPU)
-def load_pipeline(config, ckpt_path, device, scheduler="ddim"):
-    """The pruned checkpoint `ckpt_path` (arch_vector.pt + unet/) in a sampling pipeline, as artist_erasure.py loads it."""
-    from ..pipelines.pruning_pipelines import DDIMScheduler, PNDMScheduler, StableDiffusionPruningPipeline
-    from .data import load_tokenizer
-    from .erasure_utils import _load_unet, load_frozen_models
-    models = load_frozen_models(config, device)
-    unet = _load_unet(models, config, ckpt_path)
-    root = config.get_path("pretrained_model_name_or_path")
-    cls = {"ddim": DDIMScheduler, "pndm": PNDMScheduler}[scheduler]
-    sched_file = os.path.join(str(root), "scheduler", "scheduler_config.json")
-    if os.path.exists(sched_file):
-        sch = cls.from_config(sched_file)
-    else:
-        sch = cls(prediction_type=config.get_path("model.prediction_model.prediction_type", "v_prediction"))
-    return StableDiffusionPruningPipeline(models.vae, models.text_encoder, unet, sch, load_tokenizer(root))
-
-
+# ---- observation (GPU)
 @torch.no_grad()
 def observe(pipe, obs_base, obs_target, base_prompts, target_prompts, seed, steps, resolution, images_dir=None):
     """One image per prompt of every pair from the same seed (guidance 7.5, the doubled batch), the base prompt's activations

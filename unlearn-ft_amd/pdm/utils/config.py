@@ -30,6 +30,16 @@ class Cfg(dict):
         return cur
 
 
+def cfg_get(config, path, default=None):
+    """`get_path` for any config a trainer accepts: nested dicts (a `Cfg` or plain) or attribute namespaces."""
+    cur = config
+    for part in path.split("."):
+        if cur is None:
+            return default
+        cur = cur.get(part) if isinstance(cur, dict) else getattr(cur, part, None)
+    return default if cur is None else cur
+
+
 def load_config(path):
     with open(path) as f:
         return Cfg.wrap(yaml.safe_load(f) or {})

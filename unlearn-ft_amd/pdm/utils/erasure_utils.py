@@ -4,8 +4,9 @@ benchmarking/benchmarking_utils.py): for every prompt of an artist one image of 
 similarity and the share of prompts whose erased image is less similar to the prompt than the original one.
 
 Host side (no GPU needed): the prompt CSV, the result path rules, the ESD checkpoint rewriting, the pairing of the image
-files and the statistics.  GPU side: `generate` (two StableDiffusionPruningPipelines that share VAE, text encoder and tokenizer;
-the text encoder runs once per prompt) and `score` (pdm/utils/clip_utils.py's decode / pack / prep, the HIP CLIP towers and
+files and the statistics.  GPU side: `load_pipelines` (which checkpoint a --baseline means; the models come from
+pdm/utils/load_models.py), `generate` (two StableDiffusionPruningPipelines that share VAE, text encoder and tokenizer; the text
+encoder runs once per prompt) and `score` (pdm/utils/clip_utils.py's decode / pack / prep, the HIP CLIP towers and
 pdmk_cosine_pairs, one read-back at the end).  Nothing here imports pandas, diffusers or transformers' CLIPModel.
 """
 import csv
@@ -16,6 +17,8 @@ import os
 import numpy as np
 import torch
 
+from .load_models import FrozenModels, golden_path
+
 logger = logging.getLogger("pdm.erasure")
 
 BASELINES = ("pdm", "pruned_baseline", "esd", "uce", "concept-prune")
@@ -25,8 +28,7 @@ GUIDANCE = 7.5
 
 # ---- prompts
 def default_prompts_csv(target):
-    root = os.path.dirname(os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
-    return os.path.join(root, "tests", "golden", "artist_prompts", f"test_{target}.csv")
+    return golden_path("artist_prompts", f"test_{target}.csv")
 
 
 def read_prompts(path):
@@ -102,11 +104,12 @@ def esd_state_dict(nested):
     return flat
 
 
-def load_erasure_checkpoint(unet, path):
-    """'esd' in the path: the nested form, overlaid on the model's weights; otherwise a full state dict, loaded strictly."""
+def load_erasure_checkpoint(unet, path, esd=None):
+    """esd (None: 'esd' in the path): the nested form, overlaid on the model's weights; otherwise a full state dict, loaded
+    strictly."""
     logger.info("Loading erasure model from %s", path)
     st = torch.load(path, map_location="cpu")
-    if "esd" in path:
+    if ("esd" in path) if esd is None else esd:
         unet.overlay_state_dict(esd_state_dict(st))
     else:
         unet.load_state_dict(st)
@@ -199,60 +202,21 @@ def image_resolution(model_id, fallback):
     return int(fallback)
 
 
-def _load_unet(models, config, ckpt_dir):
-    """The pruned student of a trainer checkpoint directory: arch_vector.pt + unet/diffusion_pytorch_model.safetensors."""
-    from ..models.unet.unet_2d_conditional import UNet2DConditionModelPruned
-    pm = config.get_path("model.prediction_model", {}) or {}
-    arch = torch.load(os.path.join(ckpt_dir, "arch_vector.pt"), map_location="cpu")
-    return UNet2DConditionModelPruned.from_pretrained(
-        ckpt_dir, subfolder="unet", arch_vector=arch, unet_config=models.unet_config, torch_dtype=models.weight_dtype,
-        device=models.device, down_block_types=pm.get("unet_down_blocks"), up_block_types=pm.get("unet_up_blocks"),
-        mid_block_type=pm.get("unet_mid_block"), gated_ff=pm.get("gated_ff", True), ff_gate_width=pm.get("ff_gate_width", 32),
-        attention_precision=pm.get("attention_precision"), train=False)
-
-
-def load_frozen_models(config, device):
-    """VAE, text encoder, weight dtype and U-Net topology by the trainer's rules, without the trainer's set-up."""
-    from ..models.unet.spec import UNetConfig
-    from ..training.trainer import Trainer
-    models = Trainer.__new__(Trainer)
-    models.config, models.device = config, device
-    models.init_weight_dtype()
-    models.unet_config = UNetConfig.tiny() if config.get_path("tiny", False) else UNetConfig.sd21()
-    return models
-
-
 def load_pipelines(config, args, device):
     """(original, erased) pipelines sharing VAE, text encoder, tokenizer and scheduler settings."""
-    from ..pipelines.pruning_pipelines import PNDMScheduler, StableDiffusionPruningPipeline
-    from .data import load_tokenizer
-    models = load_frozen_models(config, device)
-    original = _load_unet(models, config, args.original_ckpt)
+    models = FrozenModels(config, device)
+    original = models.load_unet(args.original_ckpt)
     if args.baseline == "pdm":
         if args.ckpt_name is None:
             raise ValueError("--baseline pdm needs --ckpt_name (the fine-tuned checkpoint directory)")
-        erased = _load_unet(models, config, args.ckpt_name)
+        erased = models.load_unet(args.ckpt_name)
     elif args.baseline == "pruned_baseline":
         erased = original
     else:                                             # esd, uce, concept-prune
         if args.ckpt_name is None:
             raise ValueError(f"--baseline {args.baseline} needs --ckpt_name (the erasure checkpoint file)")
-        erased = _load_unet(models, config, args.original_ckpt)
-        if args.baseline == "esd":
-            erased.overlay_state_dict(esd_state_dict(torch.load(args.ckpt_name, map_location="cpu")))
-        else:
-            erased.load_state_dict(torch.load(args.ckpt_name, map_location="cpu"))
-    root = config.get_path("pretrained_model_name_or_path")
-    tok = load_tokenizer(root)
-    sched_file = os.path.join(str(root), "scheduler", "scheduler_config.json")
-
-    def scheduler():
-        if os.path.exists(sched_file):
-            return PNDMScheduler.from_config(sched_file)
-        return PNDMScheduler(prediction_type=config.get_path("model.prediction_model.prediction_type", "v_prediction"))
-
-    pipes = [StableDiffusionPruningPipeline(models.vae, models.text_encoder, u, scheduler(), tok) for u in (original, erased)]
-    return pipes[0], pipes[1]
+        erased = load_erasure_checkpoint(models.load_unet(args.original_ckpt), args.ckpt_name, esd=args.baseline == "esd")
+    return models.pipeline(original), models.pipeline(erased)
 
 
 @torch.no_grad()

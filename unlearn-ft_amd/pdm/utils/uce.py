@@ -17,10 +17,11 @@ Host side (no GPU needed): the text-list builders, the checkpoint name, the slic
 Not built: train_debias.py (a loop of generation and CLIP classification), the eval-scripts, `layers_to_edit` (the reference's
 __main__ never sets it), SD-1.4, and the fixed concept lists `allartist`, `i2g`, `10artists`, `imagenette`.
 """
-import os
 import random
 
 import torch
+
+from .load_models import golden_path
 
 LAMB = 0.5
 FIXED_LISTS = ("allartist", "i2g", "10artists", "imagenette")
@@ -30,8 +31,7 @@ ROW_PAD = 64                      # erase rows are zero-padded to a multiple of 
 
 # ---- flags, texts and names (train_erase.py:355-451, :479-481)
 def default_artists_file():
-    root = os.path.dirname(os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
-    return os.path.join(root, "tests", "golden", "uce", "artists1734.txt")
+    return golden_path("uce", "artists1734.txt")
 
 
 def read_artists(path=None):

@@ -20,8 +20,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.dirna
 import torch
 
 from pdm.utils import concept_prune as CP
-from pdm.utils import erasure_utils as E
-from pdm.utils.config import Cfg, load_config
+from pdm.utils.load_models import FrozenModels, cuda_device, inference_config
 
 
 def parse_args(argv=None):
@@ -37,13 +36,8 @@ def main(argv=None):
     if not os.path.exists(counts_file):
         raise FileNotFoundError(f"{counts_file}: run wanda.py with the same flags first")
     counts = torch.load(counts_file, map_location="cpu")
-    device = torch.device("cuda", args.gpu)
-    torch.cuda.set_device(device)
-    config = load_config(args.base_config_path) if args.base_config_path else Cfg()
-    config.update({"pretrained_model_name_or_path": args.model_id, "tiny": args.tiny})
-    if args.mixed_precision is not None:
-        config.update({"mixed_precision": args.mixed_precision})
-    unet = E._load_unet(E.load_frozen_models(config, device), config, args.ckpt_path)
+    config = inference_config(args.base_config_path, args.model_id, args.tiny, args.mixed_precision)
+    unet = FrozenModels(config, cuda_device(args.gpu)).load_unet(args.ckpt_path)
     print("Applying masks to the model")
     density = CP.apply_counts(unet, counts, args.select_ratio, args.timesteps)
     for l, (key, d) in enumerate(density.items()):

@@ -28,7 +28,7 @@ import torch
 
 from pdm.utils import concept_prune as CP
 from pdm.utils import erasure_utils as E
-from pdm.utils.config import Cfg, load_config
+from pdm.utils.load_models import FrozenModels, cuda_device, inference_config
 
 
 def parse_args(argv=None):
@@ -45,13 +45,9 @@ def main(argv=None):
         base_prompts, target_prompts = base_prompts[:3], target_prompts[:3]
     for d in (paths.images, paths.skilled_neurons, paths.checkpoints):
         os.makedirs(d, exist_ok=True)
-    device = torch.device("cuda", args.gpu)
-    torch.cuda.set_device(device)
-    config = load_config(args.base_config_path) if args.base_config_path else Cfg()
-    config.update({"pretrained_model_name_or_path": args.model_id, "tiny": args.tiny})
-    if args.mixed_precision is not None:
-        config.update({"mixed_precision": args.mixed_precision})
-    pipe = CP.load_pipeline(config, args.ckpt_path, device, args.scheduler)
+    device = cuda_device(args.gpu)
+    models = FrozenModels(inference_config(args.base_config_path, args.model_id, args.tiny, args.mixed_precision), device)
+    pipe = models.pipeline(models.load_unet(args.ckpt_path), args.scheduler)
     unet = pipe.unet
     layers = CP.ffn_layers(unet)
     print("Layer names: ", [key for key, *_ in layers], len(layers))

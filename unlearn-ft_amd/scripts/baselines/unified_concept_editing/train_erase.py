@@ -24,9 +24,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.dirna
 
 import torch
 
-from pdm.utils import erasure_utils as E
 from pdm.utils import uce as U
-from pdm.utils.config import Cfg, load_config
+from pdm.utils.load_models import FrozenModels, cuda_device, inference_config
 
 
 def parse_args(argv=None):
@@ -43,17 +42,10 @@ def main(argv=None):
     print(name)
     if args.ckpt_path is None:
         raise ValueError("--ckpt_path is required (the pruned checkpoint directory: arch_vector.pt + unet/)")
-    device = torch.device("cuda", int(args.device))
-    torch.cuda.set_device(device)
-    config = load_config(args.base_config_path) if args.base_config_path else Cfg()
-    config.update({"tiny": args.tiny, "mixed_precision": "no"})
-    if args.model_id is not None:
-        config.update({"pretrained_model_name_or_path": args.model_id})
-    from pdm.utils.data import load_tokenizer
-    models = E.load_frozen_models(config, device)
-    unet = E._load_unet(models, config, args.ckpt_path)
-    tokenizer = load_tokenizer(config.get_path("pretrained_model_name_or_path"))
-    U.edit_model(unet, models.text_encoder, tokenizer, old_texts, new_texts, retain_texts, lamb=U.LAMB,
+    config = inference_config(args.base_config_path, args.model_id, args.tiny, mixed_precision="no")
+    models = FrozenModels(config, cuda_device(args.device))
+    unet = models.load_unet(args.ckpt_path)
+    U.edit_model(unet, models.text_encoder, models.tokenizer, old_texts, new_texts, retain_texts, lamb=U.LAMB,
                  erase_scale=args.erase_scale, preserve_scale=preserve_scale, technique=args.technique)
     out = os.path.join(args.output_dir, "models", f"erased-{name}.pt")
     os.makedirs(os.path.dirname(out), exist_ok=True)

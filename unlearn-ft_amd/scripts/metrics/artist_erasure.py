@@ -38,10 +38,8 @@ import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 
-import torch
-
 from pdm.utils import erasure_utils as E
-from pdm.utils.config import Cfg, load_config
+from pdm.utils.load_models import cuda_device, inference_config
 
 
 def parse_args(argv=None):
@@ -85,18 +83,14 @@ def main(argv=None):
     print("Benchmarking result path: ", os.path.dirname(directory))
     os.makedirs(directory, exist_ok=True)
     prompts = E.read_prompts(args.prompts_csv or E.default_prompts_csv(args.target))
-    device = torch.device("cuda", args.gpu)
-    torch.cuda.set_device(device)
+    device = cuda_device(args.gpu)
 
     # Run the models if the folder is empty
     if len(os.listdir(directory)) == 0:
         print("Saving images after removal of concept")
         if args.original_ckpt is None:
             raise ValueError("generation needs --original_ckpt")
-        config = load_config(args.base_config_path) if args.base_config_path else Cfg()
-        config.update({"pretrained_model_name_or_path": args.model_id, "tiny": args.tiny})
-        if args.mixed_precision is not None:
-            config.update({"mixed_precision": args.mixed_precision})
+        config = inference_config(args.base_config_path, args.model_id, args.tiny, args.mixed_precision)
         original, erased = E.load_pipelines(config, args, device)
         E.generate(prompts, directory, original, erased, args.seed, E.image_resolution(args.model_id, args.image_resolution),
                    args.num_inference_steps)

@@ -10,8 +10,8 @@ caption row of the validation split, sampled by a fine-tuned student, for FID / 
   last batch stays short, where accelerate pads it by wrapping around to the first rows.
 * Models: `arch_vector.pt` and `unet/diffusion_pytorch_model.safetensors` of --finetuning_ckpt_dir (a trainer
   `checkpoint-N` directory as it is); block types from the config; VAE, CLIP text encoder and tokenizer from the snapshot
-  (`pretrained_model_name_or_path`) under the trainer's `tiny` / `random_init` rules; dtype as Trainer.init_weight_dtype
-  (`training.mixed_precision: null` -> fp32, as the reference).
+  (`pretrained_model_name_or_path`) under the trainer's `tiny` / `random_init` rules and dtype rule
+  (`training.mixed_precision: null` -> fp32, as the reference): pdm/utils/load_models.py FrozenModels.
 * Scheduler: PNDM from <snapshot>/scheduler/scheduler_config.json when present (values the class does not implement
   raise), else the SD-2.1 defaults with `model.prediction_model.prediction_type`.  Guidance 7.5; with `seed` set, a
   `torch.Generator(device).manual_seed(seed)` per batch, as the reference.
@@ -38,6 +38,8 @@ import torch.distributed as dist
 
 from pdm.utils.arg_utils import parse_args
 from pdm.utils.config import load_config
+from pdm.utils.erasure_utils import erasure_dir_name, load_erasure_checkpoint
+from pdm.utils.load_models import FrozenModels, cuda_device
 
 logger = logging.getLogger("pdm.generate_fid_images")
 GUIDANCE = 7.5
@@ -61,45 +63,8 @@ def image_file_name(image):
 def output_dir(config):
     name = config.get_path("data.dataset_name")
     if config.get("erasure_ckpt_path") is not None:
-        from pdm.utils.erasure_utils import erasure_dir_name
         return os.path.join(config.finetuning_ckpt_dir, erasure_dir_name(config.erasure_ckpt_path), f"{name}_fid_images")
     return os.path.join(config.finetuning_ckpt_dir, f"{name}_fid_images_{config.get_path('training.num_inference_steps', 50)}")
-
-
-def load_scheduler(config):
-    from pdm.pipelines.pruning_pipelines import PNDMScheduler
-    root = config.get_path("pretrained_model_name_or_path")
-    path = os.path.join(str(root), "scheduler", "scheduler_config.json")
-    if root and os.path.exists(path):
-        return PNDMScheduler.from_config(path)
-    return PNDMScheduler(prediction_type=config.get_path("model.prediction_model.prediction_type", "v_prediction"))
-
-
-def load_pipeline(config, device):
-    """StableDiffusionPruningPipeline over the checkpoint's student and the snapshot's VAE / text encoder / tokenizer."""
-    from pdm.models.unet.spec import UNetConfig
-    from pdm.models.unet.unet_2d_conditional import UNet2DConditionModelPruned
-    from pdm.pipelines.pruning_pipelines import StableDiffusionPruningPipeline
-    from pdm.training.trainer import Trainer
-    from pdm.utils.data import load_tokenizer
-    ck = config.finetuning_ckpt_dir
-    # the trainer's own rules for dtype, VAE and text encoder (tiny / random_init / local snapshot), without its set-up
-    models = Trainer.__new__(Trainer)
-    models.config, models.device = config, device
-    models.init_weight_dtype()
-    models.unet_config = UNetConfig.tiny() if config.get_path("tiny", False) else UNetConfig.sd21()
-    pm = config.get_path("model.prediction_model", {}) or {}
-    arch = torch.load(os.path.join(ck, "arch_vector.pt"), map_location="cpu")
-    unet = UNet2DConditionModelPruned.from_pretrained(
-        ck, subfolder="unet", arch_vector=arch, unet_config=models.unet_config, torch_dtype=models.weight_dtype, device=device,
-        down_block_types=pm.get("unet_down_blocks"), up_block_types=pm.get("unet_up_blocks"),
-        mid_block_type=pm.get("unet_mid_block"), gated_ff=pm.get("gated_ff", True), ff_gate_width=pm.get("ff_gate_width", 32),
-        attention_precision=pm.get("attention_precision"), train=False)
-    if config.get("erasure_ckpt_path") is not None:
-        from pdm.utils.erasure_utils import load_erasure_checkpoint
-        load_erasure_checkpoint(unet, config.erasure_ckpt_path)
-    tok = load_tokenizer(config.get_path("pretrained_model_name_or_path"))
-    return StableDiffusionPruningPipeline(models.vae, models.text_encoder, unet, load_scheduler(config), tok)
 
 
 def validation_rows(config):
@@ -129,14 +94,17 @@ def main():
     if world > 1 and not dist.is_initialized():
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         dist.init_process_group("gloo", rank=rank, world_size=world)
-    torch.cuda.set_device(local)
-    device = torch.device("cuda", local)
+    device = cuda_device(local)
     seed = config.get("seed")
     if seed is not None:
         torch.manual_seed(int(seed))
     captions, images = validation_rows(config)
     logger.info("Dataset of size %d loaded.", len(captions))
-    pipe = load_pipeline(config, device)
+    models = FrozenModels(config, device)
+    unet = models.load_unet(config.finetuning_ckpt_dir)
+    if config.get("erasure_ckpt_path") is not None:
+        load_erasure_checkpoint(unet, config.erasure_ckpt_path)
+    pipe = models.pipeline(unet)
     steps = int(config.get_path("training.num_inference_steps", 50))
     R = int(config.get("image_resolution") or 512)
     bs = int(config.get_path("data.dataloader.image_generation_batch_size", 1) or 1)
