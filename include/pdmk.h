@@ -367,6 +367,14 @@ int pdmk_mse_fwd(const void* a, int a_dtype, const void* b, int b_dtype, const f
 int pdmk_mse_bwd(const void* a, int a_dtype, const void* b, int b_dtype, const float* w, void* da, int B,
                  int64_t rows_per_b, int cols, int lda, int ldb, int ldda, float gscale, int accumulate,
                  pdmk_stream stream);
+/* ESD's head (baselines/erasing/esd_diffusers.py:105) in one pass: tgt = e_f - ng * (e_p - e_n) in fp32 from the stored
+ * values (never rounded to the compute dtype; one rounding per operation, nothing contracted), d = pred - tgt,
+ * dpred = gscale * d in `dtype` over `cols` and ZEROS in [cols, lddp) (dpred may be NULL), out[slot] += scale * sum d^2
+ * (out may be NULL) with the difference of the same stored values and the sum taken in double.  pred [rows, ldp]; e_p, e_n,
+ * e_f [rows, lde] each, all in `dtype`; e_f may alias e_n. */
+int pdmk_esd_head(const void* pred, const void* e_p, const void* e_n, const void* e_f, float ng, double* out, int slot,
+                  void* dpred, int64_t rows, int cols, int ldp, int lde, int lddp, double scale, float gscale, int dtype,
+                  pdmk_stream stream);
 /* Both at once in ONE pass over a and b, 16-byte accesses: out[slot] += ... as pdmk_mse_fwd (out may be NULL) and, when da
  * is not NULL, da (+)= gscale * w[b] * (a - b) as pdmk_mse_bwd.  cols % 8 == 0, row strides multiples of a 16-byte chunk,
  * 16-byte aligned bases (-1 otherwise: use the two scalar entry points).  The block-feature head reads 2 x 6.3 M
@@ -390,6 +398,19 @@ int pdmk_axpby(const void* x, void* y, float alpha, float beta, int64_t n, int d
 int pdmk_adamw(float* p, float* g, float* m, float* v, int64_t n, const float* lr, float beta1, float beta2,
                float eps, float weight_decay, const float* bias_corr /* [2]: 1-b1^t, 1-b2^t */, float grad_scale,
                int zero_grad, void* w_bf16 /* optional: refreshed bf16 copy of p, same offsets */, pdmk_stream stream);
+/* pdmk_adamw over a subset of the arena, in ONE launch whatever the row count (ESD trains only some modules).  `table`
+ * (device memory) has nseg rows {off, moff, n}: p / g / w_bf16 elements [off, off + n) are updated with the moments
+ * m / v [moff, moff + n), which are COMPACT (they hold the trainable elements only).  off, moff, n are multiples of 4 (a
+ * row that is not, or has n <= 0, is skipped on the device).  Nothing outside the rows is read or written; zero_grad clears g
+ * inside them only.  Scalars, lr / bias_corr and the per-element arithmetic are pdmk_adamw's, to the bit (one shared device
+ * function).  One workgroup works through one row: split long segments into rows of a few thousand elements.
+ * -1: nseg <= 0, a null or misaligned pointer. */
+typedef struct {
+    int64_t off, moff, n;
+} pdmk_adamw_seg;
+int pdmk_adamw_segments(float* p, float* g, float* m, float* v, const pdmk_adamw_seg* table, int nseg, const float* lr,
+                        float beta1, float beta2, float eps, float weight_decay, const float* bias_corr, float grad_scale,
+                        int zero_grad, void* w_bf16, pdmk_stream stream);
 /* Refresh of all dgrad weight copies in ONE launch: `table` = ntiles records of 12 int32
  * {src_off(lo,hi), dst_off(lo,hi), rows, cols, src_ld, dst_ld, r0, c0, 0, 0}; each record transposes one 64x64 tile:
  * dst[dst_off + c*dst_ld + r] = src[src_off + r*src_ld + c]. src/dst in `dtype`. */
@@ -530,6 +551,19 @@ typedef struct {
 int pdmk_plms_step(const void* pred, int ld, float g_u, float g_t, int cfg, float* sample, float* cur, float* ets,
                    const pdmk_plms_row* table, int nsteps, int32_t* state, int64_t* t_out, void* x_next, int cpad,
                    int B, int C, int HW, int dtype, pdmk_stream stream);
+
+/* The same launch for DDIM with eta 0 (DDIMScheduler.step: one pdmk_axpby, prev = c_m * model_output + c_x * sample).
+ * Row: the U-Net timestep and DDIMScheduler.coefficients(t), float64 on the host, cast to fp32 as pdmk_axpby takes them.
+ *   guided = form(g_u, uncond, g_t, text) (or pred without CFG);  prev = form(c_m, guided, c_x, sample).
+ * sample, state, t_out, x_next and "past the end does nothing" as pdmk_plms_step; there is no history. */
+typedef struct {
+    int64_t t;
+    float c_x, c_m;
+    int64_t pad_;
+} pdmk_ddim_row;
+int pdmk_ddim_step(const void* pred, int ld, float g_u, float g_t, int cfg, float* sample, const pdmk_ddim_row* table,
+                   int nsteps, int32_t* state, int64_t* t_out, void* x_next, int cpad, int B, int C, int HW, int dtype,
+                   pdmk_stream stream);
 
 /* Image epilogue of generate_fid_images.py:141-151 (`(image / 2 + 0.5).clamp(0, 1)` of the diffusers image processor, then
  * `.permute(0, 2, 3, 1).cpu().numpy()`, `img * 255`, `img.astype(np.uint8)`): fp32 NCHW [B, C, HW] in, uint8 NHWC out,

@@ -457,6 +457,41 @@ __global__ void mse_bwd_kernel(const void* __restrict__ a, int adt, const void* 
     }
 }
 
+// ESD's head (pdmk.h pdmk_esd_head): target e_f - ng (e_p - e_n) formed in fp32 from the stored predictions (one rounding per
+// operation, nothing contracted: the fp32 torch chain's own arithmetic), the gradient seed with zeroed padding columns, and the
+// squared error of the same stored values accumulated in double, one pass.  e_f may alias e_n.
+template <typename T>
+__global__ void esd_head_kernel(const T* __restrict__ pred, const T* e_p, const T* e_n, const T* e_f, float ng,
+                                double* __restrict__ out, int slot, T* __restrict__ dpred, long rows, int cols, int ldp,
+                                int lde, int lddp, double scale, float gscale) {
+    const int wcols = dpred ? lddp : cols;
+    const long total = rows * wcols;
+    double s = 0.0;
+    for (long i = blockIdx.x * (long)NT + threadIdx.x; i < total; i += (long)gridDim.x * NT) {
+        const long r = i / wcols;
+        const int c = (int)(i - r * wcols);
+        float gr = 0.f;
+        if (c < cols) {
+            const long j = r * lde + c;
+            const float ep = to_f32(e_p[j]), en = to_f32(e_n[j]), ef = to_f32(e_f[j]), pr = to_f32(pred[r * ldp + c]);
+            const float tgt = __fsub_rn(ef, __fmul_rn(ng, __fsub_rn(ep, en)));
+            gr = __fmul_rn(gscale, __fsub_rn(pr, tgt));
+            const double dd = (double)pr - ((double)ef - (double)ng * ((double)ep - (double)en));
+            s += dd * dd;
+        }
+        if (dpred) dpred[r * lddp + c] = from_f32<T>(gr);
+    }
+    s = wave_sum_d(s);
+    __shared__ double red[NT / 64];
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0 && out) {
+        double tot = 0.0;
+        for (int w = 0; w < NT / 64; ++w) tot += red[w];
+        atomicAdd(&out[slot], tot * scale);
+    }
+}
+
 // Loss value AND its gradient seed in one pass, 8 elements (one or two 16-byte loads) per thread and iteration: the block
 // feature head (trainer.py:2475-2481) reads 2 x 6.3 M activations per image; the scalar kernels above stay for the
 // 4-channel prediction heads (cols not a multiple of 8).
@@ -694,16 +729,24 @@ __global__ void up2_combine_kernel(const float* __restrict__ dwp, float* __restr
 }
 
 // ------------------------------------------------------------------------------------------------ AdamW / sumsq
+// One update, shared by adamw_kernel and adamw_segments_kernel (one inlined body: the compiler contracts both alike)
+__device__ __forceinline__ void adamw_elem(float& p, float g, float& m, float& v, float gscale, float lr, float wd, float b1,
+                                           float b2, float eps, float bc1, float bc2s) {
+    const float gr = g * gscale;
+    p *= (1.f - lr * wd);
+    m = b1 * m + (1.f - b1) * gr;
+    v = b2 * v + (1.f - b2) * gr * gr;
+    const float denom = sqrtf(v) / bc2s + eps;
+    p -= (lr / bc1) * (m / denom);
+}
+// float4 items first, first + stride, ... below nv of the five streams; U float4 per stream in flight per thread (U = 2: the
+// four read streams of the next element set are requested before the five write streams of this one go out)
 template <int U>
-__global__ void adamw_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
-                             long n, const float* __restrict__ lrp, float b1, float b2, float eps, float wd,
-                             const float* __restrict__ bc, float gscale, int zero_grad, bf16* __restrict__ wout) {
-    const float lr = lrp[0], bc1 = bc[0], bc2s = sqrtf(bc[1]);
-    const long nv = n / 4;
-    const long stride = (long)gridDim.x * NT;
-    // U float4 per stream in flight per thread (U = 2: the four read streams of the next element set are requested before the
-    // five write streams of this one go out)
-    for (long i0 = blockIdx.x * (long)NT + threadIdx.x; i0 < nv; i0 += stride * U) {
+__device__ __forceinline__ void adamw_span(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
+                                           float* __restrict__ v, bf16* __restrict__ wout, long nv, long first, long stride,
+                                           float lr, float bc1, float bc2s, float b1, float b2, float eps, float wd,
+                                           float gscale, int zero_grad) {
+    for (long i0 = first; i0 < nv; i0 += stride * U) {
         float4 P[U], G[U], Mv[U], Vv[U];
 #pragma unroll
         for (int u = 0; u < U; ++u) {
@@ -721,14 +764,7 @@ __global__ void adamw_kernel(float* __restrict__ p, float* __restrict__ g, float
             if (i >= nv) break;
             float* pp = &P[u].x; float* gg = &G[u].x; float* mm = &Mv[u].x; float* vv = &Vv[u].x;
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const float gr = gg[e] * gscale;
-                pp[e] *= (1.f - lr * wd);
-                mm[e] = b1 * mm[e] + (1.f - b1) * gr;
-                vv[e] = b2 * vv[e] + (1.f - b2) * gr * gr;
-                const float denom = sqrtf(vv[e]) / bc2s + eps;
-                pp[e] -= (lr / bc1) * (mm[e] / denom);
-            }
+            for (int e = 0; e < 4; ++e) adamw_elem(pp[e], gg[e], mm[e], vv[e], gscale, lr, wd, b1, b2, eps, bc1, bc2s);
             reinterpret_cast<float4*>(p)[i] = P[u];
             if (wout) {      // refreshed bf16 compute copy in the same pass (saves re-reading the master arena)
                 bf16x4 o;
@@ -741,6 +777,27 @@ __global__ void adamw_kernel(float* __restrict__ p, float* __restrict__ g, float
             if (zero_grad) reinterpret_cast<float4*>(g)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
         }
     }
+}
+template <int U>
+__global__ void adamw_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                             long n, const float* __restrict__ lrp, float b1, float b2, float eps, float wd,
+                             const float* __restrict__ bc, float gscale, int zero_grad, bf16* __restrict__ wout) {
+    const float lr = lrp[0], bc1 = bc[0], bc2s = sqrtf(bc[1]);
+    adamw_span<U>(p, g, m, v, wout, n / 4, blockIdx.x * (long)NT + threadIdx.x, (long)gridDim.x * NT, lr, bc1, bc2s, b1, b2,
+                  eps, wd, gscale, zero_grad);
+}
+// One workgroup per table row: p / g / wout at the row's arena offset, the compact moments at its own.  A row that is not a
+// positive multiple of 4 elements at offsets that are multiples of 4 is skipped (nothing outside a valid row is touched).
+template <int U>
+__global__ void adamw_segments_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
+                                      float* __restrict__ v, const pdmk_adamw_seg* __restrict__ table,
+                                      const float* __restrict__ lrp, float b1, float b2, float eps, float wd,
+                                      const float* __restrict__ bc, float gscale, int zero_grad, bf16* __restrict__ wout) {
+    const pdmk_adamw_seg r = table[blockIdx.x];
+    if (r.n <= 0 || r.off < 0 || r.moff < 0 || ((r.off | r.moff | r.n) & 3)) return;
+    const float lr = lrp[0], bc1 = bc[0], bc2s = sqrtf(bc[1]);
+    adamw_span<U>(p + r.off, g + r.off, m + r.moff, v + r.moff, wout ? wout + r.off : nullptr, r.n / 4, threadIdx.x, NT, lr,
+                  bc1, bc2s, b1, b2, eps, wd, gscale, zero_grad);
 }
 // Deferred sum of weight-gradient split-K slabs for up to PDMK_SLAB_GROUP_MAX weights in one launch:
 // dst[e] += sum_s ws[s * n + e], slabs added in a fixed order (bit-reproducible, no atomics); blockIdx.y = item.
@@ -952,6 +1009,25 @@ extern "C" int pdmk_mse_bwd(const void* a, int a_dtype, const void* b, int b_dty
     PDMK_CHECK_LAUNCH();
     return 0;
 }
+extern "C" int pdmk_esd_head(const void* pred, const void* e_p, const void* e_n, const void* e_f, float ng, double* out,
+                             int slot, void* dpred, int64_t rows, int cols, int ldp, int lde, int lddp, double scale,
+                             float gscale, int dtype, pdmk_stream s) {
+    if (!pred || !e_p || !e_n || !e_f || (!out && !dpred) || rows <= 0 || cols <= 0 || ldp < cols || lde < cols ||
+        (dpred && lddp < cols) || slot < 0)
+        return -1;
+    dim3 grid(grid_for(rows * (dpred ? lddp : cols), 256));
+    if (dtype == PDMK_BF16)
+        hipLaunchKernelGGL(esd_head_kernel<bf16>, grid, dim3(NT), 0, (hipStream_t)s, (const bf16*)pred, (const bf16*)e_p,
+                           (const bf16*)e_n, (const bf16*)e_f, ng, out, slot, (bf16*)dpred, (long)rows, cols, ldp, lde, lddp,
+                           scale, gscale);
+    else if (dtype == PDMK_F32)
+        hipLaunchKernelGGL(esd_head_kernel<float>, grid, dim3(NT), 0, (hipStream_t)s, (const float*)pred, (const float*)e_p,
+                           (const float*)e_n, (const float*)e_f, ng, out, slot, (float*)dpred, (long)rows, cols, ldp, lde, lddp,
+                           scale, gscale);
+    else return -2;
+    PDMK_CHECK_LAUNCH();
+    return 0;
+}
 extern "C" int pdmk_adamw(float* p, float* g, float* m, float* v, int64_t n, const float* lr, float beta1, float beta2,
                           float eps, float weight_decay, const float* bias_corr, float grad_scale, int zero_grad,
                           void* w_bf16, pdmk_stream s) {
@@ -960,6 +1036,17 @@ extern "C" int pdmk_adamw(float* p, float* g, float* m, float* v, int64_t n, con
     //  4096 or 16 384 blocks are slower)
     hipLaunchKernelGGL(adamw_kernel<2>, dim3(grid_for(n / 8, 8192)), dim3(NT), 0, (hipStream_t)s, p, g, m, v, (long)n, lr,
                        beta1, beta2, eps, weight_decay, bias_corr, grad_scale, zero_grad, (bf16*)w_bf16);
+    PDMK_CHECK_LAUNCH();
+    return 0;
+}
+extern "C" int pdmk_adamw_segments(float* p, float* g, float* m, float* v, const pdmk_adamw_seg* table, int nseg,
+                                   const float* lr, float beta1, float beta2, float eps, float weight_decay,
+                                   const float* bias_corr, float grad_scale, int zero_grad, void* w_bf16, pdmk_stream s) {
+    if (!p || !g || !m || !v || !table || !lr || !bias_corr || nseg <= 0) return -1;
+    if ((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) || ((uintptr_t)w_bf16 & 7) || ((uintptr_t)table & 7))
+        return -1;
+    hipLaunchKernelGGL(adamw_segments_kernel<2>, dim3(nseg), dim3(NT), 0, (hipStream_t)s, p, g, m, v, table, lr, beta1, beta2,
+                       eps, weight_decay, bias_corr, grad_scale, zero_grad, (bf16*)w_bf16);
     PDMK_CHECK_LAUNCH();
     return 0;
 }

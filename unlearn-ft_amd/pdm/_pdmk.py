@@ -53,6 +53,11 @@ class PlmsRow(C.Structure):
                 ("v_x", f32), ("v_v", f32), ("eps_scale", f32), ("x_scale", f32), ("vpred", i32), ("pad_", i32)]
 
 
+class DdimRow(C.Structure):
+    """pdmk_ddim_row (include/pdmk.h): one step of the fused guidance + DDIM update."""
+    _fields_ = [("t", i64), ("c_x", f32), ("c_m", f32), ("pad_", i64)]
+
+
 _SIGS = {
     "pdmk_version": ([], i32),
     "pdmk_gemm": ([C.POINTER(GemmArgs), vp], i32),
@@ -97,6 +102,8 @@ _SIGS = {
     "pdmk_mse_fwd_bwd": ([vp, i32, vp, i32, vp, vp, i32, vp, i32, i64, i32, i32, i32, i32, f64, f32, i32, vp], i32),
     "pdmk_axpby": ([vp, vp, f32, f32, i64, i32, vp], i32),
     "pdmk_adamw": ([vp, vp, vp, vp, i64, vp, f32, f32, f32, f32, vp, f32, i32, vp, vp], i32),
+    "pdmk_adamw_segments": ([vp, vp, vp, vp, vp, i32, vp, f32, f32, f32, f32, vp, f32, i32, vp, vp], i32),
+    "pdmk_esd_head": ([vp, vp, vp, vp, f32, vp, i32, vp, i64, i32, i32, i32, i32, f64, f32, i32, vp], i32),
     "pdmk_transpose_tiles": ([vp, vp, vp, i32, i32, vp], i32),
     "pdmk_sumsq": ([vp, i64, vp, i32, vp], i32),
     "pdmk_zero": ([vp, i64, vp], i32),
@@ -116,6 +123,7 @@ _SIGS = {
     "pdmk_clip_score_head": ([vp, i32, vp, i32, vp, vp, vp, i32, i32, vp], i32),
     "pdmk_cosine_pairs": ([vp, i32, vp, i32, vp, i32, vp, vp, vp, i32, i32, vp], i32),
     "pdmk_plms_step": ([vp, i32, f32, f32, i32, vp, vp, vp, vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, vp], i32),
+    "pdmk_ddim_step": ([vp, i32, f32, f32, i32, vp, vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, vp], i32),
     "pdmk_image_to_u8": ([vp, vp, i32, i32, i32, vp], i32),
     "pdmk_image_to_u8_ex": ([vp, vp, i32, i32, i32, i32, vp], i32),
     "pdmk_resize_bilinear_u8": ([vp, i64, vp, vp, i32, i32, vp, vp], i32),
@@ -921,6 +929,27 @@ def plms_step(pred, ld, g_u, g_t, cfg, sample, cur, ets, table, nsteps, state, t
                              nsteps, _p(state), _p(t_out), _p(x_next), cpad, B, Cc, HW, dt(pred), _st()), "pdmk_plms_step")
 
 
+def ddim_table(rows, device):
+    """A list of DdimRow -> the uint8 device tensor pdmk_ddim_step reads (one host-to-device copy)."""
+    arr = (DdimRow * len(rows))(*rows)
+    return torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(device)
+
+
+def ddim_step(pred, ld, g_u, g_t, cfg, sample, table, nsteps, state, t_out, x_next, cpad, B, Cc, HW):
+    """One fused guidance + DDIM step (include/pdmk.h pdmk_ddim_step).  pred / x_next in the engine dtype; sample fp32
+    [B*Cc*HW]; table from ddim_table() with nsteps rows; state int32 [2]; t_out int64."""
+    n = B * Cc * HW
+    rows = (2 * B if cfg else B) * HW
+    avail = pred.untyped_storage().nbytes() // pred.element_size() - pred.storage_offset()     # (pred may be a strided view)
+    if (pred.dtype != x_next.dtype or ld < Cc or cpad < Cc or avail < (rows - 1) * ld + Cc or x_next.numel() < rows * cpad
+            or sample.dtype != torch.float32 or not sample.is_contiguous() or sample.numel() != n
+            or table.dtype != torch.uint8 or table.numel() != nsteps * C.sizeof(DdimRow) or state.dtype != torch.int32
+            or state.numel() != 2 or t_out.dtype != torch.int64 or t_out.numel() < (2 * B if cfg else B)):
+        raise PdmkError("ddim_step: inconsistent buffers")
+    _chk(_lib.pdmk_ddim_step(_p(pred), ld, float(g_u), float(g_t), int(bool(cfg)), _p(sample), _p(table), nsteps, _p(state),
+                             _p(t_out), _p(x_next), cpad, B, Cc, HW, dt(pred), _st()), "pdmk_ddim_step")
+
+
 def _u8_shape(src, dst, name):
     B, Cc, H, W = src.shape
     if (src.dtype != torch.float32 or not src.is_contiguous() or dst.dtype != torch.uint8 or not dst.is_contiguous()
@@ -1057,6 +1086,62 @@ def axpby(x, y, alpha, beta):
 def adamw(p, g, m, v, n, lr, b1, b2, eps, wd, bias_corr, grad_scale, zero_grad, w_bf16=None):
     _chk(_lib.pdmk_adamw(_p(p), _p(g), _p(m), _p(v), n, _p(lr), b1, b2, eps, wd, _p(bias_corr), grad_scale,
                          int(zero_grad), _p(w_bf16), _st()), "pdmk_adamw")
+
+
+ADAMW_ROW = 8192       # elements one workgroup of pdmk_adamw_segments works through (a segment is cut into rows of this size)
+
+
+class AdamwTable:
+    """Segments [(arena offset, length)] as the device table of pdmk_adamw_segments.  The compact moment offsets follow the
+    segments in the given order; long segments are cut into rows of ADAMW_ROW elements (one workgroup each).  `extent` (one
+    past the last arena element a row touches) and `compact` (the moments' length) are what adamw_segments checks the
+    buffers against."""
+
+    def __init__(self, segments, device, row=ADAMW_ROW):
+        import numpy as np
+        segments = [(int(o), int(n)) for o, n in segments]
+        if not segments or row <= 0 or row % 4:
+            raise PdmkError("adamw_segments: no segments")
+        end = -1
+        for o, n in sorted(segments):
+            if o < 0 or n <= 0 or (o | n) & 3 or o < end:
+                raise PdmkError(f"adamw_segments: segment ({o}, {n}) is not a positive multiple of 4 elements at a multiple of "
+                                f"4, or overlaps its neighbour")
+            end = o + n
+        recs, moff = [], 0
+        for o, n in segments:
+            starts = np.arange(0, n, row, dtype=np.int64)
+            recs.append(np.stack([o + starts, moff + starts, np.minimum(row, n - starts)], 1))
+            moff += n
+        tab = np.ascontiguousarray(np.concatenate(recs, 0))
+        self.segments, self.nrows, self.extent, self.compact = segments, int(tab.shape[0]), end, moff
+        self.dev = torch.from_numpy(tab).to(device)
+
+
+def adamw_segments(p, g, m, v, table, lr, b1, b2, eps, wd, bias_corr, grad_scale, zero_grad, w_bf16=None):
+    """pdmk_adamw on the arena elements an AdamwTable names; m / v are compact (table.compact elements)."""
+    if (not isinstance(table, AdamwTable) or any(t.dtype != torch.float32 or not t.is_contiguous() for t in (p, g, m, v)) or p.numel() < table.extent
+            or g.numel() < table.extent or m.numel() < table.compact or v.numel() < table.compact
+            or (w_bf16 is not None and (w_bf16.dtype != torch.bfloat16 or w_bf16.numel() < table.extent))
+            or table.dev.device != p.device):
+        raise PdmkError("adamw_segments: inconsistent buffers")
+    _chk(_lib.pdmk_adamw_segments(_p(p), _p(g), _p(m), _p(v), _p(table.dev), table.nrows, _p(lr), b1, b2, eps, wd,
+                                  _p(bias_corr), grad_scale, int(zero_grad), _p(w_bf16), _st()), "pdmk_adamw_segments")
+
+
+def esd_head(pred, e_p, e_n, e_f, ng, out, slot, dpred, rows, cols, ldp, lde, lddp, scale, gscale):
+    """ESD's loss and gradient seed in one pass (include/pdmk.h pdmk_esd_head): out[slot] += scale * sum (pred - tgt)^2 with
+    tgt = e_f - ng (e_p - e_n) in fp32; dpred = gscale * (pred - tgt) over `cols`, zeros in [cols, lddp)."""
+    def avail(t):
+        return t.untyped_storage().nbytes() // t.element_size() - t.storage_offset()
+    ts = (pred, e_p, e_n, e_f) + (() if dpred is None else (dpred,))
+    if (any(t.dtype != pred.dtype for t in ts) or rows <= 0 or cols <= 0 or ldp < cols or lde < cols
+            or avail(pred) < (rows - 1) * ldp + cols or any(avail(t) < (rows - 1) * lde + cols for t in (e_p, e_n, e_f))
+            or (dpred is not None and (lddp < cols or avail(dpred) < rows * lddp))
+            or (out is not None and (out.dtype != torch.float64 or not 0 <= slot < out.numel()))):
+        raise PdmkError("esd_head: inconsistent buffers")
+    _chk(_lib.pdmk_esd_head(_p(pred), _p(e_p), _p(e_n), _p(e_f), float(ng), _p(out), slot, _p(dpred), rows, cols, ldp, lde,
+                            lddp, float(scale), float(gscale), dt(pred), _st()), "pdmk_esd_head")
 
 
 def transpose_tiles(src, dst, table, ntiles):

@@ -12,8 +12,8 @@ The denoising loop runs as replays of a captured graph (`_CapturedLoop`) when it
 followed by pdmk_plms_step, which does the guidance, the PLMS update and the next U-Net input in one launch, advances a
 device-side step counter and refreshes the U-Net's timestep buffer from a step table - so one capture serves every step.
 It is bit-identical to the eager loop (the kernel repeats pdmk_axpby's fp32 arithmetic operation by operation; DESIGN.md
-9.1).  `callback=`, block hooks, an `ffn_observer` on the U-Net's engine, another scheduler class (DDIMScheduler) or
-PDMK_SAMPLER_GRAPH=0 select the eager loop.
+9.1).  `callback=`, block hooks, an `ffn_observer` on the U-Net's engine or PDMK_SAMPLER_GRAPH=0 select the eager loop; so
+does a DDIMScheduler unless the caller passes graph=True (pdmk_ddim_step is then the step kernel).
 """
 import ctypes
 import gc
@@ -200,15 +200,29 @@ class DDIMScheduler(_Scheduler):
         k.axpby(model_output, prev, c_m, c_x)
         return SimpleNamespace(prev_sample=prev) if return_dict else (prev,)
 
+    def ddim_rows(self):
+        """The schedule of set_timesteps() as pdmk_ddim_row entries: step()'s coefficients at each timestep."""
+        rows = []
+        for t in self.timesteps.tolist():
+            c_x, c_m = self.coefficients(int(t))
+            rows.append(k.DdimRow(t=int(t), c_x=c_x, c_m=c_m))
+        return rows
+
 
 class _CapturedLoop:
     """The denoising loop of one (batch, H, W, dtype, CFG, steps, text shape, guidance) as replays of ONE single-stream
     captured graph (GraphedBilevel's docstring: graphs with parallel branches are not used): the U-Net forward over static
-    buffers, then pdmk_plms_step, which writes the next U-Net input and timesteps itself and advances the step counter.
-    The same graph is replayed once per U-Net call (N + 1 calls for N PLMS steps)."""
+    buffers, then pdmk_plms_step (kind "plms") or pdmk_ddim_step (kind "ddim"), which writes the next U-Net input and
+    timesteps itself and advances the step counter.  The same graph is replayed once per U-Net call (N + 1 calls for N PLMS
+    steps, N for N DDIM steps), or fewer when the caller stops early.  The graph reads the U-Net's weight arenas in place: it
+    stays valid while an optimiser rewrites them."""
 
-    def __init__(self, unet, B, h, w, cfg_on, guidance_scale, nsteps, T, ctx):
+    def __init__(self, unet, B, h, w, cfg_on, guidance_scale, nsteps, T, ctx, kind="plms"):
         dev, dt = unet.device, unet.dtype
+        if kind not in ("plms", "ddim"):
+            raise ValueError(f"_CapturedLoop: step kind {kind!r}")
+        self.kind = kind
+        self.Row = k.PlmsRow if kind == "plms" else k.DdimRow
         self.unet, self.B, self.C, self.h, self.w, self.cfg_on, self.nsteps = unet, B, unet.cfg.in_channels, h, w, cfg_on, nsteps
         self.g = (float(1.0 - guidance_scale), float(guidance_scale))       # axpby(out[:B], out[B:], 1 - g, g)
         self.R, self.cp = (2 * B if cfg_on else B), padc(self.C)
@@ -217,17 +231,22 @@ class _CapturedLoop:
         self.t = torch.zeros(self.R, device=dev, dtype=torch.int64)
         self.ehs = torch.zeros((self.R * T, ctx), device=dev, dtype=dt)
         self.sample = torch.zeros(n, device=dev)
-        self.cur = torch.zeros(n, device=dev)
-        self.ets = torch.zeros(4, n, device=dev)
+        if kind == "plms":
+            self.cur = torch.zeros(n, device=dev)
+            self.ets = torch.zeros(4, n, device=dev)
         self.state = torch.zeros(2, device=dev, dtype=torch.int32)
-        self.table = torch.zeros(nsteps * ctypes.sizeof(k.PlmsRow), device=dev, dtype=torch.uint8)
+        self.table = torch.zeros(nsteps * ctypes.sizeof(self.Row), device=dev, dtype=torch.uint8)
         self.graph, self.keep = None, []
         self._capture()
 
     def _body(self):
         pred, _ = self.unet.forward_nhwc(self.x, self.t, self.ehs, self.R, self.h, self.w, train=False)
-        k.plms_step(pred.t, pred.t.stride(0), *self.g, self.cfg_on, self.sample, self.cur, self.ets, self.table, self.nsteps,
-                    self.state, self.t, self.x, self.cp, self.B, self.C, self.h * self.w)
+        if self.kind == "plms":
+            k.plms_step(pred.t, pred.t.stride(0), *self.g, self.cfg_on, self.sample, self.cur, self.ets, self.table,
+                        self.nsteps, self.state, self.t, self.x, self.cp, self.B, self.C, self.h * self.w)
+        else:
+            k.ddim_step(pred.t, pred.t.stride(0), *self.g, self.cfg_on, self.sample, self.table, self.nsteps, self.state,
+                        self.t, self.x, self.cp, self.B, self.C, self.h * self.w)
         return pred
 
     def _capture(self):
@@ -266,19 +285,23 @@ class _CapturedLoop:
         eng = self.unet.engine          # what the graph reads or writes beyond its own pool stays allocated
         self.keep = [pred, eng.ws, eng._cs_arena]
 
-    def run(self, latents, ehs, rows):
+    def run(self, latents, ehs, rows, n_calls=None):
         """latents: fp32 [B, C, h, w] (contiguous, on the device); ehs: [R, T, ctx] text embeddings (unconditional half
-        first); rows: the scheduler's plms_rows().  Returns the final latents (a new tensor)."""
+        first); rows: the scheduler's plms_rows() / ddim_rows(); n_calls: U-Net calls to replay (None: all of them).  Returns
+        the latents after them (a new tensor)."""
         B, C, HW = self.B, self.C, self.h * self.w
+        n_calls = self.nsteps if n_calls is None else int(n_calls)
+        if len(rows) != self.nsteps or not 0 <= n_calls <= self.nsteps:
+            raise ValueError(f"_CapturedLoop.run: {len(rows)} rows, {n_calls} calls for a loop of {self.nsteps}")
         self.ehs.copy_(ehs.reshape(self.ehs.shape))                       # the batch's one cast of the text embeddings
-        self.table.copy_(torch.frombuffer(bytearray(bytes((k.PlmsRow * len(rows))(*rows))), dtype=torch.uint8))
+        self.table.copy_(torch.frombuffer(bytearray(bytes((self.Row * len(rows))(*rows))), dtype=torch.uint8))
         self.sample.copy_(latents.reshape(-1))
         k.nchw_to_nhwc(latents, self.x, B, C, HW, self.cp)
         if self.cfg_on:
             k.nchw_to_nhwc(latents, self.x[B * HW:], B, C, HW, self.cp)
         self.t.fill_(rows[0].t)
         self.state.zero_()
-        for _ in range(self.nsteps):
+        for _ in range(n_calls):
             self.graph.replay()
         return self.sample.view(B, C, self.h, self.w).clone()
 
@@ -319,7 +342,10 @@ class StableDiffusionPruningPipeline:
         return prompt_embeds, negative_prompt_embeds
 
     def _use_graph(self, graph, callback):
-        if graph is False or callback is not None or type(self.scheduler) is not PNDMScheduler:
+        kind = type(self.scheduler)
+        if graph is False or callback is not None or kind not in (PNDMScheduler, DDIMScheduler):
+            return False
+        if kind is DDIMScheduler and graph is not True:      # DDIM is captured only on request
             return False
         u = self.unet
         blocks = list(getattr(u, "down_blocks", [])) + [getattr(u, "mid_block", None)] + list(getattr(u, "up_blocks", []))
@@ -330,12 +356,13 @@ class StableDiffusionPruningPipeline:
         return graph is True or os.environ.get("PDMK_SAMPLER_GRAPH", "1") != "0"
 
     def _loop(self, B, h, w, cfg_on, guidance_scale, nsteps, T, ctx):
-        key = (B, h, w, self.unet.dtype, cfg_on, nsteps, T, ctx, float(guidance_scale))
+        key = (B, h, w, self.unet.dtype, cfg_on, nsteps, T, ctx, float(guidance_scale), type(self.scheduler))
         loop = self._loops.pop(key, None)
         if loop is None:
             while len(self._loops) >= self.GRAPH_SHAPES:
                 self._loops.pop(next(iter(self._loops))).close()
-            loop = _CapturedLoop(self.unet, B, h, w, cfg_on, guidance_scale, nsteps, T, ctx)
+            loop = _CapturedLoop(self.unet, B, h, w, cfg_on, guidance_scale, nsteps, T, ctx,
+                                 kind="ddim" if type(self.scheduler) is DDIMScheduler else "plms")
             self.captures += 1
         self._loops[key] = loop                                       # most recently used last
         return loop
@@ -344,12 +371,14 @@ class StableDiffusionPruningPipeline:
     def generate_samples(self, prompt_ids=None, height=None, width=None, num_inference_steps=50, guidance_scale=7.5,
                          negative_prompt_ids=None, generator=None, latents=None, prompt_embeds=None,
                          negative_prompt_embeds=None, output_type="np", return_dict=True, callback=None, callback_steps=1,
-                         prompt=None, negative_prompt=None, graph=None):
+                         prompt=None, negative_prompt=None, graph=None, end_iteration=None):
         """prompt / negative_prompt: strings or lists of strings (needs the tokenizer; with guidance and no negative prompt
         the empty prompt).  output_type "latent", "pt", "np" (float32 NHWC in [0, 1]), "u8" (uint8 NHWC numpy, the FID
         script's `(img * 255).astype(np.uint8)`, formed on the device) or "u8_round" (the same with diffusers' numpy_to_pil
         rounding, `(img * 255).round().astype("uint8")`: the pixels of `pipeline(prompt).images`).  graph: None = the captured loop when possible
-        (PDMK_SAMPLER_GRAPH=0 turns it off), False = the eager loop, True = captured whenever possible."""
+        (PDMK_SAMPLER_GRAPH=0 turns it off), False = the eager loop, True = captured whenever possible (a DDIMScheduler's loop
+        is captured only with True).  end_iteration: stop after that many scheduler steps and return the latents there (ESD's
+        partial sampling)."""
         cfg_on = guidance_scale > 1.0
         if isinstance(prompt_ids, (str, list, tuple)):            # the reference's positional `prompt`
             prompt, prompt_ids = prompt_ids, None
@@ -381,11 +410,14 @@ class StableDiffusionPruningPipeline:
         if latents is None:
             latents = torch.randn(shape, device=dev, dtype=torch.float32, generator=generator)
         latents = (latents.to(dev, torch.float32) * sch.init_noise_sigma).contiguous()
+        if end_iteration is not None and not 0 <= int(end_iteration) <= len(sch.timesteps):
+            raise ValueError(f"end_iteration={end_iteration} outside 0 ... {len(sch.timesteps)}")
         if self._use_graph(graph, callback):
             loop = self._loop(B, shape[2], shape[3], cfg_on, guidance_scale, len(sch.timesteps), ehs.shape[1], ehs.shape[2])
-            latents = loop.run(latents, ehs, sch.plms_rows())
+            rows = sch.ddim_rows() if loop.kind == "ddim" else sch.plms_rows()
+            latents = loop.run(latents, ehs, rows, n_calls=end_iteration)
         else:
-            latents = self._eager_loop(latents, ehs, B, shape, cfg_on, guidance_scale, callback, callback_steps)
+            latents = self._eager_loop(latents, ehs, B, shape, cfg_on, guidance_scale, callback, callback_steps, end_iteration)
         if output_type == "latent":
             image = latents
         else:
@@ -404,13 +436,13 @@ class StableDiffusionPruningPipeline:
                     image = image.permute(0, 2, 3, 1).cpu().numpy()
         return SimpleNamespace(images=image, nsfw_content_detected=None) if return_dict else (image, None)
 
-    def _eager_loop(self, latents, ehs, B, shape, cfg_on, guidance_scale, callback, callback_steps):
+    def _eager_loop(self, latents, ehs, B, shape, cfg_on, guidance_scale, callback, callback_steps, end_iteration=None):
         dev, sch = self.device, self.scheduler
         was_training = self.unet.training
         self.unet.eval()
         try:
             x2 = torch.empty((2 * B if cfg_on else B,) + shape[1:], device=dev, dtype=torch.float32)
-            for i, t in enumerate(sch.timesteps.tolist()):
+            for i, t in enumerate(sch.timesteps.tolist()[:end_iteration]):
                 x2[:B].copy_(latents)
                 if cfg_on:
                     x2[B:].copy_(latents)

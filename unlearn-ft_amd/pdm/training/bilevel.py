@@ -24,14 +24,22 @@ BLOCK_KEYS = ("d0", "d1", "d2", "d3", "m", "u0", "u1", "u2", "u3")
 
 
 class FusedAdamW:
-    """torch.optim.AdamW over the flat fp32 arena, one kernel launch (pdmk_adamw)."""
+    """torch.optim.AdamW over the flat fp32 arena, one kernel launch (pdmk_adamw).  segments = [(offset, length)]: only
+    those arena elements are parameters (pdmk_adamw_segments, still one launch); the moments are then compact, in segment
+    order, and the torch-layout state dict and launch_range are not available."""
 
-    def __init__(self, store, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, warmup_steps=0, sched_mult=1):
+    def __init__(self, store, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, warmup_steps=0, sched_mult=1,
+                 segments=None):
         dev = store.master.device
         self.store = store
         self.base_lr, self.betas, self.eps, self.wd = lr, betas, eps, weight_decay
-        self.m = torch.zeros_like(store.master)
-        self.v = torch.zeros_like(store.master)
+        self.table = None if segments is None else k.AdamwTable(segments, dev)
+        if self.table is None:
+            self.m = torch.zeros_like(store.master)
+            self.v = torch.zeros_like(store.master)
+        else:
+            self.m = torch.zeros(self.table.compact, device=dev)
+            self.v = torch.zeros(self.table.compact, device=dev)
         # [lr, 1 - b1^t, 1 - b2^t] live in ONE device vector refreshed per step by an asynchronous copy out of a ring of
         # pinned host rows (a pageable H2D copy would make the host wait for the stream to drain: no run-ahead, the GPU
         # idles between iterations); lr_dev / bc_dev are views of it
@@ -73,8 +81,12 @@ class FusedAdamW:
         s = self.store
         fused = s.dtype == torch.bfloat16
         with phase("adamw"):
-            k.adamw(s.master, s.grad, self.m, self.v, s.total, self.lr_dev, self.betas[0], self.betas[1], self.eps,
-                    self.wd, self.bc_dev, grad_scale, zero_grad, w_bf16=s.w if fused else None)
+            if self.table is None:
+                k.adamw(s.master, s.grad, self.m, self.v, s.total, self.lr_dev, self.betas[0], self.betas[1], self.eps,
+                        self.wd, self.bc_dev, grad_scale, zero_grad, w_bf16=s.w if fused else None)
+            else:
+                k.adamw_segments(s.master, s.grad, self.m, self.v, self.table, self.lr_dev, self.betas[0], self.betas[1],
+                                 self.eps, self.wd, self.bc_dev, grad_scale, zero_grad, w_bf16=s.w if fused else None)
             s.refresh(w_is_fresh=fused, wt=not s.defer_wt)
 
     def launch_range(self, lo, hi, grad_scale=1.0, zero_grad=True):
@@ -82,6 +94,8 @@ class FusedAdamW:
         gradients are final stream under the rest of the backward pass (HBM-bound kernel beside MFMA-bound ones)."""
         if hi <= lo:
             return
+        if self.table is not None:
+            raise NotImplementedError("launch_range on a segment optimiser")
         s = self.store
         fused = s.dtype == torch.bfloat16
         k.adamw(s.master[lo:hi], s.grad[lo:hi], self.m[lo:hi], self.v[lo:hi], hi - lo, self.lr_dev, self.betas[0],
@@ -98,6 +112,8 @@ class FusedAdamW:
         """`torch.optim.AdamW.state_dict()` layout: per-parameter {step, exp_avg, exp_avg_sq} in the reference's shapes
         (diffusers names, pruned), keyed by the parameter's index in the reference module's `.parameters()` order."""
         from ..models.unet.params import reference_param_order
+        if self.table is not None:
+            raise NotImplementedError("state_dict of a segment optimiser")
         s = self.store
         order = reference_param_order(list(s.state_dict_names()))
         state = {}

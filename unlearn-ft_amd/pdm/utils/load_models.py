@@ -121,13 +121,14 @@ class FrozenModels:
             self._tokenizer = load_tokenizer(cfg_get(self.config, "pretrained_model_name_or_path"))
         return self._tokenizer
 
-    def load_unet(self, ckpt_dir):
-        """The pruned student of a trainer checkpoint directory: arch_vector.pt + unet/diffusion_pytorch_model.safetensors."""
+    def load_unet(self, ckpt_dir, train=False):
+        """The pruned student of a trainer checkpoint directory: arch_vector.pt + unet/diffusion_pytorch_model.safetensors.
+        train=True: with gradient arena and dgrad weight copies (a baseline that fine-tunes it, ESD)."""
         from ..models.unet.unet_2d_conditional import UNet2DConditionModelPruned
         arch = torch.load(os.path.join(ckpt_dir, "arch_vector.pt"), map_location="cpu")
         return UNet2DConditionModelPruned.from_pretrained(
             ckpt_dir, subfolder="unet", arch_vector=arch, unet_config=self.unet_config, torch_dtype=self.weight_dtype,
-            device=self.device, train=False, **unet_kwargs(self.config))
+            device=self.device, train=bool(train), **unet_kwargs(self.config))
 
     def pipeline(self, unet, kind="pndm", scheduler=None, tokenizer=True):
         """StableDiffusionPruningPipeline over `unet` and the snapshot's VAE / text encoder, with `scheduler` or
