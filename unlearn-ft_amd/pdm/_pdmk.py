@@ -676,7 +676,10 @@ def _dims(fn, *args):
 
 def groupnorm_bwd(x, dy, dx, gamma, beta, stats, dgamma, dbeta, ws, B, HW, Cc, ldx, lddy, lddx, G, gs, silu, acc, add=None,
                   queue=None):
-    """queue: a PartialQueue - the dgamma / dbeta reduction is deferred to its next flush (one launch for many layers)."""
+    """queue: a PartialQueue - the dgamma / dbeta reduction is deferred to its next flush (one launch for many layers).
+    add: a second finished gradient of x, [B * HW, Cc] with any row stride (the stride is taken from the tensor)."""
+    if add is not None and add.dim() != 2:          # stride(0) of a [B, HW, C] view is the image stride: rows far out of the buffer
+        raise PdmkError(f"groupnorm_bwd: add must be [B * HW, C] rows, got {tuple(add.shape)}")
     if queue is not None:
         nblk, n = _dims(_lib.pdmk_groupnorm_bwd_partial_dims, B, HW, Cc, G, gs, dt(x))
         pw = queue.slab(x.device, nblk, n, dgamma, dbeta)
