@@ -565,6 +565,41 @@ int pdmk_ddim_step(const void* pred, int ld, float g_u, float g_t, int cfg, floa
                    int nsteps, int32_t* state, int64_t* t_out, void* x_next, int cpad, int B, int C, int HW, int dtype,
                    pdmk_stream stream);
 
+/* Safe Latent Diffusion (Schramowski et al. 2023; diffusers' StableDiffusionPipelineSafe loop): a third "safety concept"
+ * branch in classifier-free guidance.  Per element, with the predictions u (uncond), t (text), s (safety) converted to fp32,
+ * the fp32 momentum m (zero before the first U-Net call) and g = guidance_scale:
+ *     d     = t - s
+ *     scale = min(|d| * sld_guidance_scale, 1);   scale = 0 where d >= threshold
+ *     gs    = (s - u) * scale;                    gs = gs + momentum_scale * m
+ *     m     = mom_beta * m + one_minus_beta * gs                       (always, also during warm-up)
+ *     ng    = t - u;                              ng = ng - gs  if apply
+ *     pred  = u + g * ng
+ * Every operation is a separate fp32 operation rounded once (no fma anywhere): what a torch fp32 elementwise chain computes,
+ * bit for bit.  The scalars are fp32 values rounded from doubles on the host; one_minus_beta is `1 - mom_beta` formed in
+ * double and then rounded (it is not 1.f - mom_beta). */
+typedef struct {
+    float sld_guidance_scale, threshold, momentum_scale, mom_beta, one_minus_beta;
+    int32_t warmup_steps;     /* the fused steps apply the safety term from U-Net call `warmup_steps` on (0-based) */
+} pdmk_sld_params;
+
+/* The chain alone, as the eager loop uses it: pred fp32 NCHW [3B, C, HW] (thirds: uncond, text, safety) -> out fp32
+ * [B, C, HW]; mom fp32 [B, C, HW] updated in place.  apply: the host's `call index >= warmup_steps` (params->warmup_steps is
+ * not read).  16-byte accesses when B * C * HW % 4 == 0 and the three pointers are 16-byte aligned. */
+int pdmk_sld_guidance(const float* pred, float* out, float* mom, int B, int C, int HW, float guidance_scale,
+                      const pdmk_sld_params* params, int apply, pdmk_stream stream);
+
+/* pdmk_plms_step / pdmk_ddim_step with the SLD chain in place of the two-branch guidance.  pred: NHWC rows [3B * HW, ld] in
+ * dtype, thirds in the order uncond, text, safety; mom as above.  apply = state[0] >= params->warmup_steps, read from the
+ * counter the launch uses anyway, so one captured graph serves every step.  x_next ([3B * HW, cpad]) receives the new sample
+ * for all three thirds (padding channels 0), t_out (int64 [3B]) table[step + 1].t.  sample, cur, ets, table, state and "past
+ * the end does nothing" as in the two-branch launches; params is read on the host at launch. */
+int pdmk_sld_plms_step(const void* pred, int ld, float guidance_scale, const pdmk_sld_params* params, float* mom, float* sample,
+                       float* cur, float* ets, const pdmk_plms_row* table, int nsteps, int32_t* state, int64_t* t_out,
+                       void* x_next, int cpad, int B, int C, int HW, int dtype, pdmk_stream stream);
+int pdmk_sld_ddim_step(const void* pred, int ld, float guidance_scale, const pdmk_sld_params* params, float* mom, float* sample,
+                       const pdmk_ddim_row* table, int nsteps, int32_t* state, int64_t* t_out, void* x_next, int cpad, int B,
+                       int C, int HW, int dtype, pdmk_stream stream);
+
 /* Image epilogue of generate_fid_images.py:141-151 (`(image / 2 + 0.5).clamp(0, 1)` of the diffusers image processor, then
  * `.permute(0, 2, 3, 1).cpu().numpy()`, `img * 255`, `img.astype(np.uint8)`): fp32 NCHW [B, C, HW] in, uint8 NHWC out,
  * truncated (not rounded); NaN gives 0. */

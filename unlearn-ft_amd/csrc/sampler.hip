@@ -10,6 +10,9 @@
 // latent-sized call takes: B * 4 * H * W is a multiple of 4).  form() below spells that out as fma(a, x, b * y), and this file
 // is compiled without contraction so that nothing else is fused.  fp32 -> bf16 of the next U-Net input is from_f32<bf16>, as
 // in nchw2nhwc_kernel.
+// pdmk_sld_plms_step / pdmk_sld_ddim_step are the same two launches with Safe Latent Diffusion's three-branch guidance
+// (sld_chain below: plain fp32 operations, no fma) in place of the axpby; pdmk_sld_guidance is that chain alone, for the
+// eager loop.  All four step entry points are instances of one kernel (step_kernel<T, Guide, Sched>).
 #include "common.h"
 
 #pragma clang fp contract(off)
@@ -21,55 +24,119 @@ inline int grid_for(long nwork, int cap = 1024) { return (int)max(1L, min((long)
 
 __device__ __forceinline__ float form(float a, float x, float b, float y) { return __builtin_fmaf(a, x, b * y); }
 
-template <typename T>
-__global__ void plms_step_kernel(const T* __restrict__ pred, int ld, float g_u, float g_t, int cfg,
-                                 float* __restrict__ sample, float* __restrict__ cur, float* __restrict__ ets,
-                                 const pdmk_plms_row* __restrict__ table, int nsteps, int32_t* state,
-                                 int64_t* __restrict__ t_out, T* __restrict__ x_next, int cpad, int B, int C, int HW) {
+// ---- guidance: what turns the U-Net's prediction rows into the scheduler's model output for NCHW element i (pixel p, channel c)
+// Two branches (or none): pdmk_axpby(out[:B], out[B:], 1 - g, g).
+struct CfgGuide {
+    float g_u, g_t;
+    int cfg;
+    __device__ int copies() const { return cfg ? 2 : 1; }
+    template <typename T>
+    __device__ float operator()(const T* __restrict__ pred, int ld, long p, long npix, int c, long, int) const {
+        float g = to_f32(pred[p * ld + c]);                           // unconditional half (or the only one)
+        if (cfg) g = form(g_u, g, g_t, to_f32(pred[(p + npix) * ld + c]));
+        return g;
+    }
+};
+
+// Safe Latent Diffusion (include/pdmk.h pdmk_sld_params): separate fp32 operations, each rounded once - what a torch fp32
+// elementwise chain computes.  Nothing here is an fma (this file is compiled without contraction).  m is updated in place.
+__device__ __forceinline__ float sld_chain(float u, float t, float s, float& m, float g, const pdmk_sld_params& q, bool apply) {
+    const float d = t - s;
+    float scale = fabsf(d) * q.sld_guidance_scale;
+    scale = scale > 1.f ? 1.f : scale;                                // torch.clamp(max=1): NaN stays NaN
+    if (d >= q.threshold) scale = 0.f;
+    float gs = (s - u) * scale;
+    const float mm = q.momentum_scale * m;
+    gs = gs + mm;
+    const float a = q.mom_beta * m, b = q.one_minus_beta * gs;
+    m = a + b;
+    float ng = t - u;
+    if (apply) ng = ng - gs;
+    const float gn = g * ng;
+    return u + gn;
+}
+
+// Three branches, thirds in the order uncond, text, safety.  The warm-up is decided from the step counter.
+struct SldGuide {
+    float g;
+    pdmk_sld_params q;
+    float* mom;
+    __device__ int copies() const { return 3; }
+    template <typename T>
+    __device__ float operator()(const T* __restrict__ pred, int ld, long p, long npix, int c, long i, int step) const {
+        return sld_chain(to_f32(pred[p * ld + c]), to_f32(pred[(p + npix) * ld + c]), to_f32(pred[(p + 2 * npix) * ld + c]),
+                         mom[i], g, q, step >= q.warmup_steps);
+    }
+};
+
+// ---- schedulers: model output g of element i -> the previous sample, state updated in place
+struct PlmsSched {
+    float* sample;
+    float* cur;
+    float* ets;
+    const pdmk_plms_row* table;
+    __device__ int64_t t(int step) const { return table[step].t; }
+    __device__ float operator()(int step, float g, long i, long N) const {
+        const pdmk_plms_row& r = table[step];
+        float eps, base = sample[i];
+        if (r.mode == 0) {                                        // counter 0: ets = [g], cur_sample = sample
+            eps = g;
+            cur[i] = base;
+        } else if (r.mode == 1) {                                 // counter 1: (g + ets[-1]) / 2 on cur_sample
+            eps = form(r.coef[1], ets[(r.rslot[0] & 3) * N + i], r.coef[0], g);
+            base = cur[i];
+        } else {                                                  // linear multistep over ets[-1 .. -nterms]
+            eps = form(r.coef[1], ets[(r.rslot[0] & 3) * N + i], r.coef[0], g);
+            const int nterms = min(r.nterms, 4);
+            for (int k = 2; k < nterms; ++k) eps = form(r.coef[k], ets[(r.rslot[k - 1] & 3) * N + i], 1.f, eps);
+        }
+        if (r.wslot >= 0) ets[(r.wslot & 3) * N + i] = g;        // (slots masked: a bad table cannot write outside ets)
+        if (r.vpred) eps = form(r.v_x, base, r.v_v, eps);           // eps = sqrt(a) v + sqrt(1 - a) x
+        const float prev = form(r.eps_scale, eps, r.x_scale, base);
+        sample[i] = prev;
+        return prev;
+    }
+};
+
+// DDIM (eta 0): the step is linear in (sample, model output), so one table row is the timestep and DDIMScheduler.coefficients.
+struct DdimSched {
+    float* sample;
+    const pdmk_ddim_row* table;
+    __device__ int64_t t(int step) const { return table[step].t; }
+    __device__ float operator()(int step, float g, long i, long) const {
+        const float prev = form(table[step].c_m, g, table[step].c_x, sample[i]);      // axpby(model_output, prev, c_m, c_x)
+        sample[i] = prev;
+        return prev;
+    }
+};
+
+// One launch between two U-Net calls: guidance, scheduler step, the next call's input (one copy per branch) and timesteps,
+// and the step counter.  pdmk_plms_step, pdmk_ddim_step and their SLD forms are its four instances per dtype.
+template <typename T, typename Guide, typename Sched>
+__global__ void step_kernel(const T* __restrict__ pred, int ld, Guide guide, Sched sched, int nsteps, int32_t* state,
+                            int64_t* __restrict__ t_out, T* __restrict__ x_next, int cpad, int B, int C, int HW) {
     const int step = state[0];
     if (step < 0 || step >= nsteps) return;          // every workgroup reads the same counter: all of them return
-    const pdmk_plms_row& r = table[step];
     const long N = (long)B * C * HW;                 // one history slot
     const long npix = (long)B * HW;
-    const long half = npix * cpad;                   // rows of one CFG half in x_next
+    const long part = npix * cpad;                   // elements of one branch's rows in x_next
+    const int copies = guide.copies();
     for (long p = blockIdx.x * (long)NT + threadIdx.x; p < npix; p += (long)gridDim.x * NT) {
         const int b = (int)(p / HW);
         const int px = (int)(p - (long)b * HW);
-        const T* pu = pred + p * ld;                                  // unconditional half (or the only one)
-        const T* pt = pred + (p + npix) * ld;                         // text half
         T* xo = x_next + p * cpad;
         for (int c = 0; c < C; ++c) {
             const long i = ((long)b * C + c) * HW + px;               // NCHW index of the latent element
-            float g = to_f32(pu[c]);
-            if (cfg) g = form(g_u, g, g_t, to_f32(pt[c]));           // axpby(out[:B], out[B:], 1 - g, g)
-            float eps, base = sample[i];
-            if (r.mode == 0) {                                        // counter 0: ets = [g], cur_sample = sample
-                eps = g;
-                cur[i] = base;
-            } else if (r.mode == 1) {                                 // counter 1: (g + ets[-1]) / 2 on cur_sample
-                eps = form(r.coef[1], ets[(r.rslot[0] & 3) * N + i], r.coef[0], g);
-                base = cur[i];
-            } else {                                                  // linear multistep over ets[-1 .. -nterms]
-                eps = form(r.coef[1], ets[(r.rslot[0] & 3) * N + i], r.coef[0], g);
-                const int nterms = min(r.nterms, 4);
-                for (int k = 2; k < nterms; ++k) eps = form(r.coef[k], ets[(r.rslot[k - 1] & 3) * N + i], 1.f, eps);
-            }
-            if (r.wslot >= 0) ets[(r.wslot & 3) * N + i] = g;    // (slots masked: a bad table cannot write outside ets)
-            if (r.vpred) eps = form(r.v_x, base, r.v_v, eps);       // eps = sqrt(a) v + sqrt(1 - a) x
-            const float prev = form(r.eps_scale, eps, r.x_scale, base);
-            sample[i] = prev;
+            const float prev = sched(step, guide(pred, ld, p, npix, c, i, step), i, N);
             const T o = from_f32<T>(prev);
-            xo[c] = o;
-            if (cfg) xo[half + c] = o;
+            for (int k = 0; k < copies; ++k) xo[k * part + c] = o;
         }
-        for (int c = C; c < cpad; ++c) {                              // padding channels, as nchw2nhwc_kernel leaves them
-            xo[c] = from_f32<T>(0.f);
-            if (cfg) xo[half + c] = from_f32<T>(0.f);
-        }
+        for (int c = C; c < cpad; ++c)                                // padding channels, as nchw2nhwc_kernel leaves them
+            for (int k = 0; k < copies; ++k) xo[k * part + c] = from_f32<T>(0.f);
     }
     if (blockIdx.x == 0 && step + 1 < nsteps) {                       // the next U-Net call's timesteps
-        const int nt = cfg ? 2 * B : B;
-        for (int j = threadIdx.x; j < nt; j += NT) t_out[j] = table[step + 1].t;
+        const int nt = copies * B;
+        for (int j = threadIdx.x; j < nt; j += NT) t_out[j] = sched.t(step + 1);
     }
     // advance the counter once every workgroup has read it: the last one to finish does it (and re-arms the ticket)
     __shared__ int last;
@@ -85,53 +152,44 @@ __global__ void plms_step_kernel(const T* __restrict__ pred, int ld, float g_u, 
     }
 }
 
-// DDIM (eta 0): the step is linear in (sample, model output), so one table row is the timestep and DDIMScheduler.coefficients.
-// Counter, ticket, t_out and x_next are plms_step_kernel's.
-template <typename T>
-__global__ void ddim_step_kernel(const T* __restrict__ pred, int ld, float g_u, float g_t, int cfg,
-                                 float* __restrict__ sample, const pdmk_ddim_row* __restrict__ table, int nsteps,
-                                 int32_t* state, int64_t* __restrict__ t_out, T* __restrict__ x_next, int cpad, int B, int C,
-                                 int HW) {
-    const int step = state[0];
-    if (step < 0 || step >= nsteps) return;          // every workgroup reads the same counter: all of them return
-    const float c_x = table[step].c_x, c_m = table[step].c_m;
-    const long npix = (long)B * HW;
-    const long half = npix * cpad;                   // rows of one CFG half in x_next
-    for (long p = blockIdx.x * (long)NT + threadIdx.x; p < npix; p += (long)gridDim.x * NT) {
-        const int b = (int)(p / HW);
-        const int px = (int)(p - (long)b * HW);
-        const T* pu = pred + p * ld;                                  // unconditional half (or the only one)
-        const T* pt = pred + (p + npix) * ld;                         // text half
-        T* xo = x_next + p * cpad;
-        for (int c = 0; c < C; ++c) {
-            const long i = ((long)b * C + c) * HW + px;               // NCHW index of the latent element
-            float g = to_f32(pu[c]);
-            if (cfg) g = form(g_u, g, g_t, to_f32(pt[c]));           // axpby(out[:B], out[B:], 1 - g, g)
-            const float prev = form(c_m, g, c_x, sample[i]);          // axpby(model_output, prev, c_m, c_x)
-            sample[i] = prev;
-            const T o = from_f32<T>(prev);
-            xo[c] = o;
-            if (cfg) xo[half + c] = o;
+template <typename Guide, typename Sched>
+int launch_step(const void* pred, int ld, const Guide& guide, const Sched& sched, int nsteps, int32_t* state, int64_t* t_out,
+                void* x_next, int cpad, int B, int C, int HW, int dtype, pdmk_stream s) {
+    const dim3 grid(grid_for((long)B * HW));
+    if (dtype == PDMK_BF16)
+        hipLaunchKernelGGL((step_kernel<bf16, Guide, Sched>), grid, dim3(NT), 0, (hipStream_t)s, (const bf16*)pred, ld, guide,
+                           sched, nsteps, state, t_out, (bf16*)x_next, cpad, B, C, HW);
+    else if (dtype == PDMK_F32)
+        hipLaunchKernelGGL((step_kernel<float, Guide, Sched>), grid, dim3(NT), 0, (hipStream_t)s, (const float*)pred, ld, guide,
+                           sched, nsteps, state, t_out, (float*)x_next, cpad, B, C, HW);
+    else return -2;
+    PDMK_CHECK_LAUNCH();
+    return 0;
+}
+
+// The eager loop's SLD guidance on fp32 NCHW thirds: 16-byte loads and stores when n and the pointers allow.
+template <int V>
+__global__ void sld_guidance_kernel(const float* __restrict__ pred, float* __restrict__ out, float* __restrict__ mom, long n,
+                                    float g, pdmk_sld_params q, int apply) {
+    const long nv = n / V;
+    for (long j = blockIdx.x * (long)NT + threadIdx.x; j < nv; j += (long)gridDim.x * NT) {
+        float u[V], t[V], s[V], m[V], o[V];
+        if (V == 4) {
+            *reinterpret_cast<float4*>(u) = reinterpret_cast<const float4*>(pred)[j];
+            *reinterpret_cast<float4*>(t) = reinterpret_cast<const float4*>(pred + n)[j];
+            *reinterpret_cast<float4*>(s) = reinterpret_cast<const float4*>(pred + 2 * n)[j];
+            *reinterpret_cast<float4*>(m) = reinterpret_cast<const float4*>(mom)[j];
+        } else {
+            u[0] = pred[j], t[0] = pred[n + j], s[0] = pred[2 * n + j], m[0] = mom[j];
         }
-        for (int c = C; c < cpad; ++c) {                              // padding channels, as nchw2nhwc_kernel leaves them
-            xo[c] = from_f32<T>(0.f);
-            if (cfg) xo[half + c] = from_f32<T>(0.f);
+#pragma unroll
+        for (int e = 0; e < V; ++e) o[e] = sld_chain(u[e], t[e], s[e], m[e], g, q, apply != 0);
+        if (V == 4) {
+            reinterpret_cast<float4*>(out)[j] = *reinterpret_cast<const float4*>(o);
+            reinterpret_cast<float4*>(mom)[j] = *reinterpret_cast<const float4*>(m);
+        } else {
+            out[j] = o[0], mom[j] = m[0];
         }
-    }
-    if (blockIdx.x == 0 && step + 1 < nsteps) {                       // the next U-Net call's timesteps
-        const int nt = cfg ? 2 * B : B;
-        for (int j = threadIdx.x; j < nt; j += NT) t_out[j] = table[step + 1].t;
-    }
-    __shared__ int last;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        __threadfence();
-        last = atomicAdd(reinterpret_cast<unsigned*>(state + 1), 1u) == gridDim.x - 1;
-    }
-    __syncthreads();
-    if (last && threadIdx.x == 0) {
-        atomicExch(state + 1, 0);
-        atomicExch(state, step + 1);
     }
 }
 
@@ -161,16 +219,8 @@ extern "C" int pdmk_plms_step(const void* pred, int ld, float g_u, float g_t, in
     if (!pred || !sample || !cur || !ets || !table || !state || !t_out || !x_next || nsteps <= 0 || B <= 0 || C <= 0 ||
         HW <= 0 || ld < C || cpad < C)
         return -1;
-    const dim3 grid(grid_for((long)B * HW));
-    if (dtype == PDMK_BF16)
-        hipLaunchKernelGGL(plms_step_kernel<bf16>, grid, dim3(NT), 0, (hipStream_t)s, (const bf16*)pred, ld, g_u, g_t, cfg,
-                           sample, cur, ets, table, nsteps, state, t_out, (bf16*)x_next, cpad, B, C, HW);
-    else if (dtype == PDMK_F32)
-        hipLaunchKernelGGL(plms_step_kernel<float>, grid, dim3(NT), 0, (hipStream_t)s, (const float*)pred, ld, g_u, g_t, cfg,
-                           sample, cur, ets, table, nsteps, state, t_out, (float*)x_next, cpad, B, C, HW);
-    else return -2;
-    PDMK_CHECK_LAUNCH();
-    return 0;
+    return launch_step(pred, ld, CfgGuide{g_u, g_t, cfg}, PlmsSched{sample, cur, ets, table}, nsteps, state, t_out, x_next, cpad,
+                       B, C, HW, dtype, s);
 }
 
 extern "C" int pdmk_ddim_step(const void* pred, int ld, float g_u, float g_t, int cfg, float* sample,
@@ -179,16 +229,43 @@ extern "C" int pdmk_ddim_step(const void* pred, int ld, float g_u, float g_t, in
     if (!pred || !sample || !table || !state || !t_out || !x_next || nsteps <= 0 || B <= 0 || C <= 0 || HW <= 0 || ld < C ||
         cpad < C)
         return -1;
-    const dim3 grid(grid_for((long)B * HW));
-    if (dtype == PDMK_BF16)
-        hipLaunchKernelGGL(ddim_step_kernel<bf16>, grid, dim3(NT), 0, (hipStream_t)s, (const bf16*)pred, ld, g_u, g_t, cfg,
-                           sample, table, nsteps, state, t_out, (bf16*)x_next, cpad, B, C, HW);
-    else if (dtype == PDMK_F32)
-        hipLaunchKernelGGL(ddim_step_kernel<float>, grid, dim3(NT), 0, (hipStream_t)s, (const float*)pred, ld, g_u, g_t, cfg,
-                           sample, table, nsteps, state, t_out, (float*)x_next, cpad, B, C, HW);
-    else return -2;
+    return launch_step(pred, ld, CfgGuide{g_u, g_t, cfg}, DdimSched{sample, table}, nsteps, state, t_out, x_next, cpad, B, C, HW,
+                       dtype, s);
+}
+
+extern "C" int pdmk_sld_guidance(const float* pred, float* out, float* mom, int B, int C, int HW, float guidance_scale,
+                                 const pdmk_sld_params* params, int apply, pdmk_stream s) {
+    if (!pred || !out || !mom || !params || B <= 0 || C <= 0 || HW <= 0) return -1;
+    const long n = (long)B * C * HW;
+    const bool wide = n % 4 == 0 && ((uintptr_t)pred | (uintptr_t)out | (uintptr_t)mom) % 16 == 0;
+    if (wide)
+        hipLaunchKernelGGL(sld_guidance_kernel<4>, dim3(grid_for(n / 4)), dim3(NT), 0, (hipStream_t)s, pred, out, mom, n,
+                           guidance_scale, *params, apply);
+    else
+        hipLaunchKernelGGL(sld_guidance_kernel<1>, dim3(grid_for(n)), dim3(NT), 0, (hipStream_t)s, pred, out, mom, n,
+                           guidance_scale, *params, apply);
     PDMK_CHECK_LAUNCH();
     return 0;
+}
+
+extern "C" int pdmk_sld_plms_step(const void* pred, int ld, float guidance_scale, const pdmk_sld_params* params, float* mom,
+                                  float* sample, float* cur, float* ets, const pdmk_plms_row* table, int nsteps, int32_t* state,
+                                  int64_t* t_out, void* x_next, int cpad, int B, int C, int HW, int dtype, pdmk_stream s) {
+    if (!pred || !params || !mom || !sample || !cur || !ets || !table || !state || !t_out || !x_next || nsteps <= 0 || B <= 0 ||
+        C <= 0 || HW <= 0 || ld < C || cpad < C)
+        return -1;
+    return launch_step(pred, ld, SldGuide{guidance_scale, *params, mom}, PlmsSched{sample, cur, ets, table}, nsteps, state, t_out,
+                       x_next, cpad, B, C, HW, dtype, s);
+}
+
+extern "C" int pdmk_sld_ddim_step(const void* pred, int ld, float guidance_scale, const pdmk_sld_params* params, float* mom,
+                                  float* sample, const pdmk_ddim_row* table, int nsteps, int32_t* state, int64_t* t_out,
+                                  void* x_next, int cpad, int B, int C, int HW, int dtype, pdmk_stream s) {
+    if (!pred || !params || !mom || !sample || !table || !state || !t_out || !x_next || nsteps <= 0 || B <= 0 || C <= 0 ||
+        HW <= 0 || ld < C || cpad < C)
+        return -1;
+    return launch_step(pred, ld, SldGuide{guidance_scale, *params, mom}, DdimSched{sample, table}, nsteps, state, t_out, x_next,
+                       cpad, B, C, HW, dtype, s);
 }
 
 extern "C" int pdmk_image_to_u8_ex(const float* src, uint8_t* dst, int B, int C, int HW, int rounding, pdmk_stream s) {

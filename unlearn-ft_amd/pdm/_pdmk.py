@@ -58,6 +58,17 @@ class DdimRow(C.Structure):
     _fields_ = [("t", i64), ("c_x", f32), ("c_m", f32), ("pad_", i64)]
 
 
+class SldParams(C.Structure):
+    """pdmk_sld_params (include/pdmk.h): Safe Latent Diffusion's scalars as the kernels take them.  Build it with
+    sld_params(): the fp32 fields are rounded from doubles, one_minus_beta from the double 1 - mom_beta."""
+    _fields_ = [("sld_guidance_scale", f32), ("threshold", f32), ("momentum_scale", f32), ("mom_beta", f32),
+                ("one_minus_beta", f32), ("warmup_steps", i32)]
+
+    def key(self):
+        return (self.sld_guidance_scale, self.threshold, self.momentum_scale, self.mom_beta, self.one_minus_beta,
+                self.warmup_steps)
+
+
 _SIGS = {
     "pdmk_version": ([], i32),
     "pdmk_gemm": ([C.POINTER(GemmArgs), vp], i32),
@@ -124,6 +135,10 @@ _SIGS = {
     "pdmk_cosine_pairs": ([vp, i32, vp, i32, vp, i32, vp, vp, vp, i32, i32, vp], i32),
     "pdmk_plms_step": ([vp, i32, f32, f32, i32, vp, vp, vp, vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, vp], i32),
     "pdmk_ddim_step": ([vp, i32, f32, f32, i32, vp, vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, vp], i32),
+    "pdmk_sld_guidance": ([vp, vp, vp, i32, i32, i32, f32, C.POINTER(SldParams), i32, vp], i32),
+    "pdmk_sld_plms_step": ([vp, i32, f32, C.POINTER(SldParams), vp, vp, vp, vp, vp, i32, vp, vp, vp, i32, i32, i32, i32, i32,
+                            vp], i32),
+    "pdmk_sld_ddim_step": ([vp, i32, f32, C.POINTER(SldParams), vp, vp, vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, vp], i32),
     "pdmk_image_to_u8": ([vp, vp, i32, i32, i32, vp], i32),
     "pdmk_image_to_u8_ex": ([vp, vp, i32, i32, i32, i32, vp], i32),
     "pdmk_resize_bilinear_u8": ([vp, i64, vp, vp, i32, i32, vp, vp], i32),
@@ -951,6 +966,59 @@ def ddim_step(pred, ld, g_u, g_t, cfg, sample, table, nsteps, state, t_out, x_ne
         raise PdmkError("ddim_step: inconsistent buffers")
     _chk(_lib.pdmk_ddim_step(_p(pred), ld, float(g_u), float(g_t), int(bool(cfg)), _p(sample), _p(table), nsteps, _p(state),
                              _p(t_out), _p(x_next), cpad, B, Cc, HW, dt(pred), _st()), "pdmk_ddim_step")
+
+
+def sld_params(sld_guidance_scale, warmup_steps, threshold, momentum_scale, mom_beta):
+    """The five SLD scalars (Python numbers, i.e. doubles) -> SldParams: each rounded once to fp32, `1 - mom_beta` formed in
+    double first - what torch does with a Python scalar operand of an fp32 tensor."""
+    return SldParams(sld_guidance_scale=float(sld_guidance_scale), threshold=float(threshold),
+                     momentum_scale=float(momentum_scale), mom_beta=float(mom_beta), one_minus_beta=1.0 - float(mom_beta),
+                     warmup_steps=int(warmup_steps))
+
+
+def _f32c(*ts):
+    return all(t.dtype == torch.float32 and t.is_contiguous() for t in ts)
+
+
+def sld_guidance(pred, out, mom, guidance_scale, params, apply):
+    """SLD guidance of the eager loop (include/pdmk.h pdmk_sld_guidance): pred fp32 [3B, C, H, W] contiguous (uncond, text,
+    safety) -> out fp32 [B, C, H, W]; mom fp32 [B, C, H, W] updated in place.  apply: call index >= warm-up."""
+    if (not _f32c(pred, out, mom) or pred.dim() != 4 or pred.shape[0] % 3 or out.shape != mom.shape
+            or tuple(out.shape) != (pred.shape[0] // 3,) + tuple(pred.shape[1:]) or not isinstance(params, SldParams)):
+        raise PdmkError("sld_guidance: pred fp32 [3B, C, H, W], out / mom fp32 [B, C, H, W], contiguous; params SldParams")
+    B, Cc, H, W = out.shape
+    _chk(_lib.pdmk_sld_guidance(_p(pred), _p(out), _p(mom), B, Cc, H * W, float(guidance_scale), C.byref(params),
+                                int(bool(apply)), _st()), "pdmk_sld_guidance")
+
+
+def _sld_step_ok(pred, ld, params, mom, sample, table, row, nsteps, state, t_out, x_next, cpad, B, Cc, HW):
+    n, rows = B * Cc * HW, 3 * B * HW
+    return (isinstance(params, SldParams) and pred.dtype == x_next.dtype and ld >= Cc and cpad >= Cc
+            and _avail(pred) >= (rows - 1) * ld + Cc and x_next.numel() >= rows * cpad and x_next.is_contiguous()
+            and _f32c(mom, sample) and mom.numel() == n and sample.numel() == n and table.dtype == torch.uint8
+            and table.numel() == nsteps * C.sizeof(row) and state.dtype == torch.int32 and state.numel() == 2
+            and t_out.dtype == torch.int64 and t_out.numel() >= 3 * B)
+
+
+def sld_plms_step(pred, ld, guidance_scale, params, mom, sample, cur, ets, table, nsteps, state, t_out, x_next, cpad, B, Cc,
+                  HW):
+    """plms_step with SLD guidance (include/pdmk.h pdmk_sld_plms_step): pred / x_next rows of 3B * HW pixels (uncond, text,
+    safety); mom fp32 [B*Cc*HW]; the warm-up is decided on the device from state[0] and params.warmup_steps."""
+    n = B * Cc * HW
+    if (not _sld_step_ok(pred, ld, params, mom, sample, table, PlmsRow, nsteps, state, t_out, x_next, cpad, B, Cc, HW)
+            or not _f32c(cur, ets) or cur.numel() != n or ets.numel() != 4 * n):
+        raise PdmkError("sld_plms_step: inconsistent buffers")
+    _chk(_lib.pdmk_sld_plms_step(_p(pred), ld, float(guidance_scale), C.byref(params), _p(mom), _p(sample), _p(cur), _p(ets),
+                                 _p(table), nsteps, _p(state), _p(t_out), _p(x_next), cpad, B, Cc, HW, dt(pred), _st()),
+         "pdmk_sld_plms_step")
+
+
+def sld_ddim_step(pred, ld, guidance_scale, params, mom, sample, table, nsteps, state, t_out, x_next, cpad, B, Cc, HW):
+    """ddim_step with SLD guidance (include/pdmk.h pdmk_sld_ddim_step); buffers as sld_plms_step, no history."""
+    if not _sld_step_ok(pred, ld, params, mom, sample, table, DdimRow, nsteps, state, t_out, x_next, cpad, B, Cc, HW):
+        raise PdmkError("sld_ddim_step: inconsistent buffers")
+    _chk(_lib.pdmk_sld_ddim_step(_p(pred), ld, float(guidance_scale), C.byref(params), _p(mom), _p(sample), _p(table), nsteps,
+                                 _p(state), _p(t_out), _p(x_next), cpad, B, Cc, HW, dt(pred), _st()), "pdmk_sld_ddim_step")
 
 
 def _u8_shape(src, dst, name):

@@ -14,6 +14,10 @@ device-side step counter and refreshes the U-Net's timestep buffer from a step t
 It is bit-identical to the eager loop (the kernel repeats pdmk_axpby's fp32 arithmetic operation by operation; DESIGN.md
 9.1).  `callback=`, block hooks, an `ffn_observer` on the U-Net's engine or PDMK_SAMPLER_GRAPH=0 select the eager loop; so
 does a DDIMScheduler unless the caller passes graph=True (pdmk_ddim_step is then the step kernel).
+
+Safe Latent Diffusion (`safety_concept=` and the `sld_*` keywords) adds a third row block conditioned on a safety
+concept: the eager loop calls pdmk_sld_guidance before scheduler.step, the captured loop's step kernel is pdmk_sld_plms_step /
+pdmk_sld_ddim_step on 3B rows.  With SLD off nothing of it runs: the same loops, launches and bits as without the keywords.
 """
 import ctypes
 import gc
@@ -25,6 +29,7 @@ import torch
 
 from .. import _pdmk as k
 from ..models.unet.spec import padc
+from ..utils.sld import is_active as sld_is_active
 
 
 # Adams-Bashforth weights of the linear multistep update by history length, newest model output first (PLMS)
@@ -217,7 +222,7 @@ class _CapturedLoop:
     steps, N for N DDIM steps), or fewer when the caller stops early.  The graph reads the U-Net's weight arenas in place: it
     stays valid while an optimiser rewrites them."""
 
-    def __init__(self, unet, B, h, w, cfg_on, guidance_scale, nsteps, T, ctx, kind="plms"):
+    def __init__(self, unet, B, h, w, cfg_on, guidance_scale, nsteps, T, ctx, kind="plms", sld=None):
         dev, dt = unet.device, unet.dtype
         if kind not in ("plms", "ddim"):
             raise ValueError(f"_CapturedLoop: step kind {kind!r}")
@@ -225,7 +230,10 @@ class _CapturedLoop:
         self.Row = k.PlmsRow if kind == "plms" else k.DdimRow
         self.unet, self.B, self.C, self.h, self.w, self.cfg_on, self.nsteps = unet, B, unet.cfg.in_channels, h, w, cfg_on, nsteps
         self.g = (float(1.0 - guidance_scale), float(guidance_scale))       # axpby(out[:B], out[B:], 1 - g, g)
-        self.R, self.cp = (2 * B if cfg_on else B), padc(self.C)
+        self.sld = sld                  # k.SldParams: the 3B form (uncond, text, safety rows; Safe Latent Diffusion guidance)
+        if sld is not None and not cfg_on:
+            raise ValueError("_CapturedLoop: SLD needs classifier-free guidance")
+        self.R, self.cp = (3 * B if sld is not None else 2 * B if cfg_on else B), padc(self.C)
         n = B * self.C * h * w
         self.x = torch.zeros((self.R * h * w, self.cp), device=dev, dtype=dt)
         self.t = torch.zeros(self.R, device=dev, dtype=torch.int64)
@@ -234,6 +242,8 @@ class _CapturedLoop:
         if kind == "plms":
             self.cur = torch.zeros(n, device=dev)
             self.ets = torch.zeros(4, n, device=dev)
+        if sld is not None:
+            self.mom = torch.zeros(n, device=dev)
         self.state = torch.zeros(2, device=dev, dtype=torch.int32)
         self.table = torch.zeros(nsteps * ctypes.sizeof(self.Row), device=dev, dtype=torch.uint8)
         self.graph, self.keep = None, []
@@ -241,7 +251,14 @@ class _CapturedLoop:
 
     def _body(self):
         pred, _ = self.unet.forward_nhwc(self.x, self.t, self.ehs, self.R, self.h, self.w, train=False)
-        if self.kind == "plms":
+        if self.sld is not None:
+            if self.kind == "plms":
+                k.sld_plms_step(pred.t, pred.t.stride(0), self.g[1], self.sld, self.mom, self.sample, self.cur, self.ets,
+                                self.table, self.nsteps, self.state, self.t, self.x, self.cp, self.B, self.C, self.h * self.w)
+            else:
+                k.sld_ddim_step(pred.t, pred.t.stride(0), self.g[1], self.sld, self.mom, self.sample, self.table, self.nsteps,
+                                self.state, self.t, self.x, self.cp, self.B, self.C, self.h * self.w)
+        elif self.kind == "plms":
             k.plms_step(pred.t, pred.t.stride(0), *self.g, self.cfg_on, self.sample, self.cur, self.ets, self.table,
                         self.nsteps, self.state, self.t, self.x, self.cp, self.B, self.C, self.h * self.w)
         else:
@@ -287,8 +304,8 @@ class _CapturedLoop:
 
     def run(self, latents, ehs, rows, n_calls=None):
         """latents: fp32 [B, C, h, w] (contiguous, on the device); ehs: [R, T, ctx] text embeddings (unconditional half
-        first); rows: the scheduler's plms_rows() / ddim_rows(); n_calls: U-Net calls to replay (None: all of them).  Returns
-        the latents after them (a new tensor)."""
+        first, with SLD the safety third last); rows: the scheduler's plms_rows() / ddim_rows(); n_calls: U-Net calls to
+        replay (None: all of them).  Returns the latents after them (a new tensor)."""
         B, C, HW = self.B, self.C, self.h * self.w
         n_calls = self.nsteps if n_calls is None else int(n_calls)
         if len(rows) != self.nsteps or not 0 <= n_calls <= self.nsteps:
@@ -299,6 +316,9 @@ class _CapturedLoop:
         k.nchw_to_nhwc(latents, self.x, B, C, HW, self.cp)
         if self.cfg_on:
             k.nchw_to_nhwc(latents, self.x[B * HW:], B, C, HW, self.cp)
+        if self.sld is not None:
+            k.nchw_to_nhwc(latents, self.x[2 * B * HW:], B, C, HW, self.cp)
+            self.mom.zero_()
         self.t.fill_(rows[0].t)
         self.state.zero_()
         for _ in range(n_calls):
@@ -355,14 +375,16 @@ class StableDiffusionPruningPipeline:
             return False
         return graph is True or os.environ.get("PDMK_SAMPLER_GRAPH", "1") != "0"
 
-    def _loop(self, B, h, w, cfg_on, guidance_scale, nsteps, T, ctx):
+    def _loop(self, B, h, w, cfg_on, guidance_scale, nsteps, T, ctx, sld=None):
         key = (B, h, w, self.unet.dtype, cfg_on, nsteps, T, ctx, float(guidance_scale), type(self.scheduler))
+        if sld is not None:
+            key += ("sld",) + sld.key()
         loop = self._loops.pop(key, None)
         if loop is None:
             while len(self._loops) >= self.GRAPH_SHAPES:
                 self._loops.pop(next(iter(self._loops))).close()
             loop = _CapturedLoop(self.unet, B, h, w, cfg_on, guidance_scale, nsteps, T, ctx,
-                                 kind="ddim" if type(self.scheduler) is DDIMScheduler else "plms")
+                                 kind="ddim" if type(self.scheduler) is DDIMScheduler else "plms", sld=sld)
             self.captures += 1
         self._loops[key] = loop                                       # most recently used last
         return loop
@@ -371,15 +393,27 @@ class StableDiffusionPruningPipeline:
     def generate_samples(self, prompt_ids=None, height=None, width=None, num_inference_steps=50, guidance_scale=7.5,
                          negative_prompt_ids=None, generator=None, latents=None, prompt_embeds=None,
                          negative_prompt_embeds=None, output_type="np", return_dict=True, callback=None, callback_steps=1,
-                         prompt=None, negative_prompt=None, graph=None, end_iteration=None):
+                         prompt=None, negative_prompt=None, graph=None, end_iteration=None, safety_concept=None,
+                         safety_concept_ids=None, safety_concept_embeds=None, sld_guidance_scale=1000.0, sld_warmup_steps=10,
+                         sld_threshold=0.01, sld_momentum_scale=0.3, sld_mom_beta=0.4):
         """prompt / negative_prompt: strings or lists of strings (needs the tokenizer; with guidance and no negative prompt
         the empty prompt).  output_type "latent", "pt", "np" (float32 NHWC in [0, 1]), "u8" (uint8 NHWC numpy, the FID
         script's `(img * 255).astype(np.uint8)`, formed on the device) or "u8_round" (the same with diffusers' numpy_to_pil
         rounding, `(img * 255).round().astype("uint8")`: the pixels of `pipeline(prompt).images`).  graph: None = the captured loop when possible
         (PDMK_SAMPLER_GRAPH=0 turns it off), False = the eager loop, True = captured whenever possible (a DDIMScheduler's loop
         is captured only with True).  end_iteration: stop after that many scheduler steps and return the latents there (ESD's
-        partial sampling)."""
+        partial sampling).
+        safety_concept (a string, needs the tokenizer) / safety_concept_ids ([1, T] token ids) / safety_concept_embeds
+        ([1, T, ctx]): Safe Latent Diffusion - a third U-Net branch conditioned on the concept, whose direction is subtracted
+        from the guidance where the text prediction leans towards it (include/pdmk.h pdmk_sld_params; the five sld_* keywords
+        default to diffusers' StableDiffusionPipelineSafe's, the Medium preset of configs/baselines/sld.yaml).  Active only
+        with a concept, sld_guidance_scale > 1 and guidance_scale > 1; otherwise the keywords change nothing.  The concept is
+        encoded once per call and repeated over the batch; the warm-up counts U-Net calls (PNDM's repeated call included)."""
         cfg_on = guidance_scale > 1.0
+        has_concept = safety_concept is not None or safety_concept_ids is not None or safety_concept_embeds is not None
+        sld = None
+        if sld_is_active(guidance_scale, sld_guidance_scale, has_concept):
+            sld = k.sld_params(sld_guidance_scale, sld_warmup_steps, sld_threshold, sld_momentum_scale, sld_mom_beta)
         if isinstance(prompt_ids, (str, list, tuple)):            # the reference's positional `prompt`
             prompt, prompt_ids = prompt_ids, None
         if prompt is not None and prompt_ids is None and prompt_embeds is None:
@@ -403,6 +437,8 @@ class StableDiffusionPruningPipeline:
                              "caller)")
         dev = self.device
         ehs = torch.cat([negative_prompt_embeds.to(dev), prompt_embeds.to(dev)]) if cfg_on else prompt_embeds.to(dev)
+        if sld is not None:
+            ehs = torch.cat([ehs, self._safety_embeds(safety_concept, safety_concept_ids, safety_concept_embeds, B, ehs)])
         sch = self.scheduler
         sch.set_timesteps(num_inference_steps, device=dev)
         C = self.unet.cfg.in_channels
@@ -413,11 +449,13 @@ class StableDiffusionPruningPipeline:
         if end_iteration is not None and not 0 <= int(end_iteration) <= len(sch.timesteps):
             raise ValueError(f"end_iteration={end_iteration} outside 0 ... {len(sch.timesteps)}")
         if self._use_graph(graph, callback):
-            loop = self._loop(B, shape[2], shape[3], cfg_on, guidance_scale, len(sch.timesteps), ehs.shape[1], ehs.shape[2])
+            loop = self._loop(B, shape[2], shape[3], cfg_on, guidance_scale, len(sch.timesteps), ehs.shape[1], ehs.shape[2],
+                              sld=sld)
             rows = sch.ddim_rows() if loop.kind == "ddim" else sch.plms_rows()
             latents = loop.run(latents, ehs, rows, n_calls=end_iteration)
         else:
-            latents = self._eager_loop(latents, ehs, B, shape, cfg_on, guidance_scale, callback, callback_steps, end_iteration)
+            latents = self._eager_loop(latents, ehs, B, shape, cfg_on, guidance_scale, callback, callback_steps, end_iteration,
+                                       sld=sld)
         if output_type == "latent":
             image = latents
         else:
@@ -436,19 +474,42 @@ class StableDiffusionPruningPipeline:
                     image = image.permute(0, 2, 3, 1).cpu().numpy()
         return SimpleNamespace(images=image, nsfw_content_detected=None) if return_dict else (image, None)
 
-    def _eager_loop(self, latents, ehs, B, shape, cfg_on, guidance_scale, callback, callback_steps, end_iteration=None):
+    def _safety_embeds(self, concept, ids, embeds, B, ehs):
+        """The safety concept's text embeddings [B, T, ctx]: encoded once, repeated over the batch."""
+        if embeds is None:
+            if ids is None:
+                ids = self._tokenize(concept if isinstance(concept, str) else list(concept))
+            embeds = self.text_encoder(ids.to(self.device))[0]
+        embeds = embeds.to(self.device)
+        if embeds.dim() == 2:
+            embeds = embeds[None]
+        if embeds.shape[0] != 1 or tuple(embeds.shape[1:]) != tuple(ehs.shape[1:]):
+            raise ValueError(f"safety concept embeddings {tuple(embeds.shape)}: expected one concept of shape "
+                             f"{(1,) + tuple(ehs.shape[1:])}")
+        return embeds.to(ehs.dtype).expand(B, -1, -1)
+
+    def _eager_loop(self, latents, ehs, B, shape, cfg_on, guidance_scale, callback, callback_steps, end_iteration=None,
+                    sld=None):
         dev, sch = self.device, self.scheduler
         was_training = self.unet.training
         self.unet.eval()
         try:
-            x2 = torch.empty((2 * B if cfg_on else B,) + shape[1:], device=dev, dtype=torch.float32)
+            x2 = torch.empty((3 * B if sld is not None else 2 * B if cfg_on else B,) + shape[1:], device=dev,
+                             dtype=torch.float32)
+            if sld is not None:
+                mom = torch.zeros(shape, device=dev, dtype=torch.float32)
             for i, t in enumerate(sch.timesteps.tolist()[:end_iteration]):
                 x2[:B].copy_(latents)
                 if cfg_on:
-                    x2[B:].copy_(latents)
+                    x2[B:2 * B].copy_(latents)
+                if sld is not None:
+                    x2[2 * B:].copy_(latents)
                 tt = torch.full((x2.shape[0],), t, device=dev, dtype=torch.int64)
                 out = self.unet(sch.scale_model_input(x2, t), tt, ehs, return_dict=False)[0]
-                if cfg_on:        # uncond + g (text - uncond) = (1 - g) uncond + g text, in place on the text half
+                if sld is not None:
+                    noise = torch.empty(shape, device=dev, dtype=torch.float32)
+                    k.sld_guidance(out.contiguous(), noise, mom, guidance_scale, sld, i >= sld.warmup_steps)
+                elif cfg_on:      # uncond + g (text - uncond) = (1 - g) uncond + g text, in place on the text half
                     noise = out[B:]
                     k.axpby(out[:B], noise, 1.0 - guidance_scale, guidance_scale)
                 else:

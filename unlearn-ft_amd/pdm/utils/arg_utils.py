@@ -42,6 +42,9 @@ def parse_args(argv=None):
                    help="with --hip_graphs: look one batch ahead, the frozen teacher's pass over it runs beside this step's backward")
     p.add_argument("--image_resolution", type=int, default=512,
                    help="scripts/metrics/generate_fid_images.py: side of the generated images (the reference: 512)")
+    p.add_argument("--sld_type", type=str, default=None,
+                   help="scripts/metrics/generate_fid_images.py: sample with this Safe Latent Diffusion preset (configs/baselines/sld.yaml)")
+    p.add_argument("--sld_concept", type=str, default=None, help="SLD's safety concept (default: that file's sentence)")
     args = p.parse_args(argv)
     env_local_rank = int(os.environ.get("LOCAL_RANK", -1))
     if env_local_rank != -1 and env_local_rank != args.local_rank:

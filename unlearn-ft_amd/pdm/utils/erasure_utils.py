@@ -88,9 +88,11 @@ def result_root(result_dir, seed, res_path):
 
 
 def images_dir(args):
-    """<root>/<model>/<target>/<baseline>/benchmarking/concept_erase/<run_ckpt>/concept_erase"""
+    """<root>/<model>/<target>/<baseline>/benchmarking/concept_erase/<run_ckpt>/concept_erase; with --sld_type the baseline
+    component is <baseline>_SLD_<type>, so an SLD run never shares a directory with a plain one."""
+    from .sld import with_suffix
     return os.path.join(result_root(args.result_dir, args.seed, args.res_path), model_component(args.model_id), args.target,
-                        args.baseline, "benchmarking", "concept_erase", run_ckpt(args.ckpt_name, args.original_ckpt),
+                        with_suffix(args.baseline, getattr(args, "sld_type", None)), "benchmarking", "concept_erase", run_ckpt(args.ckpt_name, args.original_ckpt),
                         "concept_erase")
 
 
@@ -220,10 +222,11 @@ def load_pipelines(config, args, device):
 
 
 @torch.no_grad()
-def generate(prompts, directory, original, erased, seed, resolution, steps):
+def generate(prompts, directory, original, erased, seed, resolution, steps, sld=None):
     """original_{i}.jpg / removal_{i}.jpg for every prompt (artist_erasure.py:99-115): the initial latents are drawn once per
     prompt from Generator(device).manual_seed(seed) and the text encoder runs once; both pipelines get the same `latents` and
-    embeddings.  uint8 as diffusers' numpy_to_pil (rounded), JPEG by Pillow's default save."""
+    embeddings.  uint8 as diffusers' numpy_to_pil (rounded), JPEG by Pillow's default save.  sld: generate_samples' Safe
+    Latent Diffusion keywords (pdm/utils/sld.py sampling_kwargs) for the removal images; the concept is encoded once."""
     from PIL import Image
     dev = original.device
     f = original.vae_scale_factor
@@ -234,8 +237,13 @@ def generate(prompts, directory, original, erased, seed, resolution, steps):
         gen = torch.Generator(device=dev).manual_seed(int(seed))
         latents.append(torch.randn((1, C, resolution // f, resolution // f), device=dev, dtype=torch.float32, generator=gen))
         embeds.append(original.text_encoder(original._tokenize([prompt]))[0])
+    safe = {}
+    if sld is not None:
+        safe = {k: v for k, v in sld.items() if k != "safety_concept"}
+        safe["safety_concept_embeds"] = erased.text_encoder(erased._tokenize([sld["safety_concept"]]))[0]
     for name, pipe in (("original", original), ("removal", erased)):
         for i in range(len(prompts)):
             img = pipe(prompt_embeds=embeds[i], negative_prompt_embeds=neg, latents=latents[i], num_inference_steps=steps,
-                       guidance_scale=GUIDANCE, height=resolution, width=resolution, output_type="u8_round").images[0]
+                       guidance_scale=GUIDANCE, height=resolution, width=resolution, output_type="u8_round",
+                       **(safe if name == "removal" else {})).images[0]
             Image.fromarray(img).save(os.path.join(directory, f"{name}_{i}.jpg"))

@@ -30,6 +30,9 @@ eval_artish.sh with `--baseline pdm`): did the bilevel fine-tuning erase the art
   `ckpt_name or original_ckpt` (the reference indexes split('/') and so needs the trailing slash); <p> is the basename of
   the normalised ckpt_name without `.pt`; the reference's own root is the placeholder `path/to/concept_prune/results`.
   --model_id defaults to SD-2.1 (what eval_artish.sh passes), not the reference's SD-1.4.
+* --sld_type Weak|Medium|Strong|Max [--sld_concept TEXT, default --target]: the removal images are sampled with Safe Latent
+  Diffusion (configs/baselines/sld.yaml, pdm/utils/sld.py) on whatever model --baseline selects; the original images are not.
+  The <baseline> component of the result path becomes <baseline>_SLD_<type>.
 """
 import argparse
 import logging
@@ -40,6 +43,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspa
 
 from pdm.utils import erasure_utils as E
 from pdm.utils.load_models import cuda_device, inference_config
+from pdm.utils.sld import sampling_kwargs
 
 
 def parse_args(argv=None):
@@ -65,6 +69,8 @@ def parse_args(argv=None):
     parser.add_argument('--mixed_precision', type=str, default=None, choices=["no", "bf16"])
     parser.add_argument('--tiny', action="store_true", help="tiny U-Net topology (tests)")
     parser.add_argument('--batch_size', type=int, default=64, help="scoring batch")
+    parser.add_argument('--sld_type', type=str, default=None, help="sample the removal images with this SLD preset")
+    parser.add_argument('--sld_concept', type=str, default=None, help="SLD's safety concept (default: --target)")
     return parser.parse_args(argv)
 
 
@@ -75,6 +81,9 @@ def main(argv=None):
     if args.target is None or args.baseline is None:
         raise ValueError("--target and --baseline are required")
     E.check_baseline(args.baseline, args.ckpt_name)
+    sld = None
+    if args.sld_type is not None:
+        sld = sampling_kwargs(args.sld_type, args.sld_concept if args.sld_concept is not None else args.target)
     if args.hook_module != "unet":
         raise NotImplementedError(f"--hook_module {args.hook_module}: only `unet` is built")
     if args.ckpt_name is None and args.original_ckpt is None:
@@ -93,7 +102,7 @@ def main(argv=None):
         config = inference_config(args.base_config_path, args.model_id, args.tiny, args.mixed_precision)
         original, erased = E.load_pipelines(config, args, device)
         E.generate(prompts, directory, original, erased, args.seed, E.image_resolution(args.model_id, args.image_resolution),
-                   args.num_inference_steps)
+                   args.num_inference_steps, sld=sld)
         del original, erased
 
     print("Calculating CLIP scores for the images")

@@ -23,6 +23,9 @@ caption row of the validation split, sampled by a fine-tuned student, for FID / 
   (pdm/utils/erasure_utils.py load_erasure_checkpoint: 'esd' in the path = ESD's nested {module: {weight, bias}} form,
   non-strict; otherwise a full state dict, strict).  The images then go to the reference's directory,
   <finetuning_ckpt_dir>/<path with '/' and '.' replaced by '_'>/<data.dataset_name>_fid_images/.
+* --sld_type Weak|Medium|Strong|Max [--sld_concept TEXT, default the safety sentence of configs/baselines/sld.yaml]: the
+  images are sampled with Safe Latent Diffusion on the selected checkpoint; the image directory's name gets `_SLD_<type>`
+  appended.
 * Ranks come from RANK / WORLD_SIZE / LOCAL_RANK; nothing collective runs on the GPU (a gloo barrier at the end), so
   several ranks may share one device.
 """
@@ -40,6 +43,7 @@ from pdm.utils.arg_utils import parse_args
 from pdm.utils.config import load_config
 from pdm.utils.erasure_utils import erasure_dir_name, load_erasure_checkpoint
 from pdm.utils.load_models import FrozenModels, cuda_device
+from pdm.utils.sld import sampling_kwargs, with_suffix
 
 logger = logging.getLogger("pdm.generate_fid_images")
 GUIDANCE = 7.5
@@ -62,9 +66,12 @@ def image_file_name(image):
 
 def output_dir(config):
     name = config.get_path("data.dataset_name")
+    sld_type = config.get("sld_type")
     if config.get("erasure_ckpt_path") is not None:
-        return os.path.join(config.finetuning_ckpt_dir, erasure_dir_name(config.erasure_ckpt_path), f"{name}_fid_images")
-    return os.path.join(config.finetuning_ckpt_dir, f"{name}_fid_images_{config.get_path('training.num_inference_steps', 50)}")
+        return os.path.join(config.finetuning_ckpt_dir, erasure_dir_name(config.erasure_ckpt_path),
+                            with_suffix(f"{name}_fid_images", sld_type))
+    return os.path.join(config.finetuning_ckpt_dir,
+                        with_suffix(f"{name}_fid_images_{config.get_path('training.num_inference_steps', 50)}", sld_type))
 
 
 def validation_rows(config):
@@ -105,6 +112,10 @@ def main():
     if config.get("erasure_ckpt_path") is not None:
         load_erasure_checkpoint(unet, config.erasure_ckpt_path)
     pipe = models.pipeline(unet)
+    sld = {}
+    if config.get("sld_type") is not None:
+        sld = sampling_kwargs(config.sld_type, config.get("sld_concept"))
+        sld["safety_concept_embeds"] = pipe.text_encoder(pipe._tokenize([sld.pop("safety_concept")]))[0]
     steps = int(config.get_path("training.num_inference_steps", 50))
     R = int(config.get("image_resolution") or 512)
     bs = int(config.get_path("data.dataloader.image_generation_batch_size", 1) or 1)
@@ -113,7 +124,7 @@ def main():
     for rows in rank_batches(len(captions), bs * world, world, rank):
         gen = None if seed is None else torch.Generator(device=device).manual_seed(int(seed))
         imgs = pipe(prompt=[captions[i] for i in rows], num_inference_steps=steps, guidance_scale=GUIDANCE, generator=gen,
-                    output_type="u8", height=R, width=R).images
+                    output_type="u8", height=R, width=R, **sld).images
         for i, img in zip(rows, imgs):
             np.save(os.path.join(out, image_file_name(images[i])), img)
     if dist.is_initialized():
