@@ -20,7 +20,9 @@ least 4 cells per group: dx of a group of n cells has n - 2 degrees of freedom, 
 
 Comparisons are per (image, group) block - max |got - ref| <= tol * max |ref| over that block - so that a group of small scale
 cannot hide behind a large one; dgamma / dbeta per group.  Each comparison prints a GN_PARITY line before it asserts
-(profiles/groupnorm_parity.txt is a collected run).
+(profiles/groupnorm_parity.txt is a collected run).  GN_DIGEST lines print the sha256 of y (its whole buffer), stats, dx (whole
+buffer) and the single-slice dgamma / dbeta: two builds of the library compute the same bits if their runs print the same lines
+(profiles/gn_refactor_digest.txt).
 
 Bit-reproducibility: y, stats and dx are plain stores in a fixed order and are compared bit for bit between two runs.
 dgamma / dbeta come out of the second stage (launch_reduce_partials -> reduce_partials_kernel), which splits the nblk slabs of
@@ -32,7 +34,7 @@ import math
 import pytest
 import torch
 
-from test_kernels_gpu import DT, TOL, close  # noqa: F401  (close: the project's whole-tensor check, used for the slab form)
+from test_kernels_gpu import DT, TOL, close, digest  # noqa: F401  (close: the project's whole-tensor check, used for the slab form)
 
 NT = 256
 V = {"bf16": 8, "f32": 4}
@@ -295,6 +297,8 @@ def _run_case(dev, dn, Cc, B, HW, silu):
         return ybuf, y, stats
 
     ybuf, y, stats = fwd(gamma, beta)
+    print(f"GN_DIGEST {dn} {case} ybuf {digest(ybuf)}")
+    print(f"GN_DIGEST {dn} {case} stats {digest(stats)}")
     _check_stats(dn, case, stats, mean, var, rstd)
     _block_check("y", dn, case, y[..., :cr].reshape(B, HW, G, gs), ref_y, TOL[dn], (1, 3))
     assert bool((y[..., cr:] == 0).all()), case + ": padding channels of y"
@@ -331,6 +335,10 @@ def _run_case(dev, dn, Cc, B, HW, silu):
         for with_add in (False, True):
             what = f"{case} acc={int(acc)} add={int(with_add)}"
             dxbuf, dx, dg, db = bwd(acc, with_add)
+            print(f"GN_DIGEST {dn} {what} dxbuf {digest(dxbuf)}")
+            if _slices(nblk) == 1:
+                print(f"GN_DIGEST {dn} {what} dgamma {digest(dg)}")
+                print(f"GN_DIGEST {dn} {what} dbeta {digest(db)}")
             extra = (base.double() if acc else 0.0) + (add.double() if with_add else 0.0)
             ref = ref_dx + (extra[..., :cr].reshape(B, HW, G, gs) if acc or with_add else 0.0)
             _block_check("dx", dn, what, dx[..., :cr].reshape(B, HW, G, gs), ref, 2 * TOL[dn], (1, 3))

@@ -2,6 +2,7 @@
 statement of the same op on identical inputs.  Tolerances: fp32 path 2e-4 of the output scale (MFMA fp32 is an exact
 fmaf chain; only summation order differs); bf16 path 2e-2 of the output scale against fp32 math on the bf16-rounded
 inputs (bf16 storage of outputs/intermediates, fp32 accumulation)."""
+import hashlib
 import math
 import os
 
@@ -29,6 +30,12 @@ def close(got, ref, tol, what=""):
 
 def rnd(shape, dev, dtype, scale=1.0):
     return (torch.randn(*shape, device=dev) * scale).to(dtype)
+
+
+def digest(t):
+    """sha256 of a tensor's bytes, for the printed GN_DIGEST lines: two builds of the library are compared bit for bit by comparing
+    the lines of their runs (profiles/gn_refactor_digest.txt)"""
+    return hashlib.sha256(t.detach().contiguous().reshape(-1).view(torch.uint8).cpu().numpy().tobytes()).hexdigest()
 
 
 def conv_w_pack(w):   # [Co,Ci,3,3] -> [Co, 9*Ci]
@@ -1502,6 +1509,8 @@ def test_gemm_groupnorm_statistics_epilogue(dev, force_cfg, cand):
         st0, st1 = torch.zeros(Bn, G, 2, device=dev), torch.zeros(Bn, G, 2, device=dev)
         k.groupnorm_fwd(y, z0, gamma, beta, st0, k.groupnorm_ws(dev, Bn, G), Bn, rows, Co, Co, Co, G, gs, 1e-5, True)
         k.groupnorm_apply_colstat(y, z1, gamma, beta, st1, acc, 0, Bn, rows, Co, Co, Co, G, gs, 1e-5, True)
+        print(f"GN_DIGEST colstat cand={cand} conv B{Bn} {Hs}x{Hs} {Ci}->{Co} z1 {digest(z1)}")
+        print(f"GN_DIGEST colstat cand={cand} conv B{Bn} {Hs}x{Hs} {Ci}->{Co} st1 {digest(st1)}")
         close(st1, st0, 1e-4, "statistics from the epilogue vs the statistics pass")
         close(z1, z0, 1e-2, "groupnorm from epilogue statistics")
     # split-K producers: the statistics leave with the finish pass (pdmk_splitk_finish_colstat), slabs and ragged columns
@@ -1546,6 +1555,8 @@ def test_gemm_groupnorm_statistics_epilogue(dev, force_cfg, cand):
             k.gemm(a, w, y if R_ is res else y2, Bn * rows, N, K, K, K, N, R=R_, ldr=N, rows_per_b=rows, colstat=(acc1, 0))
         assert not torch.isfinite(y[rows + 5, 9]) and torch.isfinite(y2).all()
         k.groupnorm_apply_colstat(y, z, gamma, beta, st, acc1, 0, Bn, rows, N, N, N, G, gs, 1e-5, False)
+        print(f"GN_DIGEST colstat cand={cand} poison={poison} z {digest(z)}")
+        print(f"GN_DIGEST colstat cand={cand} poison={poison} st {digest(st)}")
         bad = ~torch.isfinite(st).all(dim=2)
         want = torch.zeros(Bn, G, dtype=torch.bool, device=dev)
         want[1, 4] = True

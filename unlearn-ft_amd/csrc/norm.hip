@@ -1,6 +1,9 @@
 // GroupNorm(+SiLU) and LayerNorm, forward and backward, NHWC / token-major, HBM-bandwidth kernels.
 // All loads/stores are 16-byte chunks along the channel dim (rows are read fully coalesced); statistics are fp32
 // per thread, fp32 LDS atomics per block, then double atomics across blocks so that E[x^2]-mean^2 is formed in double.
+#include <initializer_list>
+#include <type_traits>
+
 #include "common.h"
 #include "vec.h"
 
@@ -80,79 +83,171 @@ __host__ __device__ inline GnMap2 gn_map2(int nchunks) {
 constexpr int GN_MAXC = MAXS * NT * 8;   // channel capacity of the LDS reduction image (bf16 chunks)
 constexpr int GN_MAXBLK = 64;            // stats blocks per image
 
-template <typename T, int UNR, int SLOTS>
-__global__ __launch_bounds__(NT) void gn_stats_kernel(const T* __restrict__ x, float* __restrict__ part, int HW, int C,
-                                                      int ldx, int G, int gs, int rows_per_blk) {
-    constexpr int V = Vec<T>::N;
-    const int nchunks = C / V;
-    const GnMap2 mp = gn_map2(nchunks);
-    const int tid = threadIdx.x, cb = tid % mp.tpr, ro = tid / mp.tpr;
-    const bool active = ro < mp.rif;
-    const int b = blockIdx.y;
-    const int r0 = blockIdx.x * rows_per_blk, r1 = min(HW, r0 + rows_per_blk);
-    float s[SLOTS][V], q[SLOTS][V];
+// One thread's place in the map above, and the shape it was built from.
+struct GnThread {
+    int C, HW, nchunks, cr;   // cr = G * gs: the normalised channels (channels from cr on are padding)
+    GnMap2 mp;
+    int cb, ro, b, r0, r1;
+    bool active;              // ro < rif (a tpr that does not divide 256 leaves threads over)
+    __device__ __forceinline__ int chunk(int sl) const { return cb + mp.tpr * sl; }
+    __device__ __forceinline__ long row(int rr) const { return (long)b * HW + rr; }
+};
+template <int V>
+__device__ __forceinline__ GnThread gn_thread(int C, int HW, int rows_per_blk, int G, int gs) {
+    GnThread t;
+    t.C = C, t.HW = HW, t.nchunks = C / V;
+    t.mp = gn_map2(t.nchunks);
+    const int tid = threadIdx.x;
+    t.cb = tid % t.mp.tpr, t.ro = tid / t.mp.tpr;
+    t.b = blockIdx.y;
+    t.r0 = blockIdx.x * rows_per_blk, t.r1 = min(HW, t.r0 + rows_per_blk);
+    t.cr = G * gs;
+    t.active = t.ro < t.mp.rif;
+    return t;
+}
+__device__ __forceinline__ bool gn_aligned16(const float* gamma, const float* beta) {
+    return ((reinterpret_cast<uintptr_t>(gamma) | reinterpret_cast<uintptr_t>(beta)) & 15) == 0;
+}
+
+// gamma / beta of chunk slot sl: 16-byte loads where the whole chunk lies inside the normalised channels and both pointers are
+// 16-byte aligned (vec_gb), element by element (0 for padding channels and for chunks this thread does not own) otherwise
+template <int V>
+__device__ __forceinline__ void gn_load_gb(const GnThread& t, int sl, const float* gamma, const float* beta, bool vec_gb,
+                                           float* gm, float* bt) {
+    const int c = t.chunk(sl);
+    if (t.active && c < t.nchunks && c * V + V <= t.cr && vec_gb) {
 #pragma unroll
-    for (int sl = 0; sl < SLOTS; ++sl)
+        for (int e = 0; e < V; e += 4) {
+            const float4 g4 = *reinterpret_cast<const float4*>(gamma + c * V + e), b4 = *reinterpret_cast<const float4*>(beta + c * V + e);
+            gm[e] = g4.x; gm[e + 1] = g4.y; gm[e + 2] = g4.z; gm[e + 3] = g4.w;
+            bt[e] = b4.x; bt[e + 1] = b4.y; bt[e + 2] = b4.z; bt[e + 3] = b4.w;
+        }
+    } else {
 #pragma unroll
-        for (int e = 0; e < V; ++e) s[sl][e] = q[sl][e] = 0.f;
-    if (active) {
-        for (int r = r0 + ro; r < r1; r += mp.rif * UNR) {
+        for (int e = 0; e < V; ++e) {
+            const int ch = c * V + e;
+            const bool ok = t.active && c < t.nchunks && ch < t.cr;
+            gm[e] = ok ? gamma[ch] : 0.f;
+            bt[e] = ok ? beta[ch] : 0.f;
+        }
+    }
+}
+
+// The row sweeps of one thread over NSRC tensors that are streamed in step (x, or x and dy): a register ping-pong, pre -> cur.
+// preload(sl) issues slot sl's first sweep; a kernel calls it next to gn_load_gb, in front of everything that waits for the
+// statistics (gn_apply_kernel says why).  run() then hands every valid (slot, chunk, row, raw 16-byte values of that cell) to
+// `body`, with the next sweep's loads issued before this sweep's arithmetic.  Only active threads call run().
+template <typename T, int UNR, int SLOTS, int NSRC>
+struct GnSweep {
+    typedef typename Vec<T>::raw Raw;
+    static constexpr int V = Vec<T>::N;
+    const T* src[NSRC];
+    int ld[NSRC];
+    Raw pre[SLOTS][UNR][NSRC];
+    __device__ __forceinline__ GnSweep(const T* s0, int ld0, const T* s1 = nullptr, int ld1 = 0) {
+        src[0] = s0, ld[0] = ld0;
+        if (NSRC > 1) src[NSRC - 1] = s1, ld[NSRC - 1] = ld1;
+    }
+    __device__ __forceinline__ void load(const GnThread& t, int sl, int u, int c, int rr) {
+#pragma unroll
+        for (int k = 0; k < NSRC; ++k) pre[sl][u][k] = Vec<T>::load_raw(src[k] + t.row(rr) * ld[k] + c * V);
+    }
+    __device__ __forceinline__ void preload(const GnThread& t, int sl) {
+        const int c = t.chunk(sl);
+#pragma unroll
+        for (int u = 0; u < UNR; ++u) {
+            const int rr = t.r0 + t.ro + u * t.mp.rif;
+            if (t.active && c < t.nchunks && rr < t.r1) load(t, sl, u, c, rr);
+        }
+    }
+    template <typename F>
+    __device__ __forceinline__ void run(const GnThread& t, F&& body) {
+        const int step = t.mp.rif * UNR;
+        for (int r = t.r0 + t.ro; r < t.r1; r += step) {
+            Raw cur[SLOTS][UNR][NSRC];
 #pragma unroll
             for (int sl = 0; sl < SLOTS; ++sl) {
-                const int c = cb + mp.tpr * sl;
-                if (c < nchunks) {
-                    float f[UNR][V];
+                const int c = t.chunk(sl);
+#pragma unroll
+                for (int u = 0; u < UNR; ++u) {
+#pragma unroll
+                    for (int k = 0; k < NSRC; ++k) cur[sl][u][k] = pre[sl][u][k];
+                    const int rn = r + step + u * t.mp.rif;           // the next sweep's loads go out before this sweep's arithmetic
+                    if (c < t.nchunks && rn < t.r1) load(t, sl, u, c, rn);
+                }
+            }
+#pragma unroll
+            for (int sl = 0; sl < SLOTS; ++sl) {
+                const int c = t.chunk(sl);
+                if (c < t.nchunks) {
 #pragma unroll
                     for (int u = 0; u < UNR; ++u) {
-                        const int rr = r + u * mp.rif;
-                        if (rr < r1) Vec<T>::load(x + ((long)b * HW + rr) * ldx + c * V, f[u]);
-                        else {
-#pragma unroll
-                            for (int e = 0; e < V; ++e) f[u][e] = 0.f;
-                        }
+                        const int rr = r + u * t.mp.rif;
+                        if (rr < t.r1) body(sl, c, rr, cur[sl][u]);
                     }
-#pragma unroll
-                    for (int u = 0; u < UNR; ++u)
-#pragma unroll
-                        for (int e = 0; e < V; ++e) { s[sl][e] += f[u][e]; q[sl][e] += f[u][e] * f[u][e]; }
                 }
             }
         }
     }
-    __shared__ float red[2][GN_MAXC / 8 * V];        // [rif][C] images of the per-thread sums
-    if (active) {
+};
+
+// Per-group values expanded to the V channels of chunk slot sl: one division per chunk; the group index then steps with the
+// channel.  body(e, g, ok): element e belongs to group g; ok = a normalised channel of a chunk this thread owns
+template <int V, typename F>
+__device__ __forceinline__ void gn_for_channels(const GnThread& t, int sl, int gs, F&& body) {
+    const int c = t.chunk(sl);
+    int g = (c * V) / gs, rem = c * V - g * gs;
 #pragma unroll
-        for (int sl = 0; sl < SLOTS; ++sl) {
-            const int c = cb + mp.tpr * sl;
-            if (c < nchunks) {
+    for (int e = 0; e < V; ++e) {
+        body(e, g, c < t.nchunks && c * V + e < t.cr);
+        if (++rem == gs) { rem = 0; ++g; }
+    }
+}
+
+// the per-thread sums of an active thread -> the [rif][C] LDS images red[0], red[1]
+template <int V, int SLOTS, int N>
+__device__ __forceinline__ void gn_red_store(const GnThread& t, float (&red)[2][N], const float (&s0)[SLOTS][V],
+                                             const float (&s1)[SLOTS][V]) {
+    if (!t.active) return;
 #pragma unroll
-                for (int e = 0; e < V; ++e) {
-                    red[0][ro * C + c * V + e] = s[sl][e];
-                    red[1][ro * C + c * V + e] = q[sl][e];
-                }
+    for (int sl = 0; sl < SLOTS; ++sl) {
+        const int c = t.chunk(sl);
+        if (c < t.nchunks) {
+#pragma unroll
+            for (int e = 0; e < V; ++e) {
+                red[0][t.ro * t.C + c * V + e] = s0[sl][e];
+                red[1][t.ro * t.C + c * V + e] = s1[sl][e];
             }
         }
     }
-    __syncthreads();
-    // 256 threads: (group g = tid % 64, quarter = tid / 64) -> partial over a quarter of the group's (row, channel) cells
-    const int g = tid & 63, qt = tid >> 6;
+}
+
+// 256 partials, [quarter][64], of at most 64 sums -> the sum of thread tid's four, quarters 0 + 1 and 2 + 3 first
+template <typename F>
+__device__ __forceinline__ F gn_fold4(const F* q, int tid) {
+    return (q[tid] + q[tid + 64]) + (q[tid + 128] + q[tid + 192]);
+}
+
+// 256 threads: (group g = tid % 64, quarter = tid / 64) -> partial over a quarter of group g's `cells` cells of the two images
+// (cell i of group g is red[.][at(g, i)]), the four quarters folded, group g's (sum0, sum1) stored to slab[2 * g].  The images
+// must be complete (a barrier behind their last write); they are overwritten.
+template <int N, typename At>
+__device__ __forceinline__ void gn_group_sums_store(float (&red)[2][N], int G, int cells, At&& at, float* slab) {
+    const int tid = threadIdx.x, g = tid & 63, qt = tid >> 6;
     float ps = 0.f, pq = 0.f;
-    if (g < G) {
-        const int cells = mp.rif * gs;
+    if (g < G)
         for (int i = qt; i < cells; i += 4) {
-            const int rr = i / gs, ch = g * gs + (i - rr * gs);
-            ps += red[0][rr * C + ch];
-            pq += red[1][rr * C + ch];
+            const int j = at(g, i);
+            ps += red[0][j];
+            pq += red[1][j];
         }
-    }
     __syncthreads();
     red[0][tid] = ps;
     red[1][tid] = pq;
     __syncthreads();
     if (tid < G) {
-        float* slab = part + (((long)b * gridDim.x + blockIdx.x) * G + tid) * 2;
-        slab[0] = (red[0][tid] + red[0][tid + 64]) + (red[0][tid + 128] + red[0][tid + 192]);
-        slab[1] = (red[1][tid] + red[1][tid + 64]) + (red[1][tid + 128] + red[1][tid + 192]);
+        slab[2 * tid] = gn_fold4(red[0], tid);
+        slab[2 * tid + 1] = gn_fold4(red[1], tid);
     }
 }
 
@@ -171,10 +266,52 @@ __device__ __forceinline__ void gn_sum_slabs(const float* __restrict__ part, int
     scr[1][tid] = a1;
     __syncthreads();
     if (tid < G) {
-        out0[tid] = (scr[0][tid] + scr[0][tid + 64]) + (scr[0][tid + 128] + scr[0][tid + 192]);
-        out1[tid] = (scr[1][tid] + scr[1][tid + 64]) + (scr[1][tid + 128] + scr[1][tid + 192]);
+        out0[tid] = gn_fold4(scr[0], tid);
+        out1[tid] = gn_fold4(scr[1], tid);
     }
     __syncthreads();
+}
+
+// (its row loop loads UNR rows and then consumes them, with no ping-pong, so it is written out here and is not a GnSweep)
+template <typename T, int UNR, int SLOTS>
+__global__ __launch_bounds__(NT) void gn_stats_kernel(const T* __restrict__ x, float* __restrict__ part, int HW, int C,
+                                                      int ldx, int G, int gs, int rows_per_blk) {
+    constexpr int V = Vec<T>::N;
+    const GnThread t = gn_thread<V>(C, HW, rows_per_blk, G, gs);
+    float s[SLOTS][V], q[SLOTS][V];
+#pragma unroll
+    for (int sl = 0; sl < SLOTS; ++sl)
+#pragma unroll
+        for (int e = 0; e < V; ++e) s[sl][e] = q[sl][e] = 0.f;
+    if (t.active) {
+        for (int r = t.r0 + t.ro; r < t.r1; r += t.mp.rif * UNR) {
+#pragma unroll
+            for (int sl = 0; sl < SLOTS; ++sl) {
+                const int c = t.chunk(sl);
+                if (c < t.nchunks) {
+                    float f[UNR][V];
+#pragma unroll
+                    for (int u = 0; u < UNR; ++u) {
+                        const int rr = r + u * t.mp.rif;
+                        if (rr < t.r1) Vec<T>::load(x + t.row(rr) * ldx + c * V, f[u]);
+                        else {
+#pragma unroll
+                            for (int e = 0; e < V; ++e) f[u][e] = 0.f;
+                        }
+                    }
+#pragma unroll
+                    for (int u = 0; u < UNR; ++u)
+#pragma unroll
+                        for (int e = 0; e < V; ++e) { s[sl][e] += f[u][e]; q[sl][e] += f[u][e] * f[u][e]; }
+                }
+            }
+        }
+    }
+    __shared__ float red[2][GN_MAXC / 8 * V];
+    gn_red_store<V, SLOTS>(t, red, s, q);
+    __syncthreads();
+    gn_group_sums_store(red, G, t.mp.rif * gs, [&](int g, int i) { const int rr = i / gs; return rr * C + g * gs + (i - rr * gs); },
+                        part + ((long)t.b * gridDim.x + blockIdx.x) * G * 2);
 }
 
 template <typename T, int UNR, int SLOTS>
@@ -185,21 +322,15 @@ __global__ __launch_bounds__(NT) void gn_apply_kernel(const T* __restrict__ x, T
                                                       int C, int ldx, int ldy, int G, int gs, float eps, int silu,
                                                       int rows_per_blk, int cs_ld = 0) {
     constexpr int V = Vec<T>::N;
-    typedef typename Vec<T>::raw Raw;
-    const int nchunks = C / V;
-    const GnMap2 mp = gn_map2(nchunks);
-    const int tid = threadIdx.x, cb = tid % mp.tpr, ro = tid / mp.tpr;
-    const int b = blockIdx.y;
-    const int r0 = blockIdx.x * rows_per_blk, r1 = min(HW, r0 + rows_per_blk);
-    const int cr = G * gs;
+    const GnThread t = gn_thread<V>(C, HW, rows_per_blk, G, gs);
+    const int tid = threadIdx.x, b = t.b;
     __shared__ double scr[2][NT], d0[64], d1[64];
     __shared__ float lm[64], lr[64];
     // Everything that does not depend on the statistics is issued FIRST - this thread's gamma / beta chunks and its first sweep of
     // rows - so that those loads are in flight while the block works out mean / rstd (a chain of an L2 read, an LDS reduction and
     // a double-precision sqrt: 3-4 us per block, which every block of the grid pays at the same time; with the loads behind it the
     // kernel streamed at 2.5 TB/s where a plain copy of the same tensor reaches 6.4, tools/gn_bench.py).
-    const bool active = ro < mp.rif;
-    const bool vec_gb = ((reinterpret_cast<uintptr_t>(gamma) | reinterpret_cast<uintptr_t>(beta)) & 15) == 0;
+    const bool vec_gb = gn_aligned16(gamma, beta);
     // (the statistics' own loads are the very first: loads return in issue order, so behind the row sweep they would wait for it)
     long long l0 = 0, h0 = 0, l1 = 0, h1 = 0;
     int cs_bad = 0;
@@ -220,31 +351,11 @@ __global__ __launch_bounds__(NT) void gn_apply_kernel(const T* __restrict__ x, T
         }
     }
     float gmv[SLOTS][V], btv[SLOTS][V];
-    Raw pre[SLOTS][UNR];
+    GnSweep<T, UNR, SLOTS, 1> sweep(x, ldx);
 #pragma unroll
     for (int sl = 0; sl < SLOTS; ++sl) {
-        const int c = cb + mp.tpr * sl;
-        if (active && c < nchunks && c * V + V <= cr && vec_gb) {       // whole chunk inside the normalised channels: 16-byte loads
-#pragma unroll
-            for (int e = 0; e < V; e += 4) {
-                const float4 g4 = *reinterpret_cast<const float4*>(gamma + c * V + e), b4 = *reinterpret_cast<const float4*>(beta + c * V + e);
-                gmv[sl][e] = g4.x; gmv[sl][e + 1] = g4.y; gmv[sl][e + 2] = g4.z; gmv[sl][e + 3] = g4.w;
-                btv[sl][e] = b4.x; btv[sl][e + 1] = b4.y; btv[sl][e + 2] = b4.z; btv[sl][e + 3] = b4.w;
-            }
-        } else {
-#pragma unroll
-            for (int e = 0; e < V; ++e) {
-                const int ch = c * V + e;
-                const bool ok = active && c < nchunks && ch < cr;
-                gmv[sl][e] = ok ? gamma[ch] : 0.f;
-                btv[sl][e] = ok ? beta[ch] : 0.f;
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < UNR; ++u) {
-            const int rr = r0 + ro + u * mp.rif;
-            if (active && c < nchunks && rr < r1) pre[sl][u] = Vec<T>::load_raw(x + ((long)b * HW + rr) * ldx + c * V);
-        }
+        gn_load_gb<V>(t, sl, gamma, beta, vec_gb, gmv[sl], btv[sl]);
+        sweep.preload(t, sl);
     }
     if (nblk < 0) {
         const int g = tid >> 2, pth = tid & 3;
@@ -288,58 +399,28 @@ __global__ __launch_bounds__(NT) void gn_apply_kernel(const T* __restrict__ x, T
         }
     }
     __syncthreads();
-    if (!active) return;
+    if (!t.active) return;
     float sc[SLOTS][V], sh[SLOTS][V];   // y = x*sc + sh  (pad channels: 0)
 #pragma unroll
-    for (int sl = 0; sl < SLOTS; ++sl) {
-        const int c = cb + mp.tpr * sl;
-        int g = (c * V) / gs, rem = c * V - g * gs;          // one division per chunk; the group index then steps with the channel
-#pragma unroll
-        for (int e = 0; e < V; ++e) {
-            const int ch = c * V + e;
+    for (int sl = 0; sl < SLOTS; ++sl)
+        gn_for_channels<V>(t, sl, gs, [&](int e, int g, bool ok) {
             sc[sl][e] = sh[sl][e] = 0.f;
-            if (c < nchunks && ch < cr) {
+            if (ok) {
                 const float a = lr[g] * gmv[sl][e];
                 sc[sl][e] = a;
                 sh[sl][e] = btv[sl][e] - lm[g] * a;
             }
-            if (++rem == gs) { rem = 0; ++g; }
+        });
+    sweep.run(t, [&](int sl, int c, int rr, const auto& raw) {
+        float f[V];
+        Vec<T>::unpack(raw[0], f);
+#pragma unroll
+        for (int e = 0; e < V; ++e) {
+            const float z = f[e] * sc[sl][e] + sh[sl][e];
+            f[e] = silu ? silu_f(z) : z;
         }
-    }
-    const int step = mp.rif * UNR;
-    for (int r = r0 + ro; r < r1; r += step) {
-        Raw cur[SLOTS][UNR];
-#pragma unroll
-        for (int sl = 0; sl < SLOTS; ++sl) {
-            const int c = cb + mp.tpr * sl;
-#pragma unroll
-            for (int u = 0; u < UNR; ++u) {
-                cur[sl][u] = pre[sl][u];
-                const int rn = r + step + u * mp.rif;             // the next sweep's loads go out before this sweep's arithmetic
-                if (c < nchunks && rn < r1) pre[sl][u] = Vec<T>::load_raw(x + ((long)b * HW + rn) * ldx + c * V);
-            }
-        }
-#pragma unroll
-        for (int sl = 0; sl < SLOTS; ++sl) {
-            const int c = cb + mp.tpr * sl;
-            if (c < nchunks) {
-#pragma unroll
-                for (int u = 0; u < UNR; ++u) {
-                    const int rr = r + u * mp.rif;
-                    if (rr < r1) {
-                        float f[V];
-                        Vec<T>::unpack(cur[sl][u], f);
-#pragma unroll
-                        for (int e = 0; e < V; ++e) {
-                            const float z = f[e] * sc[sl][e] + sh[sl][e];
-                            f[e] = silu ? silu_f(z) : z;
-                        }
-                        Vec<T>::store(y + ((long)b * HW + rr) * ldy + c * V, f);
-                    }
-                }
-            }
-        }
-    }
+        Vec<T>::store(y + t.row(rr) * ldy + c * V, f);
+    });
 }
 
 // backward pass 1: per (b,g) s1 = sum gamma*dz, s2 = sum gamma*dz*xhat (slab `gpart`); per channel dgamma += sum
@@ -353,47 +434,18 @@ __global__ __launch_bounds__(NT) void gn_bwd_stats_kernel(const T* __restrict__ 
                                                           int C, int ldx, int lddy, int G, int gs, int silu,
                                                           int rows_per_blk) {
     constexpr int V = Vec<T>::N;
-    const int nchunks = C / V;
-    const GnMap2 mp = gn_map2(nchunks);
-    const int tid = threadIdx.x, cb = tid % mp.tpr, ro = tid / mp.tpr;
-    const bool active = ro < mp.rif;
-    const int b = blockIdx.y;
-    const int r0 = blockIdx.x * rows_per_blk, r1 = min(HW, r0 + rows_per_blk);
-    const int cr = G * gs;
-    typedef typename Vec<T>::raw Raw;
+    const GnThread t = gn_thread<V>(C, HW, rows_per_blk, G, gs);
+    const int tid = threadIdx.x, b = t.b, cr = t.cr;
     float a1[SLOTS][V], a2[SLOTS][V], mean[SLOTS][V], rstd[SLOTS][V], gm[SLOTS][V], bt[SLOTS][V];
     // as gn_apply_kernel: 16-byte gamma / beta loads and the first sweep of rows go out first, (mean, rstd) through LDS (one
     // coalesced load per group instead of two scalar loads and a division per channel), then a register ping-pong over the sweeps
     __shared__ float sm[64], sr[64];
-    const bool vec_gb = ((reinterpret_cast<uintptr_t>(gamma) | reinterpret_cast<uintptr_t>(beta)) & 15) == 0;
-    Raw px[SLOTS][UNR], pd[SLOTS][UNR];
+    const bool vec_gb = gn_aligned16(gamma, beta);
+    GnSweep<T, UNR, SLOTS, 2> sweep(x, ldx, dy, lddy);
 #pragma unroll
     for (int sl = 0; sl < SLOTS; ++sl) {
-        const int c = cb + mp.tpr * sl;
-        if (active && c < nchunks && c * V + V <= cr && vec_gb) {
-#pragma unroll
-            for (int e = 0; e < V; e += 4) {
-                const float4 g4 = *reinterpret_cast<const float4*>(gamma + c * V + e), b4 = *reinterpret_cast<const float4*>(beta + c * V + e);
-                gm[sl][e] = g4.x; gm[sl][e + 1] = g4.y; gm[sl][e + 2] = g4.z; gm[sl][e + 3] = g4.w;
-                bt[sl][e] = b4.x; bt[sl][e + 1] = b4.y; bt[sl][e + 2] = b4.z; bt[sl][e + 3] = b4.w;
-            }
-        } else {
-#pragma unroll
-            for (int e = 0; e < V; ++e) {
-                const int ch = c * V + e;
-                const bool ok = active && c < nchunks && ch < cr;
-                gm[sl][e] = ok ? gamma[ch] : 0.f;
-                bt[sl][e] = ok ? beta[ch] : 0.f;
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < UNR; ++u) {
-            const int rr = r0 + ro + u * mp.rif;
-            if (active && c < nchunks && rr < r1) {
-                px[sl][u] = Vec<T>::load_raw(x + ((long)b * HW + rr) * ldx + c * V);
-                pd[sl][u] = Vec<T>::load_raw(dy + ((long)b * HW + rr) * lddy + c * V);
-            }
-        }
+        gn_load_gb<V>(t, sl, gamma, beta, vec_gb, gm[sl], bt[sl]);
+        sweep.preload(t, sl);
     }
     if (tid < G) {
         sm[tid] = stats[((long)b * G + tid) * 2];
@@ -401,86 +453,39 @@ __global__ __launch_bounds__(NT) void gn_bwd_stats_kernel(const T* __restrict__ 
     }
     __syncthreads();
 #pragma unroll
-    for (int sl = 0; sl < SLOTS; ++sl) {
-        const int c = cb + mp.tpr * sl;
-        int g = (c * V) / gs, rem = c * V - g * gs;
-#pragma unroll
-        for (int e = 0; e < V; ++e) {
-            const int ch = c * V + e;
+    for (int sl = 0; sl < SLOTS; ++sl)
+        gn_for_channels<V>(t, sl, gs, [&](int e, int g, bool ok) {
             a1[sl][e] = a2[sl][e] = 0.f;
             mean[sl][e] = rstd[sl][e] = 0.f;
-            if (c < nchunks && ch < cr) {
+            if (ok) {
                 mean[sl][e] = sm[g];
                 rstd[sl][e] = sr[g];
             } else {
                 gm[sl][e] = bt[sl][e] = 0.f;
             }
-            if (++rem == gs) { rem = 0; ++g; }
-        }
-    }
-    if (active) {
-        const int step = mp.rif * UNR;
-        for (int r = r0 + ro; r < r1; r += step) {
-            Raw cx[SLOTS][UNR], cd[SLOTS][UNR];
+        });
+    if (t.active)
+        sweep.run(t, [&](int sl, int c, int rr, const auto& raw) {
+            float f[V], d[V];
+            Vec<T>::unpack(raw[0], f);
+            Vec<T>::unpack(raw[1], d);
 #pragma unroll
-            for (int sl = 0; sl < SLOTS; ++sl) {
-                const int c = cb + mp.tpr * sl;
-#pragma unroll
-                for (int u = 0; u < UNR; ++u) {
-                    cx[sl][u] = px[sl][u];
-                    cd[sl][u] = pd[sl][u];
-                    const int rn = r + step + u * mp.rif;
-                    if (c < nchunks && rn < r1) {
-                        px[sl][u] = Vec<T>::load_raw(x + ((long)b * HW + rn) * ldx + c * V);
-                        pd[sl][u] = Vec<T>::load_raw(dy + ((long)b * HW + rn) * lddy + c * V);
-                    }
-                }
+            for (int e = 0; e < V; ++e) {
+                const float xh = (f[e] - mean[sl][e]) * rstd[sl][e];
+                float dz = d[e];
+                if (silu) dz *= silu_grad_f(xh * gm[sl][e] + bt[sl][e]);
+                a1[sl][e] += dz;
+                a2[sl][e] += dz * xh;
             }
-#pragma unroll
-            for (int sl = 0; sl < SLOTS; ++sl) {
-                const int c = cb + mp.tpr * sl;
-                if (c < nchunks) {
-#pragma unroll
-                    for (int u = 0; u < UNR; ++u) {
-                        const int rr = r + u * mp.rif;
-                        if (rr < r1) {
-                            float f[V], d[V];
-                            Vec<T>::unpack(cx[sl][u], f);
-                            Vec<T>::unpack(cd[sl][u], d);
-#pragma unroll
-                            for (int e = 0; e < V; ++e) {
-                                const float xh = (f[e] - mean[sl][e]) * rstd[sl][e];
-                                float dz = d[e];
-                                if (silu) dz *= silu_grad_f(xh * gm[sl][e] + bt[sl][e]);
-                                a1[sl][e] += dz;
-                                a2[sl][e] += dz * xh;
-                            }
-                        }
-                    }
-                }
-            }
-        }
-    }
-    __shared__ float red[2][GN_MAXC / 8 * V];        // [rif][C] images of the per-thread sums
-    if (active) {
-#pragma unroll
-        for (int sl = 0; sl < SLOTS; ++sl) {
-            const int c = cb + mp.tpr * sl;
-            if (c < nchunks) {
-#pragma unroll
-                for (int e = 0; e < V; ++e) {
-                    red[0][ro * C + c * V + e] = a1[sl][e];
-                    red[1][ro * C + c * V + e] = a2[sl][e];
-                }
-            }
-        }
-    }
+        });
+    __shared__ float red[2][GN_MAXC / 8 * V];
+    gn_red_store<V, SLOTS>(t, red, a1, a2);
     __syncthreads();
     // per-channel sums over the rows in flight -> row 0 of the image (+ the dgamma/dbeta slab of this block)
     float* slab = part + ((long)blockIdx.y * gridDim.x + blockIdx.x) * 2 * cr;                 // [dgamma | dbeta]
     for (int ch = tid; ch < cr; ch += NT) {
         float t1 = 0.f, t2 = 0.f;
-        for (int rr = 0; rr < mp.rif; ++rr) { t1 += red[0][rr * C + ch]; t2 += red[1][rr * C + ch]; }
+        for (int rr = 0; rr < t.mp.rif; ++rr) { t1 += red[0][rr * C + ch]; t2 += red[1][rr * C + ch]; }
         slab[ch] = t2;
         slab[cr + ch] = t1;
         const float gmc = gamma[ch];
@@ -488,19 +493,7 @@ __global__ __launch_bounds__(NT) void gn_bwd_stats_kernel(const T* __restrict__ 
         red[1][ch] = gmc * t2;
     }
     __syncthreads();
-    const int g = tid & 63, qt = tid >> 6;
-    float ps = 0.f, pq = 0.f;
-    if (g < G)
-        for (int i = qt; i < gs; i += 4) { ps += red[0][g * gs + i]; pq += red[1][g * gs + i]; }
-    __syncthreads();
-    red[0][tid] = ps;
-    red[1][tid] = pq;
-    __syncthreads();
-    if (tid < G) {
-        float* gs_ = gpart + (((long)b * gridDim.x + blockIdx.x) * G + tid) * 2;
-        gs_[0] = (red[0][tid] + red[0][tid + 64]) + (red[0][tid + 128] + red[0][tid + 192]);
-        gs_[1] = (red[1][tid] + red[1][tid + 64]) + (red[1][tid + 128] + red[1][tid + 192]);
-    }
+    gn_group_sums_store(red, G, gs, [&](int g, int i) { return g * gs + i; }, gpart + ((long)b * gridDim.x + blockIdx.x) * G * 2);
 }
 
 template <typename T, int UNR, int SLOTS>
@@ -513,46 +506,29 @@ __global__ __launch_bounds__(NT) void gn_bwd_apply_kernel(const T* __restrict__ 
                                                           int accumulate, int rows_per_blk, const T* __restrict__ add,
                                                           int ldadd) {
     constexpr int V = Vec<T>::N;
-    typedef typename Vec<T>::raw Raw;
-    const int nchunks = C / V;
-    const GnMap2 mp = gn_map2(nchunks);
-    const int tid = threadIdx.x, cb = tid % mp.tpr, ro = tid / mp.tpr;
-    const int b = blockIdx.y;
-    const int r0 = blockIdx.x * rows_per_blk, r1 = min(HW, r0 + rows_per_blk);
-    const int cr = G * gs;
+    const GnThread t = gn_thread<V>(C, HW, rows_per_blk, G, gs);
+    const int tid = threadIdx.x, b = t.b;
     __shared__ double scr[2][NT], d0[64], d1[64];
     __shared__ float sm[64], sr[64];
     // as gn_apply_kernel: what does not depend on the group sums goes out first (gamma / beta chunks, the (mean, rstd) pairs, the
-    // first sweep of x / dy rows), so that it is in flight while the block adds up the slabs
-    const bool active = ro < mp.rif;
-    const bool vec_gb = ((reinterpret_cast<uintptr_t>(gamma) | reinterpret_cast<uintptr_t>(beta)) & 15) == 0;
+    // first sweep of x / dy rows), so that it is in flight while the block adds up the slabs.
+    // The sweep is written out here and is not a GnSweep: through the helper the two-slot bf16 instance came out with another
+    // schedule and 0.3 - 0.6 us slower at 8 x 256 x 2560 (profiles/gn_refactor_bench.txt); written out, the two- and three-slot
+    // instances are instruction for instruction what they were before the helpers.
+    typedef typename Vec<T>::raw Raw;
+    const bool vec_gb = gn_aligned16(gamma, beta);
     float gm[SLOTS][V], bt[SLOTS][V];
     Raw px[SLOTS][UNR], pd[SLOTS][UNR];
 #pragma unroll
     for (int sl = 0; sl < SLOTS; ++sl) {
-        const int c = cb + mp.tpr * sl;
-        if (active && c < nchunks && c * V + V <= cr && vec_gb) {
-#pragma unroll
-            for (int e = 0; e < V; e += 4) {
-                const float4 g4 = *reinterpret_cast<const float4*>(gamma + c * V + e), b4 = *reinterpret_cast<const float4*>(beta + c * V + e);
-                gm[sl][e] = g4.x; gm[sl][e + 1] = g4.y; gm[sl][e + 2] = g4.z; gm[sl][e + 3] = g4.w;
-                bt[sl][e] = b4.x; bt[sl][e + 1] = b4.y; bt[sl][e + 2] = b4.z; bt[sl][e + 3] = b4.w;
-            }
-        } else {
-#pragma unroll
-            for (int e = 0; e < V; ++e) {
-                const int ch = c * V + e;
-                const bool ok = active && c < nchunks && ch < cr;
-                gm[sl][e] = ok ? gamma[ch] : 0.f;
-                bt[sl][e] = ok ? beta[ch] : 0.f;
-            }
-        }
+        gn_load_gb<V>(t, sl, gamma, beta, vec_gb, gm[sl], bt[sl]);
+        const int c = t.chunk(sl);
 #pragma unroll
         for (int u = 0; u < UNR; ++u) {
-            const int rr = r0 + ro + u * mp.rif;
-            if (active && c < nchunks && rr < r1) {
-                px[sl][u] = Vec<T>::load_raw(x + ((long)b * HW + rr) * ldx + c * V);
-                pd[sl][u] = Vec<T>::load_raw(dy + ((long)b * HW + rr) * lddy + c * V);
+            const int rr = t.r0 + t.ro + u * t.mp.rif;
+            if (t.active && c < t.nchunks && rr < t.r1) {
+                px[sl][u] = Vec<T>::load_raw(x + t.row(rr) * ldx + c * V);
+                pd[sl][u] = Vec<T>::load_raw(dy + t.row(rr) * lddy + c * V);
             }
         }
     }
@@ -561,56 +537,50 @@ __global__ __launch_bounds__(NT) void gn_bwd_apply_kernel(const T* __restrict__ 
         sr[tid] = stats[((long)b * G + tid) * 2 + 1];
     }
     gn_sum_slabs(gpart, b, nblk, G, d0, d1, scr);          // (ends with a barrier: sm / sr are visible too)
-    if (!active) return;
+    if (!t.active) return;
     const float invn = 1.0f / ((float)HW * (float)gs);
     float mean[SLOTS][V], rstd[SLOTS][V], c1[SLOTS][V], c2[SLOTS][V];
 #pragma unroll
-    for (int sl = 0; sl < SLOTS; ++sl) {
-        const int c = cb + mp.tpr * sl;
-        int g = (c * V) / gs, rem = c * V - g * gs;          // one division per chunk; the group index then steps with the channel
-#pragma unroll
-        for (int e = 0; e < V; ++e) {
-            const int ch = c * V + e;
+    for (int sl = 0; sl < SLOTS; ++sl)
+        gn_for_channels<V>(t, sl, gs, [&](int e, int g, bool ok) {
             mean[sl][e] = rstd[sl][e] = c1[sl][e] = c2[sl][e] = 0.f;
-            if (c < nchunks && ch < cr) {
+            if (ok) {
                 mean[sl][e] = sm[g];
                 rstd[sl][e] = sr[g];
                 c1[sl][e] = (float)d0[g] * invn;
                 c2[sl][e] = (float)d1[g] * invn;
             }
-            if (++rem == gs) { rem = 0; ++g; }
-        }
-    }
-    const int step = mp.rif * UNR;
-    for (int r = r0 + ro; r < r1; r += step) {
+        });
+    const int step = t.mp.rif * UNR;
+    for (int r = t.r0 + t.ro; r < t.r1; r += step) {
         Raw cx[SLOTS][UNR], cd[SLOTS][UNR];
 #pragma unroll
         for (int sl = 0; sl < SLOTS; ++sl) {
-            const int c = cb + mp.tpr * sl;
+            const int c = t.chunk(sl);
 #pragma unroll
             for (int u = 0; u < UNR; ++u) {
                 cx[sl][u] = px[sl][u];
                 cd[sl][u] = pd[sl][u];
-                const int rn = r + step + u * mp.rif;             // the next sweep's loads go out before this sweep's arithmetic
-                if (c < nchunks && rn < r1) {
-                    px[sl][u] = Vec<T>::load_raw(x + ((long)b * HW + rn) * ldx + c * V);
-                    pd[sl][u] = Vec<T>::load_raw(dy + ((long)b * HW + rn) * lddy + c * V);
+                const int rn = r + step + u * t.mp.rif;           // as GnSweep::run: the next sweep's loads first
+                if (c < t.nchunks && rn < t.r1) {
+                    px[sl][u] = Vec<T>::load_raw(x + t.row(rn) * ldx + c * V);
+                    pd[sl][u] = Vec<T>::load_raw(dy + t.row(rn) * lddy + c * V);
                 }
             }
         }
 #pragma unroll
         for (int sl = 0; sl < SLOTS; ++sl) {
-            const int c = cb + mp.tpr * sl;
-            if (c < nchunks) {
+            const int c = t.chunk(sl);
+            if (c < t.nchunks) {
 #pragma unroll
                 for (int u = 0; u < UNR; ++u) {
-                    const int rr = r + u * mp.rif;
-                    if (rr < r1) {
+                    const int rr = r + u * t.mp.rif;
+                    if (rr < t.r1) {
                         float f[V], d[V], o[V], a2[V];
                         Vec<T>::unpack(cx[sl][u], f);
                         Vec<T>::unpack(cd[sl][u], d);
-                        if (accumulate) Vec<T>::load(dx + ((long)b * HW + rr) * lddx + c * V, o);
-                        if (add) Vec<T>::load(add + ((long)b * HW + rr) * ldadd + c * V, a2);
+                        if (accumulate) Vec<T>::load(dx + t.row(rr) * lddx + c * V, o);
+                        if (add) Vec<T>::load(add + t.row(rr) * ldadd + c * V, a2);
 #pragma unroll
                         for (int e = 0; e < V; ++e) {
                             const float xh = (f[e] - mean[sl][e]) * rstd[sl][e];
@@ -620,7 +590,7 @@ __global__ __launch_bounds__(NT) void gn_bwd_apply_kernel(const T* __restrict__ 
                             if (add) v += a2[e];           // a second finished gradient of x (residual fan-in) folded in
                             o[e] = accumulate ? o[e] + v : v;
                         }
-                        Vec<T>::store(dx + ((long)b * HW + rr) * lddx + c * V, o);
+                        Vec<T>::store(dx + t.row(rr) * lddx + c * V, o);
                     }
                 }
             }
@@ -638,29 +608,69 @@ inline int gn_rows_per_blk(int B, int HW, int sweep, int target_blocks, int max_
     return rpb;
 }
 
+// The four launches: rows of one sweep / rif (the kernel's UNR), block target chip-wide, blocks per image at most.  The UNR
+// template arguments, the sweep given to gn_rows_per_blk and the grid all come from here.
+struct GnLaunch {
+    int unr, target_blocks, max_blk;
+};
+constexpr GnLaunch GN_FWD_STATS{8, 512, GN_MAXBLK}, GN_FWD_APPLY{4, 1024, 1 << 20}, GN_BWD_STATS{4, 512, GN_MAXBLK},
+    GN_BWD_APPLY{2, 1024, 1 << 20};
+struct GnGrid {
+    int rpb;     // rows per block
+    dim3 grid;   // (blocks per image, B)
+};
+inline GnGrid gn_grid(const GnLaunch& l, int B, int HW, int nchunks) {
+    const int rpb = gn_rows_per_blk(B, HW, gn_map2(nchunks).rif * l.unr, l.target_blocks, l.max_blk);
+    return GnGrid{rpb, dim3((HW + rpb - 1) / rpb, B)};
+}
+
+// what every launcher refuses; red_image: the kernels keep their sums in the `red` LDS image (GN_MAXC channels of bf16 chunks)
+template <int V>
+inline bool gn_shape_ok(int C, int G, int gs, std::initializer_list<int> lds, bool red_image) {
+    for (int ld : lds)
+        if (ld % V) return false;
+    return !(C % V || G > 64 || G * gs > C || C / V > MAXS * NT || (red_image && C > GN_MAXC / 8 * V));
+}
+
+// f(std::integral_constant<int, SLOTS>) for the chunk slots a thread needs
+template <typename F>
+inline void gn_dispatch_slots(int nchunks, F&& f) {
+    const int slots = (nchunks + NT - 1) / NT;
+    if (slots == 1) f(std::integral_constant<int, 1>());
+    else if (slots == 2) f(std::integral_constant<int, 2>());
+    else f(std::integral_constant<int, 3>());
+}
+
 template <typename T>
 int gn_fwd(const void* x, void* y, const float* gamma, const float* beta, float* stats, double* ws, int B, int HW,
            int C, int ldx, int ldy, int G, int gs, float eps, int silu, hipStream_t st) {
     constexpr int V = Vec<T>::N;
-    if (C % V || ldx % V || ldy % V || G > 64 || G * gs > C || C / V > MAXS * NT || C > GN_MAXC / 8 * V) return -1;
-    const GnMap2 mp = gn_map2(C / V);
+    if (!gn_shape_ok<V>(C, G, gs, {ldx, ldy}, true)) return -1;
     float* part = reinterpret_cast<float*>(ws);                     // [B][nblk][G][2] floats <= B*G*64 doubles
-    const int rpb_s = gn_rows_per_blk(B, HW, mp.rif * 8, 512, GN_MAXBLK);
-    dim3 grid_s((HW + rpb_s - 1) / rpb_s, B);
-    const int rpb = gn_rows_per_blk(B, HW, mp.rif * 4, 1024, 1 << 20);
-    dim3 grid((HW + rpb - 1) / rpb, B);
-    const int slots = (C / V + NT - 1) / NT;
-#define PDMK_GNF(S)                                                                                                   \
-    do {                                                                                                              \
-        hipLaunchKernelGGL((gn_stats_kernel<T, 8, S>), grid_s, dim3(NT), 0, st, (const T*)x, part, HW, C, ldx, G, gs, \
-                           rpb_s);                                                                                    \
-        hipLaunchKernelGGL((gn_apply_kernel<T, 4, S>), grid, dim3(NT), 0, st, (const T*)x, (T*)y, gamma, beta, part,  \
-                           (int)grid_s.x, stats, HW, C, ldx, ldy, G, gs, eps, silu, rpb);                             \
-    } while (0)
-    if (slots == 1) PDMK_GNF(1);
-    else if (slots == 2) PDMK_GNF(2);
-    else PDMK_GNF(3);
-#undef PDMK_GNF
+    const GnGrid gst = gn_grid(GN_FWD_STATS, B, HW, C / V), gap = gn_grid(GN_FWD_APPLY, B, HW, C / V);
+    gn_dispatch_slots(C / V, [&](auto slots) {
+        constexpr int S = decltype(slots)::value;
+        hipLaunchKernelGGL((gn_stats_kernel<T, GN_FWD_STATS.unr, S>), gst.grid, dim3(NT), 0, st, (const T*)x, part, HW, C, ldx, G,
+                           gs, gst.rpb);
+        hipLaunchKernelGGL((gn_apply_kernel<T, GN_FWD_APPLY.unr, S>), gap.grid, dim3(NT), 0, st, (const T*)x, (T*)y, gamma, beta,
+                           part, (int)gst.grid.x, stats, HW, C, ldx, ldy, G, gs, eps, silu, gap.rpb);
+    });
+    PDMK_CHECK_LAUNCH();
+    return 0;
+}
+
+// statistics from the producing GEMM's epilogue (pdmk_gemm_args.colstat): the apply launch alone, nblk = -1
+template <typename T>
+int gn_apply_colstat(const void* x, void* y, const float* gamma, const float* beta, float* stats, const int64_t* colstat, int cs_ld,
+                     int B, int HW, int C, int ldx, int ldy, int G, int gs, float eps, int silu, hipStream_t st) {
+    constexpr int V = Vec<T>::N;
+    if (!gn_shape_ok<V>(C, G, gs, {ldx, ldy}, false)) return -1;
+    const GnGrid gap = gn_grid(GN_FWD_APPLY, B, HW, C / V);     // (256 ... 1024 blocks and 2 / 4 / 8 rows in flight per thread
+    gn_dispatch_slots(C / V, [&](auto slots) {                  //  measure the same, tools/gn_dbg.py)
+        hipLaunchKernelGGL((gn_apply_kernel<T, GN_FWD_APPLY.unr, decltype(slots)::value>), gap.grid, dim3(NT), 0, st, (const T*)x,
+                           (T*)y, gamma, beta, reinterpret_cast<const float*>(colstat), -1, stats, HW, C, ldx, ldy, G, gs, eps,
+                           silu, gap.rpb, cs_ld);
+    });
     PDMK_CHECK_LAUNCH();
     return 0;
 }
@@ -670,30 +680,21 @@ int gn_bwd(const void* x, const void* dy, void* dx, const float* gamma, const fl
            float* dgamma, float* dbeta, double* ws, float* part, long part_elems, int B, int HW, int C, int ldx,
            int lddy, int lddx, int G, int gs, int silu, int acc, const void* add, int ldadd, hipStream_t st) {
     constexpr int V = Vec<T>::N;
-    if (C % V || ldx % V || lddy % V || lddx % V || G > 64 || G * gs > C || C / V > MAXS * NT || C > GN_MAXC / 8 * V) return -1;
+    if (!gn_shape_ok<V>(C, G, gs, {ldx, lddy, lddx}, true)) return -1;
     if (add && ((ldadd % V) || ((uintptr_t)add & 15))) return -1;
-    const GnMap2 mp = gn_map2(C / V);
-    const int rpb_s = gn_rows_per_blk(B, HW, mp.rif * 4, 512, GN_MAXBLK);
-    dim3 grid_s((HW + rpb_s - 1) / rpb_s, B);
-    const int nblk = grid_s.x * grid_s.y, cr = G * gs;
+    const GnGrid gst = gn_grid(GN_BWD_STATS, B, HW, C / V), gap = gn_grid(GN_BWD_APPLY, B, HW, C / V);
+    const int nblk = gst.grid.x * gst.grid.y, cr = G * gs;
     if (!part || (long)nblk * 2 * cr > part_elems) return -1;
     float* gpart = reinterpret_cast<float*>(ws);                    // [B][nblk][G][2] floats <= B*G*64 doubles
-    const int rpb = gn_rows_per_blk(B, HW, mp.rif * 2, 1024, 1 << 20);
-    dim3 grid((HW + rpb - 1) / rpb, B);
-    const int slots = (C / V + NT - 1) / NT;
-#define PDMK_GNB(S)                                                                                                   \
-    do {                                                                                                              \
-        hipLaunchKernelGGL((gn_bwd_stats_kernel<T, 4, S>), grid_s, dim3(NT), 0, st, (const T*)x, (const T*)dy, gamma, \
-                           beta, stats, part, gpart, HW, C, ldx, lddy, G, gs, silu, rpb_s);                           \
-        launch_reduce_partials(part, nblk, cr, dgamma, dbeta, st);                                                    \
-        hipLaunchKernelGGL((gn_bwd_apply_kernel<T, 2, S>), grid, dim3(NT), 0, st, (const T*)x, (const T*)dy, (T*)dx,  \
-                           gamma, beta, stats, gpart, (int)grid_s.x, HW, C, ldx, lddy, lddx, G, gs, silu, acc, rpb,   \
-                           (const T*)add, ldadd);                                                                     \
-    } while (0)
-    if (slots == 1) PDMK_GNB(1);
-    else if (slots == 2) PDMK_GNB(2);
-    else PDMK_GNB(3);
-#undef PDMK_GNB
+    gn_dispatch_slots(C / V, [&](auto slots) {
+        constexpr int S = decltype(slots)::value;
+        hipLaunchKernelGGL((gn_bwd_stats_kernel<T, GN_BWD_STATS.unr, S>), gst.grid, dim3(NT), 0, st, (const T*)x, (const T*)dy,
+                           gamma, beta, stats, part, gpart, HW, C, ldx, lddy, G, gs, silu, gst.rpb);
+        launch_reduce_partials(part, nblk, cr, dgamma, dbeta, st);
+        hipLaunchKernelGGL((gn_bwd_apply_kernel<T, GN_BWD_APPLY.unr, S>), gap.grid, dim3(NT), 0, st, (const T*)x, (const T*)dy,
+                           (T*)dx, gamma, beta, stats, gpart, (int)gst.grid.x, HW, C, ldx, lddy, lddx, G, gs, silu, acc, gap.rpb,
+                           (const T*)add, ldadd);
+    });
     PDMK_CHECK_LAUNCH();
     return 0;
 }
@@ -1050,26 +1051,6 @@ int ln_bwd(const void* x, const void* dy, void* dx, const float* gamma, const fl
 
 }  // namespace
 
-template <typename T>
-int gn_apply_colstat(const void* x, void* y, const float* gamma, const float* beta, float* stats, const int64_t* colstat, int cs_ld,
-                     int B, int HW, int C, int ldx, int ldy, int G, int gs, float eps, int silu, hipStream_t st) {
-    constexpr int V = Vec<T>::N;
-    if (C % V || ldx % V || ldy % V || G > 64 || G * gs > C || C / V > MAXS * NT) return -1;
-    const GnMap2 mp = gn_map2(C / V);
-    const int rpb = gn_rows_per_blk(B, HW, mp.rif * 4, 1024, 1 << 20);     // (256 ... 1024 blocks and 2 / 4 / 8 rows in flight per thread
-    dim3 grid((HW + rpb - 1) / rpb, B);                                    //  measure the same, tools/gn_dbg.py)
-    const int slots = (C / V + NT - 1) / NT;
-#define PDMK_GNA(S)                                                                                                   \
-    hipLaunchKernelGGL((gn_apply_kernel<T, 4, S>), grid, dim3(NT), 0, st, (const T*)x, (T*)y, gamma, beta, reinterpret_cast<const float*>(colstat), -1, stats, \
-                       HW, C, ldx, ldy, G, gs, eps, silu, rpb, cs_ld)
-    if (slots == 1) PDMK_GNA(1);
-    else if (slots == 2) PDMK_GNA(2);
-    else PDMK_GNA(3);
-#undef PDMK_GNA
-    PDMK_CHECK_LAUNCH();
-    return 0;
-}
-
 extern "C" int pdmk_groupnorm_apply_colstat(const void* x, void* y, const float* gamma, const float* beta, float* stats,
                                             const int64_t* colstat, int cs_ld, int cs_col0, int B, int HW, int C, int ldx, int ldy,
                                             int G, int gs, float eps, int silu, int dtype, pdmk_stream stream) {
@@ -1103,9 +1084,8 @@ extern "C" int pdmk_groupnorm_bwd_partial_dims(int B, int HW, int C, int G, int 
     if (!nblk || !n || B <= 0 || HW <= 0 || C <= 0) return -1;
     const int V = dtype == PDMK_BF16 ? 8 : 4;
     if (C % V) return -1;
-    const GnMap2 mp = gn_map2(C / V);
-    const int rpb_s = gn_rows_per_blk(B, HW, mp.rif * 4, 512, GN_MAXBLK);
-    *nblk = ((HW + rpb_s - 1) / rpb_s) * B;
+    const dim3 grid = gn_grid(GN_BWD_STATS, B, HW, C / V).grid;    // the grid gn_bwd launches and checks part_ws_elems against
+    *nblk = grid.x * grid.y;
     *n = G * gs;
     return 0;
 }
