@@ -642,6 +642,34 @@ int pdmk_global_avgpool(const float* x, int ldx, float* y, int B, int HW, int C,
 int pdmk_fid_accumulate(const float* x, int ldx, int B, int D, double* sum, double* outer, pdmk_stream stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Perceptual metrics of the erasure evaluation (pdm/utils/perceptual.py, pdm/models/perceptual): LPIPS v0.1 (AlexNet) and the
+ * VGG-19 Gram-matrix style loss / content loss of baselines/unified-concept-editing/eval-scripts/{lpips_eval,styleloss}.py.
+ * fp32 NHWC maps [B, HW, ld] with ld >= C (a map may be a column slice of a wider buffer: columns outside [0, C) are neither
+ * read nor written), inference only.  No float atomics: the same arguments give the same bits on every launch.
+ * pdmk_relu_pool: pool 0: y = max(x, 0), same shape.  pool 2: the ReLU, then a 2 x 2 stride-2 max pool with floor sizes
+ *   (Ho = H / 2, Wo = W / 2: an odd last row / column is dropped, as nn.MaxPool2d(2, 2) does; H or W of 1: -1).  x [B, H, W, ldx],
+ *   y [B, Ho, Wo, ldy].  NaN propagates; bit-equal with torch.  With pool 0, y may be x (in place).
+ * pdmk_lpips_layer: out[b] += (1 / HW) sum_p sum_c w[c] (f0[b][p][c] / (||f0[b][p][:]||_2 + 1e-10) - f1[b][p][c] /
+ *   (||f1[b][p][:]||_2 + 1e-10))^2: lpips' normalize_tensor (eps added to the norm), lin (1 x 1 conv, no bias), spatial_average.
+ *   f0, f1 share the row stride ld; w fp32 [C]; out fp64 [B], zeroed by the caller and accumulated over the layers.  Norms and
+ *   the sum of one pixel in fp32, the sum over the pixels in fp64 in a fixed order.  An all-zero feature vector contributes
+ *   0 - other (never NaN).  16-byte loads when C % 4 == 0, ld % 4 == 0 and f0, f1, w are 16-byte aligned, element loads otherwise.
+ * pdmk_gram_pair: per image b, X_i = f_i[b] ([HW, C]): G_i = X_i^T X_i / (C HW) (each scaled in fp32, as G.div(...)),
+ *   style_out[b] += mean over C x C of (G_0 - G_1)^2, and, when content_out is not NULL, content_out[b] += mean over HW x C of
+ *   (f0 - f1)^2 from the same single pass over the two maps.  Outputs fp64 [B], accumulated into.  HW is split over workgroups
+ *   (64 x 64 tiles of the upper triangle of G on the exact-fp32 MFMA, partial tiles to ws, a finish pass that adds them in split
+ *   order): the arithmetic is a fixed function of the arguments, so an identical pair gives exactly 0.0 for both outputs.
+ *   ws: fp32 scratch of pdmk_gram_workspace_elems(B, HW, C) elements (-1 for sizes out of range), 16-byte aligned, free again
+ *   when the call's launches have run.  C <= 2048, B <= 65535.
+ * All: -1 on a null / misaligned pointer, a size < 1 or out of range, a stride smaller than the row, a workspace too small. */
+int pdmk_relu_pool(const float* x, int ldx, float* y, int ldy, int B, int H, int W, int C, int pool, pdmk_stream stream);
+int pdmk_lpips_layer(const float* f0, const float* f1, int ld, const float* w, double* out, int B, int HW, int C,
+                     pdmk_stream stream);
+int64_t pdmk_gram_workspace_elems(int B, int HW, int C);
+int pdmk_gram_pair(const float* f0, const float* f1, int ld, int B, int HW, int C, float* ws, int64_t ws_elems, double* style_out,
+                   double* content_out, pdmk_stream stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * ConceptPrune (baselines/concept_prune/wanda.py, save_union_over_time.py; pdm/utils/concept_prune.py): Wanda scores of the
  * second feed-forward Linear (ff.net.2, W [O, F]) against the norms of its input over a set of prompts, per timestep.
  * No float atomics: the same arguments give the same bits, launch after launch (the masks compare these numbers).

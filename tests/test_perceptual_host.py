@@ -1,0 +1,124 @@
+"""Host side of the perceptual metrics (no GPU): file matching and output names of the reference's lpips_eval.py / styleloss.py,
+state-dict key tables, the errors of the loaders, and the golden file against the fixtures' restatement."""
+import importlib.util
+import math
+import os
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import perceptual_fixtures as fx  # noqa: E402
+
+from pdm.models.perceptual import spec as S
+from pdm.utils import perceptual as P
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLDEN = os.path.join(ROOT, "tests", "golden", "perceptual_ref.npz")
+
+
+def _script(name):
+    path = os.path.join(ROOT, "unlearn-ft_amd", "scripts", "baselines", "unified_concept_editing", name + ".py")
+    spec = importlib.util.spec_from_file_location(name + "_host", path)
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def test_case_matching():
+    names = ["1_0.png", "1_1.png", "10_0.png", "11_0.png", "2_0.png", "1_2.jpg", "1_3.png.tmp", "x1_0.png", "notes.txt"]
+    assert P.case_files(names, 1) == ["1_0.png", "1_1.png", "1_3.png.tmp"]       # `'.png' in name`, as the reference
+    assert P.case_files(names, 10) == ["10_0.png"] and P.case_files(names, 2) == ["2_0.png"] and P.case_files(names, 3) == []
+
+
+def test_output_names():
+    assert P.result_csv("out", "/a/b/erased-model", "lpipsloss") == os.path.join("out", "erased-model_lpipsloss.csv")
+    assert P.result_csv("out", "/a/b/erased-model/", "lpipsloss") == os.path.join("out", "erased-model_lpipsloss.csv")
+    assert P.result_csv("out/", "rel/dir/", "styleloss") == os.path.join("out/", "dir_styleloss.csv")
+
+
+def test_flags_of_the_reference():
+    for name, imsize, bs in (("lpips_eval", 64, 64), ("styleloss", 512, 8)):
+        a = _script(name).parse_args(["--original_path", "o", "--edited_path", "e", "--csv_path", "c", "--save_path", "s", "--image"])
+        assert (a.original_path, a.edited_path, a.csv_path, a.save_path, a.image) == ("o", "e", "c", "s", True)
+        assert (a.imsize, a.batch_size, a.device) == (imsize, bs, "cuda:0")
+
+
+def test_state_dict_tables():
+    assert [u.name for u in S.ALEX_UNITS] == [t[0] for t in fx.ALEX] and [u.name for u in S.VGG_UNITS] == [t[0] for t in fx.VGG[:5]]
+    for u, (_, ci, co, k, s, p) in zip(S.ALEX_UNITS, fx.ALEX):
+        assert (u.ci, u.co, u.kh, u.kw, u.stride, u.ph, u.pw) == (ci, co, k, k, s, p, p)
+    assert S.conv_shapes(S.VGG_UNITS)["features.10.weight"] == (256, 128, 3, 3)
+    assert list(S.lin_shapes()) == [f"lin{i}.model.1.weight" for i in range(5)] and S.lin_shapes()["lin1.model.1.weight"] == (1, 192, 1, 1)
+    sd = fx.vgg_state_dict()
+    assert sorted(S.checked(sd, S.conv_shapes(S.VGG_UNITS), "VGG-19")) == sorted(n for n in sd if not n.startswith("features.12"))
+    with pytest.raises(KeyError, match=r"features\.7\.bias"):
+        S.checked({n: t for n, t in sd.items() if n != "features.7.bias"}, S.conv_shapes(S.VGG_UNITS), "VGG-19")
+    with pytest.raises(ValueError, match=r"features\.0\.weight"):
+        S.checked(dict(sd, **{"features.0.weight": torch.zeros(64, 3, 5, 5)}), S.conv_shapes(S.VGG_UNITS), "VGG-19")
+    mean, std = S.lpips_input_norm()
+    x = np.linspace(0, 1, 7)
+    for c in range(3):        # the composed Normalize of the [0, 1] image is the ScalingLayer of the [-1, 1] image
+        assert np.allclose((x - mean[c]) / std[c], ((2 * x - 1) - S.LPIPS_SHIFT[c]) / S.LPIPS_SCALE[c], rtol=1e-14, atol=1e-14)
+
+
+def test_missing_weights_say_what_to_place_where(tmp_path):
+    from pdm.models.perceptual import nets
+    with pytest.raises(FileNotFoundError) as e:
+        nets._load_file(str(tmp_path / "nope.pth"), S.VGG_WEIGHTS_NAME, "--vgg_weights", "torchvision VGG-19")
+    msg = str(e.value)
+    assert str(tmp_path / "nope.pth") in msg and "vgg19-dcbb9e9d.pth" in msg and "--vgg_weights" in msg and "nothing is downloaded" in msg
+    assert nets.hub_checkpoint("alex.pth").endswith(os.path.join(".cache", "torch", "hub", "checkpoints", "alex.pth"))
+
+
+def test_non_square_image_is_refused_by_name(tmp_path):
+    from PIL import Image
+    path = str(tmp_path / "3_0.png")
+    Image.fromarray(np.zeros((40, 48, 3), np.uint8)).save(path)
+    with pytest.raises(ValueError, match=r"3_0\.png.*not square"):
+        P.load_rgb(path)
+    with pytest.raises(ValueError, match="not square"):
+        P.load_rgb(np.zeros((4, 5, 3), np.uint8))
+    grey = str(tmp_path / "4_0.png")
+    Image.fromarray(np.full((8, 8), 7, np.uint8)).save(grey)
+    assert P.load_rgb(grey).shape == (8, 8, 3)                     # read as RGB
+
+
+def test_folder_loop_without_a_gpu(tmp_path, capsys):
+    """evaluate_folders with a stand-in metric: means per case, a missing edited file skipped and printed, NaN without files."""
+    o, e = tmp_path / "o", tmp_path / "e"
+    o.mkdir(), e.mkdir()
+    for n in ("1_0.png", "1_1.png", "10_0.png", "2_0.png"):
+        (o / n).write_bytes(b"x")
+        if n != "1_1.png":
+            (e / n).write_bytes(b"x")
+    csv_path = tmp_path / "p.csv"
+    csv_path.write_text("case_number,prompt,evaluation_seed\n1,\"a, b\",5\n2,c,6\n10,d,7\n3,e,8\n")
+    seen = []
+
+    def metric(a, b):
+        seen.append([os.path.basename(x) for x in a])
+        return (np.arange(len(a), dtype=np.float64) + 1,)
+
+    header, rows = P.evaluate_folders(str(o), str(e), str(csv_path), ["m"], metric)
+    assert "1_1.png: No File" in capsys.readouterr().out
+    assert seen == [["1_0.png", "2_0.png", "10_0.png"]] and header == ["case_number", "prompt", "evaluation_seed", "m"]
+    assert [r[:2] for r in rows] == [["1", "a, b"], ["2", "c"], ["10", "d"], ["3", "e"]]
+    assert [r[-1] for r in rows[:3]] == [1.0, 2.0, 3.0] and math.isnan(rows[3][-1])
+    out = P.write_frame(str(tmp_path / "r" / "x.csv"), header, rows)
+    lines = open(out).read().splitlines()
+    assert lines[0] == ",case_number,prompt,evaluation_seed,m" and lines[1] == '0,1,"a, b",5,1.0' and lines[4] == "3,3,e,8,nan"
+
+
+def test_golden_file_is_consistent_with_the_fixtures():
+    """The numbers of the reference's own code (float64) against the fixtures' restatement of the same pairs: 1e-12; the
+    reference's float32 run is within 1e-5 of its float64 run (what makes it a yardstick)."""
+    z = np.load(GOLDEN)
+    assert z["ref64"].shape == (3, 3) and z["ref32"].shape == (3, 3)
+    mine = fx.vgg_losses(fx.vgg_state_dict(), *fx.golden_pairs(), 48, torch.float64)
+    assert np.abs(mine - z["ref64"]).max() <= 1e-12 * np.abs(z["ref64"]).max()
+    assert (np.abs(mine - z["ref64"]) <= 1e-11 * np.abs(z["ref64"])).all()
+    assert (np.abs(z["ref32"] - z["ref64"]) <= 1e-5 * np.abs(z["ref64"])).all() and z["gap"].max() <= 1e-5 and z["lpips_gap"].max() <= 1e-5
+    assert np.allclose(z["ref64"][:, 2], 1e6 * z["ref64"][:, 0] + z["ref64"][:, 1], rtol=1e-14)

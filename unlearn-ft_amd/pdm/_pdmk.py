@@ -147,6 +147,10 @@ _SIGS = {
     "pdmk_pool2d": ([vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp], i32),
     "pdmk_global_avgpool": ([vp, i32, vp, i32, i32, i32, vp], i32),
     "pdmk_fid_accumulate": ([vp, i32, i32, i32, vp, vp, vp], i32),
+    "pdmk_relu_pool": ([vp, i32, vp, i32, i32, i32, i32, i32, i32, vp], i32),
+    "pdmk_lpips_layer": ([vp, vp, i32, vp, vp, i32, i32, i32, vp], i32),
+    "pdmk_gram_workspace_elems": ([i32, i32, i32], i64),
+    "pdmk_gram_pair": ([vp, vp, i32, i32, i32, i32, vp, i64, vp, vp, vp], i32),
     "pdmk_rownorm_colsq_workspace_elems": ([i32, i32], i64),
     "pdmk_rownorm_colsq": ([vp, i32, i32, i32, i32, vp, vp, i64, vp], i32),
     "pdmk_wanda_count": ([vp, i32, i32, i32, i32, vp, vp, i32, i32, vp, vp], i32),
@@ -1108,6 +1112,43 @@ def fid_accumulate(x, total, outer):
             or not outer.is_contiguous()):
         raise PdmkError("fid_accumulate: x fp32 [B, D], total fp64 [D], outer fp64 [D, D] contiguous")
     _chk(_lib.pdmk_fid_accumulate(_p(x), x.stride(0), B, D, _p(total), _p(outer), _st()), "pdmk_fid_accumulate")
+
+
+def relu_pool(x, ldx, y, ldy, B, H, W, Cc, pool):
+    """y = max(x, 0) (pool 0), then a 2 x 2 stride-2 max pool with floor sizes (pool 2); NHWC fp32, strided rows."""
+    Ho, Wo = (H // 2, W // 2) if pool == 2 else (H, W)
+    if (x.dtype != torch.float32 or y.dtype != torch.float32 or min(B, H, W, Cc) < 1
+            or _avail(x) < (B * H * W - 1) * ldx + Cc or _avail(y) < (B * Ho * Wo - 1) * ldy + Cc):
+        raise PdmkError("relu_pool: fp32 buffers, x >= [B*H*W rows of ldx], y >= [B*Ho*Wo rows of ldy]")
+    _chk(_lib.pdmk_relu_pool(_p(x), ldx, _p(y), ldy, B, H, W, Cc, int(pool), _st()), "pdmk_relu_pool")
+
+
+def lpips_layer(f0, f1, ld, w, out, B, HW, Cc):
+    """out[b] += one LPIPS layer of the pair of maps f0, f1 ([B, HW, ld] fp32, C channels), w fp32 [C], out fp64 [B]."""
+    if (f0.dtype != torch.float32 or f1.dtype != torch.float32 or w.dtype != torch.float32 or out.dtype != torch.float64
+            or min(B, HW, Cc) < 1 or w.numel() < Cc or not w.is_contiguous() or out.numel() < B or not out.is_contiguous()
+            or min(_avail(f0), _avail(f1)) < (B * HW - 1) * ld + Cc):
+        raise PdmkError("lpips_layer: f0 / f1 fp32 >= [B*HW rows of ld], w fp32 [C], out fp64 [B] contiguous")
+    _chk(_lib.pdmk_lpips_layer(_p(f0), _p(f1), ld, _p(w), _p(out), B, HW, Cc, _st()), "pdmk_lpips_layer")
+
+
+def gram_workspace_elems(B, HW, Cc):
+    n = _lib.pdmk_gram_workspace_elems(B, HW, Cc)
+    if n < 0:
+        raise PdmkError(f"pdmk_gram_workspace_elems({B}, {HW}, {Cc}): sizes out of range")
+    return n
+
+
+def gram_pair(f0, f1, ld, B, HW, Cc, ws, style_out, content_out=None):
+    """style_out[b] += mean((G_0 - G_1)^2), content_out[b] += mean((f0 - f1)^2) (None: not taken); maps [B, HW, ld] fp32,
+    outputs fp64 [B], ws fp32 scratch of gram_workspace_elems(B, HW, C) elements."""
+    if (f0.dtype != torch.float32 or f1.dtype != torch.float32 or ws.dtype != torch.float32 or not ws.is_contiguous()
+            or min(B, HW, Cc) < 1 or min(_avail(f0), _avail(f1)) < (B * HW - 1) * ld + Cc
+            or any(o is not None and (o.dtype != torch.float64 or o.numel() < B or not o.is_contiguous())
+                   for o in (style_out, content_out)) or style_out is None):
+        raise PdmkError("gram_pair: f0 / f1 fp32 >= [B*HW rows of ld], ws fp32, style_out / content_out fp64 [B] contiguous")
+    _chk(_lib.pdmk_gram_pair(_p(f0), _p(f1), ld, B, HW, Cc, _p(ws), ws.numel(), _p(style_out), _p(content_out), _st()),
+         "pdmk_gram_pair")
 
 
 def softmax_rows(s, p, rows, cols, lds, ldp):

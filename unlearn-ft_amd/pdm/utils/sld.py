@@ -66,8 +66,27 @@ def with_suffix(name, sld_type):
     return name if sld_type is None else f"{name}_SLD_{sld_type}"
 
 
-def read_cases(path, from_case=0):
-    """[(case_number, prompt, evaluation_seed)] of the prompt CSV in file order, rows with case_number < from_case left out."""
+def sample_cases(pipe, prompts_path, folder, from_case=0, till_case=None, num_samples=1, **sampling):
+    """The row loop of the reference's sld-generate-images.py and generate-images.py: per row of the prompt CSV
+    `torch.Generator(device).manual_seed(evaluation_seed)`, `num_samples` images of the prompt as one batch (`sampling`: the
+    keywords of the pipeline call), uint8 as diffusers' numpy_to_pil (rounded), written to <folder>/<case_number>_<n>.png.
+    Returns the paths written, in order."""
+    import torch
+    from PIL import Image
+    os.makedirs(folder, exist_ok=True)
+    written = []
+    for case_number, prompt, seed in read_cases(prompts_path, from_case, till_case):
+        gen = torch.Generator(device=pipe.device).manual_seed(seed)
+        images = pipe(prompt=[prompt] * num_samples, generator=gen, output_type="u8_round", **sampling).images
+        for num, im in enumerate(images):
+            written.append(os.path.join(folder, image_name(case_number, num)))
+            Image.fromarray(im).save(written[-1])
+    return written
+
+
+def read_cases(path, from_case=0, till_case=None):
+    """[(case_number, prompt, evaluation_seed)] of the prompt CSV in file order, rows with case_number < from_case (or, with
+    till_case, > till_case) left out."""
     cases = []
     with open(path, encoding="utf-8", newline="") as f:
         for row in csv.DictReader(f):
@@ -76,7 +95,7 @@ def read_cases(path, from_case=0):
                 raise ValueError(f"{path}: expected the columns `case_number`, `prompt` and `evaluation_seed`, "
                                  f"got {sorted(k for k in row if k)}")
             case = int(row["case_number"])
-            if case < int(from_case):
+            if case < int(from_case) or (till_case is not None and case > int(till_case)):
                 continue
             cases.append((case, str(row["prompt"]), int(row["evaluation_seed"])))
     return cases

@@ -14,7 +14,8 @@ block, D comes from pdmk_uce_delta and the update is one more GEMM on that matri
 
 Host side (no GPU needed): the text-list builders, the checkpoint name, the slice arithmetic.  GPU side: `edit_model`.
 
-Not built: train_debias.py (a loop of generation and CLIP classification), the eval-scripts, `layers_to_edit` (the reference's
+Not built: train_debias.py (a loop of generation and CLIP classification), the eval-scripts other than generate-images.py,
+lpips_eval.py and styleloss.py (those three: pdm/utils/perceptual.py), `layers_to_edit` (the reference's
 __main__ never sets it), SD-1.4, and the fixed concept lists `allartist`, `i2g`, `10artists`, `imagenette`.
 """
 import random

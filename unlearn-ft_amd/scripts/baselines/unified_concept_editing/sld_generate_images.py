@@ -54,20 +54,11 @@ def parse_args(argv=None):
 @torch.no_grad()
 def generate_SLD(pipe, sld_concept, sld_type, prompts_path, save_path, guidance_scale=7.5, image_size=512, ddim_steps=50,
                  num_samples=1, from_case=0):
-    from PIL import Image
     kw = S.sampling_kwargs(sld_type, sld_concept)
     print(kw["safety_concept"])
-    folder = S.folder_path(save_path, sld_type, sld_concept)
-    os.makedirs(folder, exist_ok=True)
-    written = []
-    for case_number, prompt, seed in S.read_cases(prompts_path, from_case):
-        gen = torch.Generator(device=pipe.device).manual_seed(seed)
-        images = pipe(prompt=[prompt] * num_samples, generator=gen, guidance_scale=guidance_scale, height=image_size,
-                      width=image_size, num_inference_steps=ddim_steps, output_type="u8_round", **kw).images
-        for num, im in enumerate(images):
-            written.append(os.path.join(folder, S.image_name(case_number, num)))
-            Image.fromarray(im).save(written[-1])
-    return written
+    return S.sample_cases(pipe, prompts_path, S.folder_path(save_path, sld_type, sld_concept), from_case=from_case,
+                          num_samples=num_samples, guidance_scale=guidance_scale, height=image_size, width=image_size,
+                          num_inference_steps=ddim_steps, **kw)
 
 
 def main(argv=None):
