@@ -623,6 +623,11 @@ int pdmk_image_to_u8_ex(const float* src, uint8_t* dst, int B, int C, int HW, in
  *   of a wider buffer: columns outside [0, Co) are not touched), w [Co][kh * kw * Ci] contiguous, bias [Co] or NULL, relu 0 / 1.
  *   Taps outside the image read zero.  16-byte loads when Ci % 4 == 0, lda % 4 == 0 and x, w are 16-byte aligned; any
  *   geometry otherwise (element gathers).
+ * pdmk_conv2d_fwd_res: pdmk_conv2d_fwd with a residual operand: v = acc + bias[n]; v += res[m * ldr + n]; relu last.  res fp32,
+ *   laid out like y (rows m = (b, oy, ox), row stride ldr >= Co).  res may be EXACTLY y (same pointer, ldr == ldc): every
+ *   thread reads its element before it writes it, so a ResNet identity block writes conv3 over its input; any other overlap
+ *   of res and y is the caller's error.  res == NULL is pdmk_conv2d_fwd, bit for bit (ldr is then ignored).  The residual is
+ *   read in the epilogue only.  -1 also on ldr < Co or a misaligned res.
  * pdmk_pool2d: 3 x 3 window, mode 0 max, mode 1 average over the taps inside the image (count_include_pad=False); stride
  *   >= 1, pad 0 or 1; x [B, H, W, ldx], y [B, Ho, Wo, ldy], C channels of each row.
  * pdmk_global_avgpool: x [B, HW, ldx] -> y [B, C] contiguous, rows summed in order then divided by HW.
@@ -636,10 +641,24 @@ int pdmk_image_resize_u8(const uint8_t* src, int64_t src_bytes, const pdmk_image
                          int B, int OH, int OW, uint8_t* out, pdmk_stream stream);
 int pdmk_conv2d_fwd(const float* x, int lda, const float* w, const float* bias, float* y, int ldc, int B, int H, int W, int Ci,
                     int Co, int kh, int kw, int stride, int pad_h, int pad_w, int relu, pdmk_stream stream);
+int pdmk_conv2d_fwd_res(const float* x, int lda, const float* w, const float* bias, const float* res, int ldr, float* y, int ldc,
+                        int B, int H, int W, int Ci, int Co, int kh, int kw, int stride, int pad_h, int pad_w, int relu,
+                        pdmk_stream stream);
 int pdmk_pool2d(const float* x, int ldx, float* y, int ldy, int B, int H, int W, int C, int mode, int stride, int pad,
                 pdmk_stream stream);
 int pdmk_global_avgpool(const float* x, int ldx, float* y, int B, int HW, int C, pdmk_stream stream);
 int pdmk_fid_accumulate(const float* x, int ldx, int B, int D, double* sum, double* outer, pdmk_stream stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * Classifier head of the object-erasure evaluation (pdm/models/resnet, pdm/utils/object_erasure.py).
+ * pdmk_softmax_topk: logits fp32 [B, N] (row stride ld >= N) -> probs fp32 [B, k], idx int32 [B, k] (both contiguous):
+ *   probs[b][j] is the j-th largest value of softmax(logits[b]) and idx[b][j] its column.  1 <= k <= min(N, 16), N <= 65536.
+ *   One wave per row: row maximum, sum exp(x - max) in fp32 in a fixed lane / element order, k rounds of a wave arg-max over
+ *   the logits; only the k winners are divided.  Equal logits (-0 == +0) come lower column first - this library's rule, torch
+ *   leaves the order of ties open.  A NaN logit ranks above everything (as torch.topk), lower column first among NaNs, and
+ *   every probability of that row is NaN.  No atomics: the same arguments give the same bits on every launch.
+ *   -1 on a null / misaligned pointer, a size out of range or ld < N. */
+int pdmk_softmax_topk(const float* logits, int ld, int B, int N, int k, float* probs, int32_t* idx, pdmk_stream stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Perceptual metrics of the erasure evaluation (pdm/utils/perceptual.py, pdm/models/perceptual): LPIPS v0.1 (AlexNet) and the

@@ -2,6 +2,8 @@
 //   pdmk_conv2d_fwd      : NHWC implicit-GEMM convolution, general (kh, kw, stride, pad_h, pad_w), exact-fp32 MFMA
 //                          (v_mfma_f32_16x16x4_f32), fused per-channel bias + ReLU, strided input / output rows so that a
 //                          branch of a Mixed block writes its column slice of the block's output buffer (no concat copy).
+//   pdmk_conv2d_fwd_res  : the same launch with a residual operand (fp32, laid out like the output) added between the bias and
+//                          the ReLU in the epilogue: ResNet's relu(bn(conv3) + identity).  The K loop is untouched.
 //   pdmk_pool2d          : NHWC 3x3 max pool and 3x3 average pool whose divisor is the number of taps inside the image
 //                          (count_include_pad=False), any stride / pad <= 1.
 //   pdmk_global_avgpool  : [B, HW, C] -> [B, C], one thread per output, rows summed in order.
@@ -29,12 +31,12 @@ constexpr int BN = 64, BK = 16;      // the tile is 64 WM x 64 (WM = 2, or 1 whe
 constexpr int RSB = BN + 8;
 
 struct ConvGeom {
-    int B, H, W, Ci, Co, kh, kw, stride, ph, pw, Ho, Wo, lda, ldc, M, K, relu;
+    int B, H, W, Ci, Co, kh, kw, stride, ph, pw, Ho, Wo, lda, ldc, M, K, relu, ldr;
 };
 
 template <bool VEC, int WM>
 __global__ __launch_bounds__(NT) void conv2d_kernel(const float* __restrict__ x, const float* __restrict__ w,
-                                                    const float* __restrict__ bias, float* __restrict__ y, ConvGeom g) {
+                                                    const float* __restrict__ bias, const float* res, float* y, ConvGeom g) {
     constexpr int BM = 64 * WM, RSA = BM + 8;
     __shared__ float As[BK * RSA];
     __shared__ float Bs[BK * RSB];
@@ -156,9 +158,24 @@ __global__ __launch_bounds__(NT) void conv2d_kernel(const float* __restrict__ x,
         }
     }
 
-    // epilogue: lane l holds rows 4 (l >> 4) + r, column l & 15 of each 16 x 16 tile
+    // epilogue: lane l holds rows 4 (l >> 4) + r, column l & 15 of each 16 x 16 tile.  res may be y itself (neither is
+    // __restrict__): a thread reads its elements of res before it writes those elements of y, and no other thread touches
+    // them.  The residual values of a column tile are fetched together before that tile is stored: four round trips, not one
+    // per element behind a store it could alias.  (Fetching the whole fragment, or one tile ahead, costs the 128-row form
+    // a wave of occupancy, with or without a residual.)
+    float rv[WM][4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
+        if (res) {
+            const int nr = n0 + 16 * j + (lane & 15);
+#pragma unroll
+            for (int i = 0; i < WM; ++i)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int m = m0 + wave * 16 * WM + 16 * i + 4 * (lane >> 4) + r;
+                    rv[i][r] = (nr < g.Co && m < g.M) ? res[(long)m * g.ldr + nr] : 0.f;
+                }
+        }
         const int n = n0 + 16 * j + (lane & 15);
         if (n >= g.Co) continue;
         const float bv = bias ? bias[n] : 0.f;
@@ -169,6 +186,7 @@ __global__ __launch_bounds__(NT) void conv2d_kernel(const float* __restrict__ x,
                 const int m = m0 + wave * 16 * WM + 16 * i + 4 * (lane >> 4) + r;
                 if (m < g.M) {
                     float v = acc[i][j][r] + bv;
+                    if (res) v += rv[i][r];
                     if (g.relu) v = fmaxf(v, 0.f);
                     y[(long)m * g.ldc + n] = v;
                 }
@@ -287,8 +305,10 @@ unsigned grid_for(long n) {
 
 }  // namespace
 
-extern "C" int pdmk_conv2d_fwd(const float* x, int lda, const float* w, const float* bias, float* y, int ldc, int B, int H, int W,
-                               int Ci, int Co, int kh, int kw, int stride, int pad_h, int pad_w, int relu, pdmk_stream stream) {
+extern "C" int pdmk_conv2d_fwd_res(const float* x, int lda, const float* w, const float* bias, const float* res, int ldr, float* y,
+                                   int ldc, int B, int H, int W, int Ci, int Co, int kh, int kw, int stride, int pad_h, int pad_w,
+                                   int relu, pdmk_stream stream) {
+    if (res && (ldr < Co || ((uintptr_t)res & 3))) return -1;
     if (!x || !w || !y || B < 1 || H < 1 || W < 1 || Ci < 1 || Co < 1 || kh < 1 || kw < 1 || kh > 16 || kw > 16 || stride < 1 ||
         pad_h < 0 || pad_w < 0 || pad_h >= kh || pad_w >= kw || lda < Ci || ldc < Co || H + 2 * pad_h < kh || W + 2 * pad_w < kw)
         return -1;
@@ -296,7 +316,7 @@ extern "C" int pdmk_conv2d_fwd(const float* x, int lda, const float* w, const fl
     g.B = B, g.H = H, g.W = W, g.Ci = Ci, g.Co = Co, g.kh = kh, g.kw = kw, g.stride = stride, g.ph = pad_h, g.pw = pad_w;
     g.Ho = (H + 2 * pad_h - kh) / stride + 1;
     g.Wo = (W + 2 * pad_w - kw) / stride + 1;
-    g.lda = lda, g.ldc = ldc, g.relu = relu ? 1 : 0;
+    g.lda = lda, g.ldc = ldc, g.relu = relu ? 1 : 0, g.ldr = res ? ldr : 0;
     const int64_t M = (int64_t)B * g.Ho * g.Wo, K = (int64_t)kh * kw * Ci;
     if (M > (1ll << 30) || K > (1ll << 24) || (int64_t)B * H * W * lda > (1ll << 40)) return -1;
     g.M = (int)M, g.K = (int)K;
@@ -307,12 +327,17 @@ extern "C" int pdmk_conv2d_fwd(const float* x, int lda, const float* w, const fl
     const bool small = (M + 127) / 128 * gy < 512;
     dim3 grid((unsigned)((M + (small ? 63 : 127)) / (small ? 64 : 128)), (unsigned)gy);
     hipStream_t st = (hipStream_t)stream;
-    if (vec && small) hipLaunchKernelGGL((conv2d_kernel<true, 1>), grid, dim3(NT), 0, st, x, w, bias, y, g);
-    else if (vec) hipLaunchKernelGGL((conv2d_kernel<true, 2>), grid, dim3(NT), 0, st, x, w, bias, y, g);
-    else if (small) hipLaunchKernelGGL((conv2d_kernel<false, 1>), grid, dim3(NT), 0, st, x, w, bias, y, g);
-    else hipLaunchKernelGGL((conv2d_kernel<false, 2>), grid, dim3(NT), 0, st, x, w, bias, y, g);
+    if (vec && small) hipLaunchKernelGGL((conv2d_kernel<true, 1>), grid, dim3(NT), 0, st, x, w, bias, res, y, g);
+    else if (vec) hipLaunchKernelGGL((conv2d_kernel<true, 2>), grid, dim3(NT), 0, st, x, w, bias, res, y, g);
+    else if (small) hipLaunchKernelGGL((conv2d_kernel<false, 1>), grid, dim3(NT), 0, st, x, w, bias, res, y, g);
+    else hipLaunchKernelGGL((conv2d_kernel<false, 2>), grid, dim3(NT), 0, st, x, w, bias, res, y, g);
     PDMK_CHECK_LAUNCH();
     return 0;
+}
+
+extern "C" int pdmk_conv2d_fwd(const float* x, int lda, const float* w, const float* bias, float* y, int ldc, int B, int H, int W,
+                               int Ci, int Co, int kh, int kw, int stride, int pad_h, int pad_w, int relu, pdmk_stream stream) {
+    return pdmk_conv2d_fwd_res(x, lda, w, bias, nullptr, 0, y, ldc, B, H, W, Ci, Co, kh, kw, stride, pad_h, pad_w, relu, stream);
 }
 
 extern "C" int pdmk_pool2d(const float* x, int ldx, float* y, int ldy, int B, int H, int W, int C, int mode, int stride, int pad,

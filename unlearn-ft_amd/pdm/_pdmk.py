@@ -144,6 +144,8 @@ _SIGS = {
     "pdmk_resize_bilinear_u8": ([vp, i64, vp, vp, i32, i32, vp, vp], i32),
     "pdmk_image_resize_u8": ([vp, i64, vp, vp, i32, i32, i32, vp, vp], i32),
     "pdmk_conv2d_fwd": ([vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp], i32),
+    "pdmk_conv2d_fwd_res": ([vp, i32, vp, vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp], i32),
+    "pdmk_softmax_topk": ([vp, i32, i32, i32, i32, vp, vp, vp], i32),
     "pdmk_pool2d": ([vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp], i32),
     "pdmk_global_avgpool": ([vp, i32, vp, i32, i32, i32, vp], i32),
     "pdmk_fid_accumulate": ([vp, i32, i32, i32, vp, vp, vp], i32),
@@ -1086,6 +1088,37 @@ def conv2d_fwd(x, lda, w, bias, y, ldc, B, H, W, Ci, Co, kh, kw, stride, pad_h, 
         raise PdmkError("conv2d_fwd: fp32 buffers, x >= [B*H*W rows of lda], y >= [B*Ho*Wo rows of ldc], w [Co, kh*kw*Ci]")
     _chk(_lib.pdmk_conv2d_fwd(_p(x), lda, _p(w), _p(bias), _p(y), ldc, B, H, W, Ci, Co, kh, kw, stride, pad_h, pad_w,
                               int(bool(relu)), _st()), "pdmk_conv2d_fwd")
+
+
+def conv2d_fwd_res(x, lda, w, bias, res, ldr, y, ldc, B, H, W, Ci, Co, kh, kw, stride, pad_h, pad_w, relu=True):
+    """conv2d_fwd with a residual added before the ReLU (include/pdmk.h pdmk_conv2d_fwd_res): res fp32, laid out like y with
+    row stride ldr; it may be y itself (in place), no other overlap.  res None is conv2d_fwd."""
+    Ho, Wo = (H + 2 * pad_h - kh) // stride + 1, (W + 2 * pad_w - kw) // stride + 1
+    if (any(t.dtype != torch.float32 for t in (x, w, y)) or (bias is not None and (bias.dtype != torch.float32 or bias.numel() < Co))
+            or w.numel() < Co * kh * kw * Ci or not w.is_contiguous() or _avail(x) < (B * H * W - 1) * lda + Ci
+            or _avail(y) < (B * Ho * Wo - 1) * ldc + Co
+            or (res is not None and (res.dtype != torch.float32 or ldr < Co or _avail(res) < (B * Ho * Wo - 1) * ldr + Co))):
+        raise PdmkError("conv2d_fwd_res: fp32 buffers, x >= [B*H*W rows of lda], y / res >= [B*Ho*Wo rows of ldc / ldr], "
+                        "w [Co, kh*kw*Ci]")
+    _chk(_lib.pdmk_conv2d_fwd_res(_p(x), lda, _p(w), _p(bias), _p(res), ldr, _p(y), ldc, B, H, W, Ci, Co, kh, kw, stride, pad_h,
+                                  pad_w, int(bool(relu)), _st()), "pdmk_conv2d_fwd_res")
+
+
+def softmax_topk(logits, k, probs=None, idx=None):
+    """Top-k of softmax(logits) per row (include/pdmk.h pdmk_softmax_topk): logits fp32 [B, N] with unit column stride (a
+    column slice of a wider buffer is fine) -> (probs fp32 [B, k], idx int32 [B, k]); ties lower column first."""
+    if (logits.dim() != 2 or logits.dtype != torch.float32 or logits.stride(1) != 1 or logits.shape[0] < 1
+            or (logits.shape[0] > 1 and logits.stride(0) < logits.shape[1])):
+        raise PdmkError("softmax_topk: logits fp32 [B, N], unit column stride, row stride >= N")
+    B, N = logits.shape
+    probs = torch.empty((B, k), device=logits.device, dtype=torch.float32) if probs is None else probs
+    idx = torch.empty((B, k), device=logits.device, dtype=torch.int32) if idx is None else idx
+    if (probs.dtype != torch.float32 or idx.dtype != torch.int32 or tuple(probs.shape) != (B, k) or tuple(idx.shape) != (B, k)
+            or not probs.is_contiguous() or not idx.is_contiguous()):
+        raise PdmkError("softmax_topk: probs fp32 [B, k], idx int32 [B, k], both contiguous")
+    ld = logits.stride(0) if B > 1 else max(N, logits.stride(0))
+    _chk(_lib.pdmk_softmax_topk(_p(logits), ld, B, N, int(k), _p(probs), _p(idx), _st()), "pdmk_softmax_topk")
+    return probs, idx
 
 
 def pool2d(x, ldx, y, ldy, B, H, W, Cc, mode, stride, pad):
