@@ -659,6 +659,22 @@ int pdmk_fid_accumulate(const float* x, int ldx, int B, int D, double* sum, doub
  *   every probability of that row is NaN.  No atomics: the same arguments give the same bits on every launch.
  *   -1 on a null / misaligned pointer, a size out of range or ld < N. */
 int pdmk_softmax_topk(const float* logits, int ld, int B, int N, int k, float* probs, int32_t* idx, pdmk_stream stream);
+/* pdmk_zeroshot_head: CLIP zero-shot classification of B images against A class texts (baselines/unified-concept-editing/
+ *   train-scripts/train_debias.py get_ratios, eval-scripts/CLIP_classify.py; pdm/utils/uce_debias.py).  img fp32 [B, D] (row
+ *   stride lda >= D), txt fp32 [A, D] (row stride ldb >= D), neither normalised; scale: the host's fp32 exp(logit_scale).
+ *   One wave per image row: cos[a] = <img, txt_a> / (||img|| ||txt_a||) with the three sums in fp64 from the fp32 inputs in a
+ *   fixed lane / element order (a zero norm gives cos = 0); logit[a] = fp32((double)scale * cos[a]); probs[b][a] =
+ *   fp32(exp(d_a) / sum_a exp(d_a)) with d_a = the fp32 difference logit[a] - max and the rest in fp64, rounded once (torch's
+ *   softmax formula on the fp32 logits); mask[b][a] = (logit[a] == max) - the reference's probs >= rowmax, so two identical
+ *   class rows both get 1 and an all-zero image row gets ones everywhere.  probs fp32 [B, A], mask int32 [B, A], both contiguous.
+ *   hits (may be NULL) int32 [G, A], contiguous, zeroed by the caller and accumulated into: hits[g][a] += mask[b][a] with
+ *   g = group[b] (group: DEVICE int32 [B]; NULL: g = 0) by integer atomicAdd - exact and independent of order, so the same
+ *   arguments give the same bits.  A row whose group lies outside [0, G) is left out of hits.  No floating-point atomics.
+ *   1 <= A <= PDMK_ZEROSHOT_MAX_CLASSES, 1 <= D <= 4096, 1 <= B <= 65535, G >= 1 with hits.
+ *   -1 on a null / misaligned pointer, a size out of range or a stride smaller than D. */
+#define PDMK_ZEROSHOT_MAX_CLASSES 64
+int pdmk_zeroshot_head(const float* img, int lda, const float* txt, int ldb, int B, int A, int D, float scale, float* probs,
+                       int32_t* mask, const int32_t* group, int32_t* hits, int G, pdmk_stream stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Perceptual metrics of the erasure evaluation (pdm/utils/perceptual.py, pdm/models/perceptual): LPIPS v0.1 (AlexNet) and the
@@ -737,8 +753,20 @@ int pdmk_wanda_apply(void* w, int dtype, int O, int F, int ldw, const int32_t* c
  *   the reference's N - <u, N> u - O with u = O / ||O||; an all-zero block gives D = N where the reference divides by zero.
  *   Rows [row_seg[P], m) of the column range are written as zeros; columns outside [col_seg[0], col_seg[Q]) are not touched.
  *   ws: 2 P Q fp64 (technique 1; may be NULL for technique 0).  P <= 65534.
+ * pdmk_uce_debias_delta (train-scripts/train_debias.py; pdm/utils/uce_debias.py): O, D fp32 [m, ld]; U fp32 [A, m, ld],
+ *   attribute-major, attribute j at U + j m ld with O's row segmentation; w fp32 [P, A] on the DEVICE; row_seg / col_seg as
+ *   for pdmk_uce_delta.  Per block (p, q), norms Frobenius over the block:  T_0 = O, T_{j+1} = T_j + (w[p][j] ||T_j||) U_j /
+ *   ||U_j||, D = T_A - O = sum_j c_j U_j with c_j = w[p][j] ||T_j|| / ||U_j|| - the reference adds into an alias of O, so the
+ *   norm is the running one.  Pass one (a workgroup per block): the (A + 1)(A + 2) / 2 dot products of {O, U_0 .. U_{A-1}} in
+ *   fp64 in a fixed order (no atomics); ||T_j||^2 is the quadratic form of (1, c_0 .. c_{j-1}) in that Gram matrix, and one
+ *   thread runs the A steps in fp64 into ws.  Pass two: D = fp32(sum_j c_j U_j), the sum in fp64 in the order of j, rounded
+ *   once; 16-byte loads and stores for a block whose first column, width and ld are multiples of 4 with 16-byte aligned U and
+ *   D.  A block whose weights are all zero gets exact zeros.  A zero U_j block contributes nothing (c_j = 0) where the
+ *   reference divides by zero and yields NaN.  Rows [row_seg[P], m) of the column range are written as zeros; columns outside
+ *   [col_seg[0], col_seg[Q]) are not touched.  ws: fp64, at least P Q A elements.  1 <= A <= PDMK_DEBIAS_MAX_ATTR, P <= 65534.
  * All: -1 on a null / misaligned pointer, a size out of range, a stride smaller than the row, a workspace too small. */
 #define PDMK_SPD_MAX_N 4096
+#define PDMK_DEBIAS_MAX_ATTR 8
 int64_t pdmk_spd_workspace_elems(int n, int m);
 int pdmk_spd_system_f64(const double* g_a, double s_a, const double* g_b, double s_b, double lam, double* A, int n, int lda,
                         pdmk_stream stream);
@@ -747,6 +775,8 @@ int pdmk_spd_solve_f64(const double* L, int n, int ldl, const float* B, int m, i
                        double* ws, int64_t ws_elems, pdmk_stream stream);
 int pdmk_uce_delta(const float* O, const float* N, float* D, int m, int ld, const int32_t* row_seg, int P, const int32_t* col_seg,
                    int Q, int technique, double* ws, pdmk_stream stream);
+int pdmk_uce_debias_delta(const float* O, const float* U, float* D, int m, int ld, int A, const float* w, const int32_t* row_seg,
+                          int P, const int32_t* col_seg, int Q, double* ws, int64_t ws_elems, pdmk_stream stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Data-parallel gradient exchange: DDP's all-reduce inside accelerator.backward

@@ -1,5 +1,7 @@
 // The classifier head of the object-erasure evaluation (pdm/models/resnet): top-k of softmax(logits) on the device.
 //   pdmk_softmax_topk : logits fp32 [B, N] (row stride ld) -> probs fp32 [B, k], idx int32 [B, k], k <= 16, N <= 65536.
+// and CLIP's zero-shot head of the debiasing baseline (pdm/utils/uce_debias.py), further down:
+//   pdmk_zeroshot_head : image features [B, D], class-text features [A, D] -> softmax probs, "which class wins" mask, counts.
 //
 // One wave per row, four rows per workgroup; lane l owns the columns l, l + 64, l + 128, ... (coalesced 256-byte reads).  With
 // N <= 1024 the lane's 16 values stay in registers for all three steps, otherwise each step reads the row again:
@@ -107,6 +109,55 @@ __global__ __launch_bounds__(NT) void softmax_topk_kernel(const float* __restric
     }
 }
 
+// One wave per image row, four rows per workgroup; lane l owns the columns l, l + 64, ... of the feature rows (coalesced
+// 256-byte reads; the image row is read again per class, from cache).  Sums in fp64: each lane adds its columns in order, then
+// the xor butterfly, which leaves the same bits in every lane.  Lane a keeps class a's logit, so the row maximum, the softmax
+// sum and the mask are one value per lane; lanes from A on hold -inf / 0.  The softmax of the fp32 logits is evaluated in fp64
+// and rounded once, so what separates it from torch's fp32 evaluation of the same formula is torch's own rounding.
+__global__ __launch_bounds__(NT) void zeroshot_head_kernel(const float* __restrict__ img, int lda, const float* __restrict__ txt,
+                                                           int ldb, int B, int A, int D, float scale, float* __restrict__ probs,
+                                                           int* __restrict__ mask, const int* __restrict__ group,
+                                                           int* __restrict__ hits, int G) {
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * (NT / 64) + (threadIdx.x >> 6);
+    if (row >= B) return;                                   // whole waves leave: the shuffles below see full waves
+    const float* x = img + (long)row * lda;
+    double xx = 0.0;
+    for (int c = lane; c < D; c += 64) {
+        const double v = (double)x[c];
+        xx = fma(v, v, xx);
+    }
+    xx = wave_sum_d(xx);
+    float logit = -INFINITY;
+    for (int a = 0; a < A; ++a) {
+        const float* t = txt + (long)a * ldb;
+        double d = 0.0, tt = 0.0;
+        for (int c = lane; c < D; c += 64) {
+            const double v = (double)x[c], u = (double)t[c];
+            d = fma(v, u, d);
+            tt = fma(u, u, tt);
+        }
+        d = wave_sum_d(d);
+        tt = wave_sum_d(tt);
+        const double den = sqrt(xx) * sqrt(tt);
+        const double cs = den > 0.0 ? d / den : 0.0;
+        const float z = (float)((double)scale * cs);
+        if (lane == a) logit = z;
+    }
+    const float mx = wave_max(logit);
+    const double e = lane < A ? exp((double)(logit - mx)) : 0.0;      // the fp32 difference, as torch forms it
+    const double s = wave_sum_d(e);
+    if (lane < A) {
+        const int hit = logit == mx ? 1 : 0;
+        probs[(long)row * A + lane] = (float)(e / s);
+        mask[(long)row * A + lane] = hit;
+        if (hits && hit) {
+            const int g = group ? group[row] : 0;
+            if (g >= 0 && g < G) atomicAdd(&hits[(long)g * A + lane], 1);
+        }
+    }
+}
+
 }  // namespace
 
 extern "C" int pdmk_softmax_topk(const float* logits, int ld, int B, int N, int k, float* probs, int* idx, pdmk_stream stream) {
@@ -117,6 +168,19 @@ extern "C" int pdmk_softmax_topk(const float* logits, int ld, int B, int N, int 
     hipStream_t st = (hipStream_t)stream;
     if (N <= 64 * REG_E) hipLaunchKernelGGL(softmax_topk_kernel<true>, grid, dim3(NT), 0, st, logits, ld, B, N, k, probs, idx);
     else hipLaunchKernelGGL(softmax_topk_kernel<false>, grid, dim3(NT), 0, st, logits, ld, B, N, k, probs, idx);
+    PDMK_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int pdmk_zeroshot_head(const float* img, int lda, const float* txt, int ldb, int B, int A, int D, float scale,
+                                  float* probs, int* mask, const int* group, int* hits, int G, pdmk_stream stream) {
+    if (!img || !txt || !probs || !mask ||
+        (((uintptr_t)img | (uintptr_t)txt | (uintptr_t)probs | (uintptr_t)mask | (uintptr_t)group | (uintptr_t)hits) & 3) || B < 1 ||
+        B > 65535 || A < 1 || A > PDMK_ZEROSHOT_MAX_CLASSES || D < 1 || D > 4096 || lda < D || ldb < D || (hits && G < 1))
+        return -1;
+    const dim3 grid((unsigned)((B + NT / 64 - 1) / (NT / 64)));
+    hipLaunchKernelGGL(zeroshot_head_kernel, grid, dim3(NT), 0, (hipStream_t)stream, img, lda, txt, ldb, B, A, D, scale, probs,
+                       mask, group, hits, G);
     PDMK_CHECK_LAUNCH();
     return 0;
 }

@@ -4,6 +4,7 @@
 //   pdmk_spd_factor_f64 : blocked right-looking Cholesky A = L L^T in place, 64-wide panels, three launches per panel
 //   pdmk_spd_solve_f64  : X = B (L L^T)^-1 for the rows of B, forward then backward block substitution per block of 16 rows
 //   pdmk_uce_delta      : D = N - O (replace) or N - (1 + <O, N> / <O, O>) O per (pair, projection) block (tensor)
+//   pdmk_uce_debias_delta : D = sum_j c_j U_j per block, c_j from the debiasing recurrence on the block's Gram matrix
 //
 // Every triangular system against a 64 x 64 diagonal block is solved by substitution (one division per element), never by a
 // product with an explicit inverse: the componentwise error bounds of Cholesky factorisation and of the
@@ -318,6 +319,121 @@ __global__ void __launch_bounds__(NT) uce_delta_kernel(const float* __restrict__
     }
 }
 
+// ---------------------------------------------------------------------------------------------------- debias delta
+constexpr int DA = PDMK_DEBIAS_MAX_ATTR;
+constexpr int DV = DA + 1;                 // vectors of a block: O, then the attributes
+constexpr int DG = DV * (DV + 1) / 2;      // their dot products, (a, b) with a <= b at a DV - a (a - 1) / 2 + b - a
+
+// One workgroup per block (pair p, projection q).  Thread t takes the block's elements t, t + 256, ... in row-major order and
+// adds the products of the (A + 1) values there to its (A + 1)(A + 2) / 2 fp64 sums (a product of two fp32 values is exact in
+// fp64), then the wave butterfly and the four waves in order, as uce_dot_kernel.  Thread 0 then runs the recurrence
+//   c_j = w[p][j] sqrt(t^T G t) / sqrt(G[j + 1][j + 1]),   t = (1, c_0 .. c_{j-1})
+// into ws[(p Q + q) A + j]; a zero U_j (the reference: NaN) gives c_j = 0.
+__global__ void __launch_bounds__(NT) debias_coef_kernel(const float* __restrict__ O, const float* __restrict__ U, long ustride,
+                                                         int ld, int A, const float* __restrict__ w,
+                                                         const int32_t* __restrict__ row_seg, const int32_t* __restrict__ col_seg,
+                                                         int Q, double* __restrict__ ws) {
+    __shared__ double red[DG][NT / 64];
+    __shared__ double G[DV][DV];
+    __shared__ double t[DV];
+    const int p = blockIdx.x / Q, q = blockIdx.x - p * Q;
+    const int r0 = row_seg[p], c0 = col_seg[q], wd = col_seg[q + 1] - c0;
+    const long cnt = (long)(row_seg[p + 1] - r0) * wd;
+    double acc[DG];
+#pragma unroll
+    for (int g = 0; g < DG; ++g) acc[g] = 0.0;
+    for (long e = threadIdx.x; e < cnt; e += NT) {
+        const long r = e / wd;
+        const long at = (r0 + r) * ld + c0 + (e - r * wd);
+        double v[DV];
+        v[0] = (double)O[at];
+#pragma unroll
+        for (int j = 0; j < DA; ++j) v[j + 1] = j < A ? (double)U[j * ustride + at] : 0.0;
+#pragma unroll
+        for (int a = 0; a < DV; ++a)
+#pragma unroll
+            for (int b = a; b < DV; ++b)
+                if (b <= A) acc[a * DV - a * (a - 1) / 2 + b - a] = fma(v[a], v[b], acc[a * DV - a * (a - 1) / 2 + b - a]);
+    }
+#pragma unroll
+    for (int a = 0; a < DV; ++a)
+#pragma unroll
+        for (int b = a; b < DV; ++b)
+            if (b <= A) {
+                const int g = a * DV - a * (a - 1) / 2 + b - a;
+                const double s = wave_sum_d(acc[g]);
+                if ((threadIdx.x & 63) == 0) red[g][threadIdx.x >> 6] = s;
+            }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int a = 0; a <= A; ++a)
+            for (int b = a; b <= A; ++b) {
+                const int g = a * DV - a * (a - 1) / 2 + b - a;
+                G[a][b] = G[b][a] = ((red[g][0] + red[g][1]) + red[g][2]) + red[g][3];
+            }
+        t[0] = 1.0;
+        for (int j = 0; j < A; ++j) {
+            double n2 = 0.0;
+            for (int a = 0; a <= j; ++a)
+                for (int b = 0; b <= j; ++b) n2 = fma(t[a] * t[b], G[a][b], n2);
+            const double uu = G[j + 1][j + 1];
+            const double c = uu > 0.0 ? (double)w[(long)p * A + j] * sqrt(fmax(n2, 0.0)) / sqrt(uu) : 0.0;
+            t[j + 1] = c;
+            ws[(long)blockIdx.x * A + j] = c;
+        }
+    }
+}
+
+// grid (Q, P + 1): block (q, p < P) writes D = fp32(sum_j c_j U_j) over its block, the sum in fp64 in the order of j; row
+// block P is the padding [row_seg[P], m), written as zeros.  vec: U, D and ld allow 16-byte accesses; a block uses them when
+// its first column and width are multiples of 4 as well.
+__global__ void __launch_bounds__(NT) debias_delta_kernel(const float* __restrict__ U, long ustride, float* __restrict__ D, int m,
+                                                          int ld, int A, const int32_t* __restrict__ row_seg, int P,
+                                                          const int32_t* __restrict__ col_seg, int Q, const double* __restrict__ ws,
+                                                          int vec) {
+    const int p = blockIdx.y, q = blockIdx.x;
+    const bool pad = p == P;
+    const int r0 = row_seg[p], r1 = pad ? m : row_seg[p + 1];
+    const int c0 = col_seg[q], wd = col_seg[q + 1] - c0;
+    double c[DA];
+#pragma unroll
+    for (int j = 0; j < DA; ++j) c[j] = (!pad && j < A) ? ws[((long)p * Q + q) * A + j] : 0.0;
+    if (vec && ((c0 | wd) & 3) == 0) {
+        const int w4 = wd >> 2;
+        const long cnt = (long)(r1 - r0) * w4;
+        for (long e = threadIdx.x; e < cnt; e += NT) {
+            const long r = e / w4;
+            const long at = (r0 + r) * ld + c0 + 4 * (e - r * w4);
+            double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
+            if (!pad) {
+#pragma unroll
+                for (int j = 0; j < DA; ++j)
+                    if (j < A) {
+                        const float4 u = *reinterpret_cast<const float4*>(U + j * ustride + at);
+                        s0 = fma(c[j], (double)u.x, s0);
+                        s1 = fma(c[j], (double)u.y, s1);
+                        s2 = fma(c[j], (double)u.z, s2);
+                        s3 = fma(c[j], (double)u.w, s3);
+                    }
+            }
+            *reinterpret_cast<float4*>(D + at) = make_float4((float)s0, (float)s1, (float)s2, (float)s3);
+        }
+        return;
+    }
+    const long cnt = (long)(r1 - r0) * wd;
+    for (long e = threadIdx.x; e < cnt; e += NT) {
+        const long r = e / wd;
+        const long at = (r0 + r) * ld + c0 + (e - r * wd);
+        double s = 0.0;
+        if (!pad) {
+#pragma unroll
+            for (int j = 0; j < DA; ++j)
+                if (j < A) s = fma(c[j], (double)U[j * ustride + at], s);
+        }
+        D[at] = (float)s;
+    }
+}
+
 }  // namespace
 
 extern "C" int64_t pdmk_spd_workspace_elems(int n, int m) {
@@ -373,6 +489,25 @@ extern "C" int pdmk_uce_delta(const float* O, const float* N, float* D, int m, i
         hipLaunchKernelGGL(uce_dot_kernel, dim3((unsigned)P * (unsigned)Q), dim3(NT), 0, st, O, N, ld, row_seg, col_seg, Q, ws);
     hipLaunchKernelGGL(uce_delta_kernel, dim3(Q, P + 1), dim3(NT), 0, st, O, N, D, m, ld, row_seg, P, col_seg, Q,
                        technique == 1 ? ws : nullptr);
+    PDMK_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int pdmk_uce_debias_delta(const float* O, const float* U, float* D, int m, int ld, int A, const float* w,
+                                     const int32_t* row_seg, int P, const int32_t* col_seg, int Q, double* ws, int64_t ws_elems,
+                                     pdmk_stream s) {
+    const uintptr_t words = (uintptr_t)O | (uintptr_t)U | (uintptr_t)D | (uintptr_t)w | (uintptr_t)row_seg | (uintptr_t)col_seg;
+    if (!O || !U || !D || !w || !row_seg || !col_seg || !ws || m < 1 || ld < 1 || P < 1 || Q < 1 || P > 65534 || A < 1 ||
+        A > PDMK_DEBIAS_MAX_ATTR || (words & 3) || ((uintptr_t)ws & 7) || (int64_t)P * Q > 0x7fffffffLL ||
+        ws_elems < (int64_t)P * Q * A)
+        return -1;
+    hipStream_t st = (hipStream_t)s;
+    const long ustride = (long)m * ld;
+    const int vec = (ld & 3) == 0 && (((uintptr_t)U | (uintptr_t)D) & 15) == 0;
+    hipLaunchKernelGGL(debias_coef_kernel, dim3((unsigned)P * (unsigned)Q), dim3(NT), 0, st, O, U, ustride, ld, A, w, row_seg,
+                       col_seg, Q, ws);
+    hipLaunchKernelGGL(debias_delta_kernel, dim3(Q, P + 1), dim3(NT), 0, st, U, ustride, D, m, ld, A, row_seg, P, col_seg, Q, ws,
+                       vec);
     PDMK_CHECK_LAUNCH();
     return 0;
 }

@@ -146,6 +146,7 @@ _SIGS = {
     "pdmk_conv2d_fwd": ([vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp], i32),
     "pdmk_conv2d_fwd_res": ([vp, i32, vp, vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp], i32),
     "pdmk_softmax_topk": ([vp, i32, i32, i32, i32, vp, vp, vp], i32),
+    "pdmk_zeroshot_head": ([vp, i32, vp, i32, i32, i32, i32, f32, vp, vp, vp, vp, i32, vp], i32),
     "pdmk_pool2d": ([vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp], i32),
     "pdmk_global_avgpool": ([vp, i32, vp, i32, i32, i32, vp], i32),
     "pdmk_fid_accumulate": ([vp, i32, i32, i32, vp, vp, vp], i32),
@@ -162,6 +163,7 @@ _SIGS = {
     "pdmk_spd_factor_f64": ([vp, i32, i32, vp, vp], i32),
     "pdmk_spd_solve_f64": ([vp, i32, i32, vp, i32, i32, vp, i32, vp, i32, vp, i64, vp], i32),
     "pdmk_uce_delta": ([vp, vp, vp, i32, i32, vp, i32, vp, i32, i32, vp, vp], i32),
+    "pdmk_uce_debias_delta": ([vp, vp, vp, i32, i32, i32, vp, vp, i32, vp, i32, vp, i64, vp], i32),
     "pdmk_gemm_splitk_workspace_bytes": ([i64, i32, i32], i64),
     "pdmk_groupnorm_workspace_bytes": ([i32, i32], i64),
     "pdmk_groupnorm_bwd_part_workspace_bytes": ([i32, i32], i64),
@@ -1421,3 +1423,65 @@ def uce_delta(O, N, D, row_seg, col_seg, technique):
     ws = torch.empty(2 * P * Q, device=O.device, dtype=torch.float64) if technique == 1 else None
     _chk(_lib.pdmk_uce_delta(_p(O), _p(N), _p(D), m, ld, _p(seg), P, _p(seg[P + 1:]), Q, int(technique), _p(ws), _st()),
          "pdmk_uce_delta")
+
+
+DEBIAS_MAX_ATTR = 8
+
+
+def uce_debias_delta(O, U, D, w, row_seg, col_seg):
+    """D = sum_j c_j U[j] per (pair, projection) block with the debiasing recurrence's c_j (include/pdmk.h
+    pdmk_uce_debias_delta): O, D fp32 [m, w] views of one row stride, U fp32 [A, m, w] with that row stride and attribute stride
+    m * ld, w fp32 [P, A] on the device; row_seg / col_seg: host lists of P + 1 first rows / Q + 1 first columns.  Rows from
+    row_seg[-1] on are zeroed."""
+    m, ld = O.shape[0], O.stride(0)
+    for t in (O, D):
+        if t.dtype != torch.float32 or t.dim() != 2 or t.shape != O.shape or t.stride() != O.stride() or t.stride(1) != 1:
+            raise PdmkError("uce_debias_delta: O, D must be fp32 [m, w] views of one shape and row stride")
+    A = U.shape[0] if U.dim() == 3 else 0
+    if (U.dtype != torch.float32 or U.dim() != 3 or not 1 <= A <= DEBIAS_MAX_ATTR or tuple(U.shape[1:]) != tuple(O.shape)
+            or U.stride() != (m * ld, ld, 1)):
+        raise PdmkError(f"uce_debias_delta: U must be fp32 [A, m, w] with strides (m ld, ld, 1), 1 <= A <= {DEBIAS_MAX_ATTR}")
+    row_seg, col_seg = [int(v) for v in row_seg], [int(v) for v in col_seg]
+    P, Q = len(row_seg) - 1, len(col_seg) - 1
+    if (P < 1 or Q < 1 or P > 65534 or any(b < a for a, b in zip(row_seg, row_seg[1:]))
+            or any(b < a for a, b in zip(col_seg, col_seg[1:])) or row_seg[0] < 0 or col_seg[0] < 0 or row_seg[-1] > m
+            or col_seg[-1] > O.shape[1]):
+        raise PdmkError(f"uce_debias_delta: segments must ascend inside [0, {m}] x [0, {O.shape[1]}]")
+    if w.dtype != torch.float32 or tuple(w.shape) != (P, A) or not w.is_contiguous() or w.device != O.device:
+        raise PdmkError(f"uce_debias_delta: w must be contiguous fp32 [{P}, {A}] on the matrices' device")
+    seg = torch.tensor(row_seg + col_seg, dtype=torch.int32).to(O.device)
+    ws = torch.empty(P * Q * A, device=O.device, dtype=torch.float64)
+    _chk(_lib.pdmk_uce_debias_delta(_p(O), _p(U), _p(D), m, ld, A, _p(w), _p(seg), P, _p(seg[P + 1:]), Q, _p(ws), ws.numel(),
+                                    _st()), "pdmk_uce_debias_delta")
+
+
+ZEROSHOT_MAX_CLASSES = 64
+
+
+def zeroshot_head(img, txt, scale, probs=None, mask=None, group=None, hits=None):
+    """CLIP zero-shot head (include/pdmk.h pdmk_zeroshot_head): img fp32 [B, D], txt fp32 [A, D] (unit column stride, a row
+    stride >= D), scale the host's fp32 exp(logit_scale) -> (probs fp32 [B, A], mask int32 [B, A]).  hits int32 [G, A]
+    (contiguous, accumulated into) and group int32 [B] on the device (None: every row counts in hits[0]) are optional."""
+    def rows(t):
+        return t.dtype == torch.float32 and t.dim() == 2 and t.stride(1) == 1 and t.stride(0) >= t.shape[1]
+    if not rows(img) or not rows(txt) or img.shape[1] != txt.shape[1] or txt.device != img.device:
+        raise PdmkError("zeroshot_head: img fp32 [B, D], txt fp32 [A, D], unit column stride, row stride >= D, one device")
+    (B, D), A = img.shape, txt.shape[0]
+    if not (1 <= B <= 65535 and 1 <= A <= ZEROSHOT_MAX_CLASSES and 1 <= D <= 4096):
+        raise PdmkError(f"zeroshot_head: B = {B}, A = {A}, D = {D} outside 1 .. 65535, 1 .. {ZEROSHOT_MAX_CLASSES}, 1 .. 4096")
+    probs = torch.empty((B, A), device=img.device, dtype=torch.float32) if probs is None else probs
+    mask = torch.empty((B, A), device=img.device, dtype=torch.int32) if mask is None else mask
+    if (probs.dtype != torch.float32 or mask.dtype != torch.int32 or tuple(probs.shape) != (B, A) or tuple(mask.shape) != (B, A)
+            or not probs.is_contiguous() or not mask.is_contiguous()):
+        raise PdmkError("zeroshot_head: probs fp32 [B, A], mask int32 [B, A], both contiguous")
+    G = 0
+    if hits is not None:
+        if hits.dtype != torch.int32 or hits.dim() != 2 or hits.shape[1] != A or not hits.is_contiguous() or hits.shape[0] < 1:
+            raise PdmkError(f"zeroshot_head: hits must be contiguous int32 [G, {A}]")
+        G = hits.shape[0]
+    if group is not None and (hits is None or group.dtype != torch.int32 or tuple(group.shape) != (B,) or not group.is_contiguous()
+                              or group.device != img.device):
+        raise PdmkError(f"zeroshot_head: group must be contiguous int32 [{B}] on the device, with hits")
+    _chk(_lib.pdmk_zeroshot_head(_p(img), img.stride(0), _p(txt), txt.stride(0), B, A, D, float(scale), _p(probs), _p(mask),
+                                 _p(group), _p(hits), G, _st()), "pdmk_zeroshot_head")
+    return probs, mask

@@ -14,8 +14,9 @@ block, D comes from pdmk_uce_delta and the update is one more GEMM on that matri
 
 Host side (no GPU needed): the text-list builders, the checkpoint name, the slice arithmetic.  GPU side: `edit_model`.
 
-Not built: train_debias.py (a loop of generation and CLIP classification), the eval-scripts other than generate-images.py,
-lpips_eval.py and styleloss.py (those three: pdm/utils/perceptual.py), `layers_to_edit` (the reference's
+Built elsewhere: train_debias.py (a loop of generation, CLIP classification and this edit with other targets) and
+CLIP_classify.py in pdm/utils/uce_debias.py; generate-images.py, lpips_eval.py and styleloss.py in pdm/utils/perceptual.py;
+imageclassify.py in pdm/utils/object_erasure.py.  Not built: the NudeNet-based eval-scripts, `layers_to_edit` (the reference's
 __main__ never sets it), SD-1.4, and the fixed concept lists `allartist`, `i2g`, `10artists`, `imagenette`.
 """
 import random
