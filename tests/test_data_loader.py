@@ -140,3 +140,45 @@ def test_random_draws_do_not_depend_on_the_worker_count(tmp_path):
     tops_lefts = torch.cat([d[:, 5:7] for _, d, _ in runs[0]])
     assert 0 < int(flips.sum()) < flips.numel()         # both flip outcomes are drawn
     assert int(tops_lefts.max()) > 0
+
+
+def test_shared_packer_layout():
+    """pack_images on images of 0, 1, 2 and 3 bytes mod 4: word-aligned offsets, zero gaps and spare word, the head equal to
+    the descriptors; the CLIP and FID packers are this packer with their geometry."""
+    from pdm.utils import clip_utils, fid_utils
+    from pdm.utils.data import DESC_BYTES, center_crop_origin, pack_images, resized_size
+    rng = np.random.default_rng(0)
+    shapes = [(1, 1), (1, 3), (2, 3), (4, 4)]                                   # 3, 9, 18, 48 bytes
+    arrays = [rng.integers(1, 256, (h, w, 3), dtype=np.uint8) for h, w in shapes]
+    assert sorted(a.size % 4 for a in arrays) == [0, 1, 2, 3]
+    rows = [[h, w, 10 + i, 20 + i, i, 2 * i, i % 2] for i, (h, w) in enumerate(shapes)]
+    packed, desc = pack_images(arrays, rows)
+    assert packed.dtype == torch.uint8 and desc.dtype == torch.int64 and tuple(desc.shape) == (4, 8)
+    assert desc[:, 0].tolist() == [0, 4, 16, 36] and desc[:, 1:].tolist() == rows
+    head = 4 * DESC_BYTES
+    assert packed.numel() == head + 36 + 48 + 4
+    buf = packed.numpy()
+    assert buf[:head].view(np.int64).reshape(4, 8).tolist() == desc.tolist()
+    used = np.zeros(buf.size, bool)
+    used[:head] = True
+    for o, a in zip(desc[:, 0].tolist(), arrays):
+        assert o % 4 == 0 and np.array_equal(buf[head + o:head + o + a.size], a.reshape(-1))
+        used[head + o:head + o + a.size] = True
+    assert (~used).sum() == 1 + 3 + 2 + 0 + 4 and not buf[~used].any()         # the gaps and the spare word
+    # a geometry callable gives the same rows
+    same, d2 = pack_images(arrays, lambda h, w: (h + 1, w + 2, 3, 4, 1))
+    assert d2[:, 1:].tolist() == [[h, w, h + 1, w + 2, 3, 4, 1] for h, w in shapes] and torch.equal(same[head:], packed[head:])
+    # the named wrappers
+    for R in (2, 5):
+        want = pack_images(arrays, [[h, w, *resized_size(h, w, R), *center_crop_origin(*resized_size(h, w, R), R), 0] for h, w in shapes])
+        got = clip_utils.pack_images(arrays, R)
+        assert torch.equal(got[0], want[0]) and torch.equal(got[1], want[1])
+    want = pack_images(arrays, [[h, w, h, w, 0, 0, 0] for h, w in shapes])
+    got = fid_utils.pack_images(arrays)
+    assert torch.equal(got[0], want[0]) and torch.equal(got[1], want[1])
+    # no images: descriptors [0, 8] and the spare word alone; anything but uint8 [H, W, 3] is refused
+    packed, desc = pack_images([], [])
+    assert tuple(desc.shape) == (0, 8) and packed.tolist() == [0, 0, 0, 0]
+    for bad in (np.zeros((2, 2), np.uint8), np.zeros((2, 2, 4), np.uint8), np.zeros((2, 2, 3), np.float32)):
+        with pytest.raises(ValueError):
+            pack_images([bad], lambda h, w: (h, w, 0, 0, 0))

@@ -13,6 +13,7 @@ SCRIPTS = os.path.join(ROOT, "unlearn-ft_amd", "scripts", "metrics")
 GOLDEN = os.path.join(ROOT, "tests", "golden", "fid_frechet.npz")
 sys.path.insert(0, SCRIPTS)
 
+from pdm.models import convnet  # noqa: E402
 from pdm.models.inception import spec  # noqa: E402
 from pdm.utils import fid_utils as fu  # noqa: E402
 
@@ -65,7 +66,7 @@ def test_fold_batchnorm_matches_eval_batchnorm(shape, stride, pad):
     var = torch.rand(co, generator=g, dtype=torch.float64) + 0.05
     x = torch.randn(2, shape[1], 11, 11, generator=g, dtype=torch.float64)
     ref = F.batch_norm(F.conv2d(x, w, None, stride, pad), mean, var, gamma, beta, False, 0.0, 1e-3)
-    wf, bf = spec.fold_batchnorm(w, gamma, beta, mean, var)
+    wf, bf = convnet.fold_batchnorm(w, gamma, beta, mean, var, spec.BN_EPS)
     got = F.conv2d(x, wf, bf, stride, pad)
     assert (got - ref).abs().max() <= 1e-12 * ref.abs().max()
 
@@ -74,7 +75,7 @@ def test_fold_batchnorm_matches_eval_batchnorm(shape, stride, pad):
 def test_unit_table_counts_and_names():
     units = spec.build_units()
     assert len(units) == 94
-    assert sum(u.numel for u in units) == 21_785_568
+    assert sum(u.co * u.k + 2 * u.co for u in units) == 21_785_568       # conv weight + BatchNorm weight and bias
     shapes = spec.state_dict_shapes()
     assert len(shapes) == 564
     assert shapes["Conv2d_1a_3x3.conv.weight"] == (32, 3, 3, 3)
@@ -116,23 +117,28 @@ def _state_dict():
     return sd
 
 
+def _checked_trunk(sd):
+    """What InceptionV3FID.load_state_dict checks."""
+    return convnet.checked(sd, spec.state_dict_shapes(num_batches_tracked=False), "Inception", spec.ignored)
+
+
 def test_state_dict_contract():
     sd = _state_dict()
     assert len([n for n in sd if not n.startswith(("fc.", "AuxLogits."))]) == 564
-    trunk = spec.checked_trunk(sd)
+    trunk = _checked_trunk(sd)
     assert len(trunk) == 94 * 5 and not any("num_batches_tracked" in n or n.startswith("fc.") for n in trunk)
     missing = dict(sd)
     del missing["Mixed_6c.branch7x7_2.bn.running_mean"]
     with pytest.raises(KeyError, match="Mixed_6c.branch7x7_2.bn.running_mean"):
-        spec.checked_trunk(missing)
+        _checked_trunk(missing)
     bad = dict(sd)
     bad["Mixed_7a.branch3x3_2.conv.weight"] = torch.zeros(320, 192, 3, 1)
     with pytest.raises(ValueError, match="Mixed_7a.branch3x3_2.conv.weight"):
-        spec.checked_trunk(bad)
+        _checked_trunk(bad)
     extra = dict(sd)
     extra["Mixed_8a.conv.weight"] = torch.zeros(1)
     with pytest.raises(KeyError):
-        spec.checked_trunk(extra)
+        _checked_trunk(extra)
 
 
 def test_from_pretrained_missing_file_names_the_path(tmp_path):

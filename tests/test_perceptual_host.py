@@ -12,6 +12,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import perceptual_fixtures as fx  # noqa: E402
 
+from pdm.models.convnet import checked
 from pdm.models.perceptual import spec as S
 from pdm.utils import perceptual as P
 
@@ -53,11 +54,11 @@ def test_state_dict_tables():
     assert S.conv_shapes(S.VGG_UNITS)["features.10.weight"] == (256, 128, 3, 3)
     assert list(S.lin_shapes()) == [f"lin{i}.model.1.weight" for i in range(5)] and S.lin_shapes()["lin1.model.1.weight"] == (1, 192, 1, 1)
     sd = fx.vgg_state_dict()
-    assert sorted(S.checked(sd, S.conv_shapes(S.VGG_UNITS), "VGG-19")) == sorted(n for n in sd if not n.startswith("features.12"))
+    assert sorted(checked(sd, S.conv_shapes(S.VGG_UNITS), "VGG-19")) == sorted(n for n in sd if not n.startswith("features.12"))
     with pytest.raises(KeyError, match=r"features\.7\.bias"):
-        S.checked({n: t for n, t in sd.items() if n != "features.7.bias"}, S.conv_shapes(S.VGG_UNITS), "VGG-19")
+        checked({n: t for n, t in sd.items() if n != "features.7.bias"}, S.conv_shapes(S.VGG_UNITS), "VGG-19")
     with pytest.raises(ValueError, match=r"features\.0\.weight"):
-        S.checked(dict(sd, **{"features.0.weight": torch.zeros(64, 3, 5, 5)}), S.conv_shapes(S.VGG_UNITS), "VGG-19")
+        checked(dict(sd, **{"features.0.weight": torch.zeros(64, 3, 5, 5)}), S.conv_shapes(S.VGG_UNITS), "VGG-19")
     mean, std = S.lpips_input_norm()
     x = np.linspace(0, 1, 7)
     for c in range(3):        # the composed Normalize of the [0, 1] image is the ScalingLayer of the [-1, 1] image
@@ -65,12 +66,12 @@ def test_state_dict_tables():
 
 
 def test_missing_weights_say_what_to_place_where(tmp_path):
-    from pdm.models.perceptual import nets
+    from pdm.models import convnet
     with pytest.raises(FileNotFoundError) as e:
-        nets._load_file(str(tmp_path / "nope.pth"), S.VGG_WEIGHTS_NAME, "--vgg_weights", "torchvision VGG-19")
+        convnet.load_weights_file(str(tmp_path / "nope.pth"), S.VGG_WEIGHTS_NAME, "--vgg_weights", "torchvision VGG-19")
     msg = str(e.value)
     assert str(tmp_path / "nope.pth") in msg and "vgg19-dcbb9e9d.pth" in msg and "--vgg_weights" in msg and "nothing is downloaded" in msg
-    assert nets.hub_checkpoint("alex.pth").endswith(os.path.join(".cache", "torch", "hub", "checkpoints", "alex.pth"))
+    assert convnet.hub_checkpoint("alex.pth").endswith(os.path.join(".cache", "torch", "hub", "checkpoints", "alex.pth"))
 
 
 def test_non_square_image_is_refused_by_name(tmp_path):

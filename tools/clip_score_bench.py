@@ -39,6 +39,7 @@ def main():
     from pdm.models.clip.clip_model import CLIPModel
     from pdm.models.clip.convert import TEXT_DEFAULTS, VISION_DEFAULTS
     from pdm.utils.clip_utils import clip_score, pack_images
+    from pdm.utils.data import upload
     dev = torch.device("cuda:0")
     lines = [f"# tools/clip_score_bench.py on one {torch.cuda.get_device_properties(0).gcnArchName.split(':')[0]}; "
              f"ViT-B/32 shapes, random weights"]
@@ -46,10 +47,9 @@ def main():
     rng = np.random.default_rng(0)
     arrays = [rng.integers(0, 256, (512, 512, 3), dtype=np.uint8) for _ in range(B)]
     packed, desc = pack_images(arrays, 224)
-    buf = packed.to(dev)
-    head = B * 64
+    src, dev_desc = upload(packed, B, dev)
     pix = torch.empty(B, 3, 224, 224, device=dev)
-    ms = timed(lambda: _pdmk.image_prep_ex(buf[head:], desc, buf[:head].view(torch.int64), pix, filter=1))
+    ms = timed(lambda: _pdmk.image_prep_ex(src, desc, dev_desc, pix, filter=1))
     lines.append(f"bicubic prep 64 x 512^2 -> 224: {ms:.3f} ms ({B / ms * 1e3:.0f} images/s)")
     models = {}
     for name, dt in (("fp32", torch.float32), ("bf16", torch.bfloat16)):

@@ -103,22 +103,21 @@ def main():
                                    seed=0, random_flip=True)
         hb = next(iter(ld1))
         B = hb["image_desc"].shape[0]
-        buf = hb["packed"].to(dev)
-        head = B * D.DESC_BYTES
+        src, dev_desc = D.upload(hb["packed"], B, dev)
         out = torch.empty(B, 3, args.res, args.res, device=dev)
         for _ in range(5):
-            _pdmk.image_prep(buf[head:], hb["image_desc"], buf[:head].view(torch.int64), out)
+            _pdmk.image_prep(src, hb["image_desc"], dev_desc, out)
         reps = 50
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         torch.cuda.synchronize()
         e0.record()
         for _ in range(reps):
-            _pdmk.image_prep(buf[head:], hb["image_desc"], buf[:head].view(torch.int64), out)
+            _pdmk.image_prep(src, hb["image_desc"], dev_desc, out)
         e1.record()
         torch.cuda.synchronize()
         ms = e0.elapsed_time(e1) / reps
-        moved = buf.numel() - head + out.numel() * 4
-        print(json.dumps({"what": "kernel", "batch": B, "res": args.res, "ms": round(ms, 4), "MB_in": round((buf.numel() - head) / 1e6, 2),
+        moved = src.numel() + out.numel() * 4
+        print(json.dumps({"what": "kernel", "batch": B, "res": args.res, "ms": round(ms, 4), "MB_in": round(src.numel() / 1e6, 2),
                           "MB_out": round(out.numel() * 4 / 1e6, 2), "GB_per_s": round(moved / ms / 1e6, 1)}), flush=True)
 
 

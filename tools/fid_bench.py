@@ -41,6 +41,7 @@ def main():
     from pdm import _pdmk as k
     from pdm.models.inception.inception_v3 import InceptionV3FID
     from pdm.utils import fid_utils as fu
+    from pdm.utils.data import upload
     import fid_fixtures as fx
     dev, B = torch.device("cuda:0"), args.batch
     lines = [f"device {torch.cuda.get_device_name(0)}, torch {torch.__version__}, batch {B}"]
@@ -52,9 +53,9 @@ def main():
     g = torch.Generator().manual_seed(0)
     imgs = [torch.randint(0, 256, (512, 512, 3), generator=g, dtype=torch.uint8).numpy() for _ in range(B)]
     packed, desc = fu.pack_images(imgs)
-    buf, head = packed.to(dev), B * 64
+    src, dev_desc = upload(packed, B, dev)
     x = torch.empty(B, 299, 299, 3, device=dev)
-    ms = timed(lambda: k.resize_bilinear_u8(buf[head:], desc, buf[:head].view(torch.int64), x))
+    ms = timed(lambda: k.resize_bilinear_u8(src, desc, dev_desc, x))
     say(f"pdmk_resize_bilinear_u8 {B} x 512^2 -> 299^2: {ms:.3f} ms ({(B * 512 * 512 * 3 + x.numel() * 4) / ms / 1e6:.0f} GB/s of image bytes in + floats out)")
 
     sd = fx.seeded_state_dict(0)

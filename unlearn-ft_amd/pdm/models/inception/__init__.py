@@ -1,4 +1,5 @@
-from .spec import ConvUnit, build_units, state_dict_shapes, fold_batchnorm  # noqa: F401
+from ..convnet import ConvUnit, fold_batchnorm  # noqa: F401
+from .spec import build_units, state_dict_shapes  # noqa: F401
 
 
 def __getattr__(name):          # the model itself needs the GPU library's host side; the table above does not

@@ -1,19 +1,18 @@
 """`InceptionV3FID`: pytorch-fid's `InceptionV3(output_blocks=[3])` on libpdmk - the feature extractor of clean-fid's
-`legacy_pytorch` FID (pdm/utils/fid_utils.py).  fp32, inference only, NHWC.
+`legacy_pytorch` FID (pdm/utils/fid_utils.py).  fp32, inference only, NHWC; a `ConvTrunk` (pdm/models/convnet.py).
 
-Every unit is one pdmk_conv2d_fwd launch (implicit GEMM on exact-fp32 MFMA, BatchNorm folded into weight and bias in
-float64 on the host, ReLU in the epilogue); the 1x1 units go through the same kernel, so they get the fused ReLU and the
-column-slice output too.  A Mixed block allocates its output [B * H * W, C_out] once and every branch's last unit writes
-its column slice of it (row stride C_out): no concat copies.  Pools are pdmk_pool2d (the branch_pool average divides by
-the taps inside the image; Mixed_7c's branch_pool is a max pool - the FID network's deviations from torchvision's), the
-head is pdmk_global_avgpool over the 8 x 8 map.  Launches are eager on the current stream.
+Every unit is one pdmk_conv2d_fwd launch (BatchNorm folded into weight and bias in float64 on the host, ReLU in the
+epilogue); the 1x1 units go through the same kernel, so they get the fused ReLU and the column-slice output too.  A Mixed
+block allocates its output [B * H * W, C_out] once and every branch's last unit writes its column slice of it (row stride
+C_out): no concat copies.  Pools are pdmk_pool2d (the branch_pool average divides by the taps inside the image; Mixed_7c's
+branch_pool is a max pool - the FID network's deviations from torchvision's), the head is pdmk_global_avgpool over the
+8 x 8 map.
 """
-import os
-
 import torch
 
 from ... import _pdmk as k
-from .spec import build_units, checked_trunk, fold_batchnorm, init_state_dict
+from ..convnet import ConvTrunk, Map, checked, fold_unit, hub_checkpoint, load_weights_file
+from . import spec as S
 
 WEIGHTS_NAME = "pt_inception-2015-12-05-6726825d.pth"
 INPUT_SIZE = 299
@@ -22,75 +21,36 @@ FEATURE_DIM = 2048
 
 def default_weights_path():
     """Where torch hub keeps pytorch-fid's / clean-fid's Inception weights."""
-    return os.path.join(os.path.expanduser("~"), ".cache", "torch", "hub", "checkpoints", WEIGHTS_NAME)
+    return hub_checkpoint(WEIGHTS_NAME)
 
 
-class _Map:
-    """An NHWC activation: t is a 2-D view [B * H * W, C] of a buffer whose row stride may be wider than C."""
-
-    def __init__(self, t, B, H, W):
-        self.t, self.B, self.H, self.W, self.C, self.ld = t, B, H, W, t.shape[1], t.stride(0)
-
-
-class InceptionV3FID:
+class InceptionV3FID(ConvTrunk):
     def __init__(self, device=None, seed=0, init=True):
-        if not torch.cuda.is_available():
-            raise RuntimeError("InceptionV3FID (MI355X engine) needs a GPU; there is no CPU fallback")
-        self.device = torch.device(device or "cuda:0")
-        self.units = {u.name: u for u in build_units()}
-        off, self.offsets = 0, {}
-        for u in self.units.values():                       # weight [Co, kh * kw * Ci] then bias [Co], each on a 512-byte line
-            self.offsets[u.name] = (off, off + (u.co * u.k + 127) // 128 * 128)
-            off = self.offsets[u.name][1] + (u.co + 127) // 128 * 128
-        self.arena = torch.zeros(off, device=self.device, dtype=torch.float32)
+        super().__init__(device, S.build_units())
         if init:
-            self.load_state_dict(init_state_dict(seed))
+            self.load_state_dict(S.init_state_dict(seed))
 
     @classmethod
     def from_pretrained(cls, path=None, device=None):
         """The weights file given, else torch hub's cache; never fetched."""
-        path = path or default_weights_path()
-        if not os.path.isfile(path):
-            raise FileNotFoundError(f"Inception weights not found at {path}: place pytorch-fid's {WEIGHTS_NAME} there or pass "
-                                    f"--inception_weights FILE (nothing is downloaded)")
-        sd = torch.load(path, map_location="cpu", weights_only=True)
+        sd = load_weights_file(path, WEIGHTS_NAME, "--inception_weights", "pytorch-fid Inception")
         model = cls(device=device, init=False)
         model.load_state_dict(sd)
         return model
 
     def load_state_dict(self, sd):
         """pytorch-fid's keys; fc.*, AuxLogits.* and num_batches_tracked are ignored, a missing / mis-shaped trunk key raises."""
-        sd = checked_trunk(sd, list(self.units.values()))
+        units = list(self.units.values())
+        sd = checked(sd, S.state_dict_shapes(units, num_batches_tracked=False), "Inception", S.ignored)
         host = torch.zeros(self.arena.numel(), dtype=torch.float32)
-        for u in self.units.values():
-            n = u.name
-            w, b = fold_batchnorm(sd[f"{n}.conv.weight"], sd[f"{n}.bn.weight"], sd[f"{n}.bn.bias"], sd[f"{n}.bn.running_mean"],
-                                  sd[f"{n}.bn.running_var"])
-            wo, bo = self.offsets[n]
-            host[wo:wo + u.co * u.k] = w.permute(0, 2, 3, 1).reshape(-1).to(torch.float32)       # k = (ky, kx, ci)
-            host[bo:bo + u.co] = b.to(torch.float32)
+        for u in units:
+            self.fill_conv(host, u, *fold_unit(sd, *S.keys(u), S.BN_EPS))
         self.arena.copy_(host)
 
     # ------------------------------------------------------------------ ops
-    def _new(self, B, H, W, C):
-        return _Map(torch.empty((B * H * W, C), device=self.device, dtype=torch.float32), B, H, W)
-
     def conv(self, x, name, out=None):
-        u = self.units[name]
-        assert x.C == u.ci, (name, x.C, u.ci)
-        Ho, Wo = (x.H + 2 * u.ph - u.kh) // u.stride + 1, (x.W + 2 * u.pw - u.kw) // u.stride + 1
-        y = _Map(out, x.B, Ho, Wo) if out is not None else self._new(x.B, Ho, Wo, u.co)
-        assert y.C == u.co and y.t.shape[0] == x.B * Ho * Wo
-        wo, bo = self.offsets[name]
-        k.conv2d_fwd(x.t, x.ld, self.arena[wo:wo + u.co * u.k], self.arena[bo:bo + u.co], y.t, y.ld, x.B, x.H, x.W, u.ci, u.co,
-                     u.kh, u.kw, u.stride, u.ph, u.pw, relu=True)
-        return y
-
-    def pool(self, x, mode, stride, pad, out=None):
-        Ho, Wo = (x.H + 2 * pad - 3) // stride + 1, (x.W + 2 * pad - 3) // stride + 1
-        y = _Map(out, x.B, Ho, Wo) if out is not None else self._new(x.B, Ho, Wo, x.C)
-        k.pool2d(x.t, x.ld, y.t, y.ld, x.B, x.H, x.W, x.C, mode, stride, pad)
-        return y
+        """Every unit ends in a ReLU."""
+        return super().conv(x, name, True, out=out)
 
     def _chain(self, x, names, out):
         for n in names[:-1]:
@@ -100,7 +60,7 @@ class InceptionV3FID:
     def _mixed(self, x, n, widths, stride=1):
         """The block's output map and its column slices, one per entry of `widths`."""
         H, W = ((x.H - 3) // 2 + 1, (x.W - 3) // 2 + 1) if stride == 2 else (x.H, x.W)
-        y = self._new(x.B, H, W, sum(widths))
+        y = self.new_map(x.B, H, W, sum(widths))
         cols, c = [], 0
         for wd in widths:
             cols.append(y.t[:, c:c + wd])
@@ -155,7 +115,7 @@ class InceptionV3FID:
         """x fp32 [B, 299, 299, 3] in [-1, 1] on the device -> pool3 features [B, 2048] fp32."""
         B, H, W, C = x.shape
         assert C == 3 and x.dtype == torch.float32 and x.is_contiguous() and min(H, W) >= 75, tuple(x.shape)
-        m = _Map(x.reshape(B * H * W, 3), B, H, W)
+        m = Map(x.reshape(B * H * W, 3), B, H, W)
         for n in ("Conv2d_1a_3x3", "Conv2d_2a_3x3", "Conv2d_2b_3x3"):
             m = self.conv(m, n)
         m = self.pool(m, "max", 2, 0)

@@ -6,31 +6,11 @@ The three deviations of the FID network from torchvision's are in the forward pa
 branch_pool average of Mixed_5b/5c/5d, 6b-6e and 7b divides by the number of taps inside the image, Mixed_7c's branch_pool
 is a max pool, and `fc` (1008 outputs) / AuxLogits are never evaluated.
 """
-from dataclasses import dataclass
-
 import torch
 
+from ..convnet import ConvUnit, conv_bn_shapes
+
 BN_EPS = 1e-3
-
-
-@dataclass(frozen=True)
-class ConvUnit:
-    name: str       # state-dict prefix: <name>.conv.weight, <name>.bn.{weight,bias,running_mean,running_var,num_batches_tracked}
-    ci: int
-    co: int
-    kh: int = 1
-    kw: int = 1
-    stride: int = 1
-    ph: int = 0
-    pw: int = 0
-
-    @property
-    def k(self):
-        return self.kh * self.kw * self.ci
-
-    @property
-    def numel(self):            # trunk parameters of the unit: conv weight + BatchNorm weight and bias
-        return self.co * self.k + 2 * self.co
 
 
 def _u(name, ci, co, k=1, stride=1, pad=0):
@@ -91,39 +71,20 @@ def build_units():
     return units
 
 
+def keys(u):
+    """(conv prefix, BatchNorm prefix) of a unit: <name>.conv.weight, <name>.bn.{weight,bias,running_mean,running_var,
+    num_batches_tracked}."""
+    return f"{u.name}.conv", f"{u.name}.bn"
+
+
 def state_dict_shapes(units=None, num_batches_tracked=True):
     """{key: shape} of the trunk in pytorch-fid's / torchvision's naming (6 entries per unit with num_batches_tracked)."""
-    out = {}
-    for u in units or build_units():
-        out[f"{u.name}.conv.weight"] = (u.co, u.ci, u.kh, u.kw)
-        for s in ("weight", "bias", "running_mean", "running_var"):
-            out[f"{u.name}.bn.{s}"] = (u.co,)
-        if num_batches_tracked:
-            out[f"{u.name}.bn.num_batches_tracked"] = ()
-    return out
+    return conv_bn_shapes(units or build_units(), keys, num_batches_tracked)
 
 
-def fold_batchnorm(w, gamma, beta, mean, var, eps=BN_EPS):
-    """Eval-mode BatchNorm folded into the conv in float64: (w * g / sqrt(var + eps), beta - mean * g / sqrt(var + eps)),
-    both float64 (the caller rounds to fp32 once)."""
-    w, gamma, beta, mean, var = (t.detach().to(torch.float64).cpu() for t in (w, gamma, beta, mean, var))
-    s = gamma / torch.sqrt(var + eps)
-    return w * s.reshape(-1, 1, 1, 1), beta - mean * s
-
-
-def checked_trunk(sd, units=None):
-    """The trunk tensors of a pytorch-fid state dict: `fc.*`, `AuxLogits.*` and `num_batches_tracked` are ignored, a
-    missing or mis-shaped trunk key raises KeyError / ValueError naming it, any other key raises KeyError."""
-    want = state_dict_shapes(units, num_batches_tracked=False)
-    extra = [n for n in sd if n not in want and not n.startswith(("fc.", "AuxLogits.")) and not n.endswith("num_batches_tracked")]
-    if extra:
-        raise KeyError(f"unexpected keys in the Inception state dict: {sorted(extra)[:5]}")
-    for n, shape in want.items():
-        if n not in sd:
-            raise KeyError(f"missing key {n} in the Inception state dict")
-        if tuple(sd[n].shape) != tuple(shape):
-            raise ValueError(f"{n}: shape {tuple(sd[n].shape)}, expected {tuple(shape)}")
-    return {n: sd[n] for n in want}
+def ignored(key):
+    """The keys of a pytorch-fid state dict that the trunk does not use (convnet.checked raises on any other stray)."""
+    return key.startswith(("fc.", "AuxLogits.")) or key.endswith("num_batches_tracked")
 
 
 def init_state_dict(seed=0, units=None):

@@ -1,5 +1,5 @@
 """`AlexNetLPIPS` and `VGG19Style`: the two small trunks of the perceptual metrics on libpdmk, with their metric heads.
-fp32, inference only, NHWC; the pattern of pdm/models/inception: one weight arena, every conv one pdmk_conv2d_fwd launch
+fp32, inference only, NHWC; `ConvTrunk`s (pdm/models/convnet.py): one weight arena, every conv one pdmk_conv2d_fwd launch
 (exact-fp32 MFMA implicit GEMM), launches eager on the current stream, weights from files that are never fetched.
 
 Both take a batch of PAIRS as one batch of 2 B images (the B originals, then the B edited ones), so a tap is one buffer whose two
@@ -14,95 +14,43 @@ The input normalisation is NOT folded into the first conv: zero padding applies 
 be wrong on the border pixels.  pdmk_image_prep_ex normalises ((x - mean) / std of the [0, 1] image; for LPIPS the composed
 pair of spec.lpips_input_norm) and pdmk_nchw_to_nhwc lays the result out for the first conv.
 """
-import os
-
 import torch
 
 from ... import _pdmk as k
+from ..convnet import ConvTrunk, Map, checked, load_weights_file
 from . import spec as S
 
 
-def hub_checkpoint(name):
-    """Where torch hub keeps a downloaded checkpoint of that file name."""
-    return os.path.join(os.path.expanduser("~"), ".cache", "torch", "hub", "checkpoints", name)
-
-
-def _load_file(path, name, flag, source):
-    path = path or hub_checkpoint(name)
-    if not os.path.isfile(path):
-        raise FileNotFoundError(f"{source} weights not found at {path}: place {name} there or pass {flag} FILE "
-                                f"(nothing is downloaded)")
-    return torch.load(path, map_location="cpu", weights_only=True)
-
-
-class _Map:
-    """An NHWC activation: t is a 2-D view [B * H * W, C] of a buffer whose row stride may be wider than C."""
-
-    def __init__(self, t, B, H, W):
-        self.t, self.B, self.H, self.W, self.C, self.ld = t, B, H, W, t.shape[1], t.stride(0)
-
-
-class _Trunk:
-    """Conv weights [Co, kh * kw * Ci] (k = (ky, kx, ci)) and biases in one arena, each on a 512-byte line; `extra` = further
-    fp32 vectors {name: length} behind them."""
+class _Trunk(ConvTrunk):
+    """A trunk of conv + bias units under torchvision's `features.N.{weight,bias}`, run on a batch of pairs."""
     UNITS, WHAT = (), ""
 
     def __init__(self, device, extra=None):
-        if not torch.cuda.is_available():
-            raise RuntimeError(f"{type(self).__name__} (MI355X engine) needs a GPU; there is no CPU fallback")
-        self.device = torch.device(device or "cuda:0")
-        off, self.offsets = 0, {}
-        for u in self.UNITS:
-            self.offsets[u.name] = (off, off + (u.co * u.k + 127) // 128 * 128)
-            off = self.offsets[u.name][1] + (u.co + 127) // 128 * 128
-        for n, length in (extra or {}).items():
-            self.offsets[n] = off
-            off += (length + 127) // 128 * 128
-        self.arena = torch.zeros(off, device=self.device, dtype=torch.float32)
+        super().__init__(device, self.UNITS, extra)
 
     def _fill_convs(self, host, sd):
-        sd = S.checked(sd, S.conv_shapes(self.UNITS), self.WHAT)
+        sd = checked(sd, S.conv_shapes(self.UNITS), self.WHAT)
         for u in self.UNITS:
-            wo, bo = self.offsets[u.name]
-            host[wo:wo + u.co * u.k] = sd[f"{u.name}.weight"].detach().permute(0, 2, 3, 1).reshape(-1).to(torch.float32)
-            host[bo:bo + u.co] = sd[f"{u.name}.bias"].detach().to(torch.float32)
-
-    def conv(self, x, i, relu):
-        u = self.UNITS[i]
-        assert x.C == u.ci, (u.name, x.C, u.ci)
-        Ho, Wo = (x.H + 2 * u.ph - u.kh) // u.stride + 1, (x.W + 2 * u.pw - u.kw) // u.stride + 1
-        if Ho < 1 or Wo < 1:
-            raise ValueError(f"{type(self).__name__}: a {x.H} x {x.W} map is too small for {u.name}")
-        y = _Map(torch.empty((x.B * Ho * Wo, u.co), device=self.device, dtype=torch.float32), x.B, Ho, Wo)
-        wo, bo = self.offsets[u.name]
-        k.conv2d_fwd(x.t, x.ld, self.arena[wo:wo + u.co * u.k], self.arena[bo:bo + u.co], y.t, y.ld, x.B, x.H, x.W, u.ci, u.co,
-                     u.kh, u.kw, u.stride, u.ph, u.pw, relu=relu)
-        return y
+            self.fill_conv(host, u, sd[f"{u.name}.weight"], sd[f"{u.name}.bias"])
 
     def _input(self, x):
         B2, H, W, C = x.shape
         assert C == 3 and x.dtype == torch.float32 and x.is_contiguous() and B2 % 2 == 0, tuple(x.shape)
-        return _Map(x.reshape(B2 * H * W, 3), B2, H, W)
+        return Map(x.reshape(B2 * H * W, 3), B2, H, W)
 
     @torch.no_grad()
     def prep(self, images_a, images_b, imsize):
         """Two equally long lists of SQUARE uint8 [H, W, 3] arrays -> the normalised fp32 NHWC batch [2 B, imsize, imsize, 3]:
         Pillow's bilinear Resize(imsize) + ToTensor bit for bit (pdmk_image_prep_ex, filter 0), then this trunk's Normalize."""
-        from ...utils.clip_utils import DESC_BYTES, pack_images
+        from ...utils.clip_utils import pack_images
+        from ...utils.data import prep_nhwc
         arrays = list(images_a) + list(images_b)
         assert len(images_a) == len(images_b) and arrays
         for a in arrays:
             if a.ndim != 3 or a.shape[2] != 3 or a.dtype.name != "uint8" or a.shape[0] != a.shape[1]:
                 raise ValueError(f"expected square uint8 [H, W, 3] images, got {a.dtype} {a.shape}")
         packed, desc = pack_images(arrays, imsize)
-        n = len(arrays)
-        buf = packed.to(self.device, non_blocking=True)
-        head = n * DESC_BYTES
-        pix = torch.empty(n, 3, imsize, imsize, device=self.device)
-        k.image_prep_ex(buf[head:], desc, buf[:head].view(torch.int64), pix, filter=0, mean=self.MEAN, std=self.STD)
-        x = torch.empty(n, imsize, imsize, 3, device=self.device)
-        k.nchw_to_nhwc(pix, x, n, 3, imsize * imsize, 3)
-        return x
+        return prep_nhwc(packed, desc, imsize, self.device, 0, self.MEAN, self.STD)
 
 
 class AlexNetLPIPS(_Trunk):
@@ -118,8 +66,8 @@ class AlexNetLPIPS(_Trunk):
     @classmethod
     def from_pretrained(cls, alexnet_weights=None, lpips_weights=None, device=None):
         """torchvision's AlexNet checkpoint and lpips' v0.1 linear heads from the files given, else torch hub's cache."""
-        sd = _load_file(alexnet_weights, S.ALEX_WEIGHTS_NAME, "--alexnet_weights", "torchvision AlexNet")
-        lin = _load_file(lpips_weights, S.LPIPS_WEIGHTS_NAME, "--lpips_weights", "lpips v0.1 (weights/v0.1/alex.pth)")
+        sd = load_weights_file(alexnet_weights, S.ALEX_WEIGHTS_NAME, "--alexnet_weights", "torchvision AlexNet")
+        lin = load_weights_file(lpips_weights, S.LPIPS_WEIGHTS_NAME, "--lpips_weights", "lpips v0.1 (weights/v0.1/alex.pth)")
         model = cls(device=device, init=False)
         model.load_state_dict(sd, lin)
         return model
@@ -128,7 +76,7 @@ class AlexNetLPIPS(_Trunk):
         """torchvision's `features.N.{weight,bias}` (classifier.* ignored) and lpips' `linN.model.1.weight`."""
         host = torch.zeros(self.arena.numel(), dtype=torch.float32)
         self._fill_convs(host, sd)
-        for n, t in S.checked(lin, S.lin_shapes(), "lpips").items():
+        for n, t in checked(lin, S.lin_shapes(), "lpips").items():
             host[self.offsets[n]:self.offsets[n] + t.numel()] = t.detach().reshape(-1).to(torch.float32)
         self.arena.copy_(host)
 
@@ -138,18 +86,13 @@ class AlexNetLPIPS(_Trunk):
         m = self._input(x)
         B = m.B // 2
         out = torch.zeros(B, device=self.device, dtype=torch.float64)
-        for i, c in enumerate(S.LPIPS_CHANNELS):
-            m = self.conv(m, i, relu=True)
+        for i, u in enumerate(self.UNITS):
+            m = self.conv(m, u, True)
             HW = m.H * m.W
             o = self.offsets[S.lin_key(i)]
-            k.lpips_layer(m.t, m.t[B * HW:], m.ld, self.arena[o:o + c], out, B, HW, c)
+            k.lpips_layer(m.t, m.t[B * HW:], m.ld, self.arena[o:o + u.co], out, B, HW, u.co)
             if i in S.ALEX_POOL_AFTER:
-                if min(m.H, m.W) < 3:
-                    raise ValueError(f"AlexNetLPIPS: a {m.H} x {m.W} map is too small for the 3 x 3 max pool")
-                Ho, Wo = (m.H - 3) // 2 + 1, (m.W - 3) // 2 + 1
-                y = _Map(torch.empty((m.B * Ho * Wo, m.C), device=self.device, dtype=torch.float32), m.B, Ho, Wo)
-                k.pool2d(m.t, m.ld, y.t, y.ld, m.B, m.H, m.W, m.C, "max", 2, 0)
-                m = y
+                m = self.pool(m, "max", 2, 0)
         return out
 
 
@@ -165,7 +108,7 @@ class VGG19Style(_Trunk):
 
     @classmethod
     def from_pretrained(cls, vgg_weights=None, device=None):
-        sd = _load_file(vgg_weights, S.VGG_WEIGHTS_NAME, "--vgg_weights", "torchvision VGG-19")
+        sd = load_weights_file(vgg_weights, S.VGG_WEIGHTS_NAME, "--vgg_weights", "torchvision VGG-19")
         model = cls(device=device, init=False)
         model.load_state_dict(sd)
         return model
@@ -184,7 +127,7 @@ class VGG19Style(_Trunk):
         style = torch.zeros(B, device=self.device, dtype=torch.float64)
         content = torch.zeros(B, device=self.device, dtype=torch.float64)
         for i, u in enumerate(self.UNITS):
-            m = self.conv(m, i, relu=False)
+            m = self.conv(m, u, False)
             HW = m.H * m.W
             ws = torch.empty(k.gram_workspace_elems(B, HW, m.C), device=self.device, dtype=torch.float32)
             k.gram_pair(m.t, m.t[B * HW:], m.ld, B, HW, m.C, ws, style, content if i == S.VGG_CONTENT else None)
@@ -193,8 +136,7 @@ class VGG19Style(_Trunk):
             if i in S.VGG_POOL_AFTER:
                 if min(m.H, m.W) < 2:
                     raise ValueError(f"VGG19Style: a {m.H} x {m.W} map is too small for the 2 x 2 max pool")
-                y = _Map(torch.empty((m.B * (m.H // 2) * (m.W // 2), m.C), device=self.device, dtype=torch.float32), m.B,
-                         m.H // 2, m.W // 2)
+                y = self.new_map(m.B, m.H // 2, m.W // 2, m.C)
                 k.relu_pool(m.t, m.ld, y.t, y.ld, m.B, m.H, m.W, m.C, 2)
                 m = y
             else:

@@ -8,7 +8,7 @@
 """
 import torch
 
-from ..inception.spec import ConvUnit
+from ..convnet import ConvUnit
 
 ALEX_UNITS = (ConvUnit("features.0", 3, 64, 11, 11, 4, 2, 2), ConvUnit("features.3", 64, 192, 5, 5, 1, 2, 2),
               ConvUnit("features.6", 192, 384, 3, 3, 1, 1, 1), ConvUnit("features.8", 384, 256, 3, 3, 1, 1, 1),
@@ -51,17 +51,6 @@ def conv_shapes(units):
 
 def lin_shapes():
     return {lin_key(i): (1, c, 1, 1) for i, c in enumerate(LPIPS_CHANNELS)}
-
-
-def checked(sd, want, what):
-    """The tensors of `want` ({key: shape}) out of `sd`; other keys (the classifier, deeper VGG layers) are ignored, a missing
-    key raises KeyError and a mis-shaped one ValueError, both naming it."""
-    for n, shape in want.items():
-        if n not in sd:
-            raise KeyError(f"missing key {n} in the {what} state dict")
-        if tuple(sd[n].shape) != tuple(shape):
-            raise ValueError(f"{n}: shape {tuple(sd[n].shape)}, expected {tuple(shape)} ({what})")
-    return {n: sd[n] for n in want}
 
 
 def init_conv_state_dict(units, seed):

@@ -23,7 +23,8 @@ os.environ.setdefault("TRANSFORMERS_OFFLINE", "1")
 import numpy as np
 import torch
 
-from .data import DESC_BYTES, center_crop_origin, open_rgb, resized_size
+from . import data
+from .data import center_crop_origin, open_rgb, resized_size
 
 IMAGE_EXTENSIONS = {"bmp", "jpg", "jpeg", "pgm", "png", "ppm", "tif", "tiff", "webp"}
 TEXT_EXTENSIONS = {"txt"}
@@ -116,24 +117,11 @@ def load_image(path):
 
 
 def pack_images(arrays, R):
-    """One uint8 host buffer: B pdmk_image_desc (resize the short side to R, center crop R x R) then the HWC images, each
-    on a 4-byte word; and the descriptors as an int64 [B, 8] tensor."""
-    desc, off = [], 0
-    for a in arrays:
-        h, w = a.shape[:2]
+    """data.pack_images with CLIP's geometry: resize the short side to R, center crop R x R."""
+    def geometry(h, w):
         rh, rw = resized_size(h, w, R)
-        top, left = center_crop_origin(rh, rw, R)
-        desc.append([off, h, w, rh, rw, top, left, 0])
-        off += (a.size + 3) & ~3
-    B = len(arrays)
-    head = B * DESC_BYTES
-    packed = torch.zeros(head + off + 4, dtype=torch.uint8)
-    buf = packed.numpy()
-    d = np.asarray(desc, np.int64).reshape(B, 8)
-    buf[:head] = d.reshape(-1).view(np.uint8)
-    for (o, *_), a in zip(desc, arrays):
-        buf[head + o:head + o + a.size] = a.reshape(-1)
-    return packed, torch.from_numpy(d.copy())
+        return (rh, rw) + center_crop_origin(rh, rw, R) + (0,)
+    return data.pack_images(arrays, geometry)
 
 
 class _ScoreBatches(torch.utils.data.Dataset):
@@ -156,10 +144,9 @@ def prep_images(packed, desc, R, device):
     """Packed host batch -> CLIP pixel values fp32 [B, 3, R, R] on the device (one H2D copy, one kernel)."""
     from .. import _pdmk
     B = desc.shape[0]
-    buf = packed.to(device, non_blocking=True)
-    head = B * DESC_BYTES
+    src, dev_desc = data.upload(packed, B, device)
     pix = torch.empty(B, 3, R, R, device=device)
-    _pdmk.image_prep_ex(buf[head:], desc, buf[:head].view(torch.int64), pix, filter=1)
+    _pdmk.image_prep_ex(src, desc, dev_desc, pix, filter=1)
     return pix
 
 

@@ -58,6 +58,56 @@ def center_crop_origin(rh, rw, R):
     return int(round((rh - R) / 2.0)), int(round((rw - R) / 2.0))
 
 
+# ---- the packed image batch: what the workers build, and its way to the device
+def pack_images(arrays, rows):
+    """uint8 [H, W, 3] arrays -> (packed, desc): one uint8 host buffer of B pdmk_image_desc, then the HWC images, each on a
+    4-byte word, then one spare word (gaps and spare word zero); and the descriptors [offset, h, w, rh, rw, top, left,
+    flip] as an int64 [B, 8] tensor.  rows: per image [h, w, rh, rw, top, left, flip], or a callable (h, w) -> (rh, rw,
+    top, left, flip)."""
+    for a in arrays:
+        if a.ndim != 3 or a.shape[2] != 3 or a.dtype != np.uint8:
+            raise ValueError(f"expected uint8 [H, W, 3] images, got {a.dtype} {a.shape}")
+    if callable(rows):
+        rows = [a.shape[:2] + tuple(rows(*a.shape[:2])) for a in arrays]
+    B = len(arrays)
+    d = np.zeros((B, 8), np.int64)
+    off = 0
+    for i, a in enumerate(arrays):
+        d[i, 0], d[i, 1:] = off, rows[i]
+        off += (a.size + 3) & ~3                     # every image starts on a 4-byte word
+    head = B * DESC_BYTES
+    packed = torch.empty(head + off + 4, dtype=torch.uint8)
+    buf = packed.numpy()
+    buf[:head] = d.reshape(-1).view(np.uint8)
+    starts = d[:, 0].tolist() + [off]
+    for i, a in enumerate(arrays):
+        at = head + starts[i]
+        buf[at:at + a.size] = a.reshape(-1)
+        buf[at + a.size:head + starts[i + 1]] = 0
+    buf[head + off:] = 0
+    return packed, torch.from_numpy(d)
+
+
+def upload(packed, B, device):
+    """One non-blocking H2D copy of a packed batch of B images -> (the image bytes, the descriptors as an int64 view)."""
+    buf = packed.to(device, non_blocking=True)
+    head = B * DESC_BYTES
+    return buf[head:], buf[:head].view(torch.int64)
+
+
+def prep_nhwc(packed, desc, R, device, filter, mean, std):
+    """Packed host batch -> normalised fp32 NHWC [B, R, R, 3] on the device: pdmk_image_prep_ex (resize, crop, / 255,
+    (x - mean) / std), then pdmk_nchw_to_nhwc."""
+    from .. import _pdmk
+    B = desc.shape[0]
+    src, dev_desc = upload(packed, B, device)
+    pix = torch.empty(B, 3, R, R, device=device)
+    _pdmk.image_prep_ex(src, desc, dev_desc, pix, filter=filter, mean=mean, std=std)
+    x = torch.empty(B, R, R, 3, device=device)
+    _pdmk.nchw_to_nhwc(pix, x, B, 3, R * R, 3)
+    return x
+
+
 # ---- datasets (pdm/utils/data_utils.py:12-65)
 def load_coco_dataset(images_dir, annotations_file):
     """One row per caption annotation: (image path, caption); 2014 splits use COCO_<split>_%012d.jpg names."""
@@ -203,8 +253,7 @@ class PackedBatches(torch.utils.data.Dataset):
     def __getitem__(self, b):
         R = self.R
         rng = np.random.default_rng([self.seed, self.epoch, self.rank, int(b)])
-        images, desc, captions, index = [], [], [], []
-        off = 0
+        images, geometry, captions, index = [], [], [], []
         for i in self.plan[b]:
             row = self.rows[int(i)]
             caption = pick_caption(row[self.caption_column], self.train, rng)
@@ -218,22 +267,13 @@ class PackedBatches(torch.utils.data.Dataset):
             else:
                 top, left = int(rng.integers(rh - R + 1)), int(rng.integers(rw - R + 1))
             flip = int(self.train and self.random_flip and rng.random() < 0.5)
-            desc.append([off, h, w, rh, rw, top, left, flip])
+            geometry.append([h, w, rh, rw, top, left, flip])
             images.append(a)
             captions.append(caption)
             index.append(int(i))
-            off += (a.size + 3) & ~3                     # every image starts on a 4-byte word
         B = len(images)
-        head = B * DESC_BYTES
-        packed = torch.empty(head + off + 4, dtype=torch.uint8)
-        buf = packed.numpy()
-        d = np.asarray(desc, np.int64).reshape(B, 8)
-        buf[:head] = d.reshape(-1).view(np.uint8)
-        for (o, *_), a in zip(desc, images):
-            buf[head + o:head + o + a.size] = a.reshape(-1)
-        buf[head + off:] = 0
-        out = {"packed": packed, "image_desc": torch.from_numpy(d.copy()), "index": torch.tensor(index, dtype=torch.int64),
-               "captions": captions}
+        packed, desc = pack_images(images, geometry)
+        out = {"packed": packed, "image_desc": desc, "index": torch.tensor(index, dtype=torch.int64), "captions": captions}
         if self.tokenizer is not None:
             ids = tokenize(self.tokenizer, captions) if B else torch.zeros(0, self.empty_ids().shape[1], dtype=torch.int64)
             out["input_ids"] = ids
@@ -299,10 +339,9 @@ def to_device(hb, R, device):
     if B == 0:
         out["pixel_values"] = torch.empty(0, 3, R, R, device=device)
     else:
-        buf = hb["packed"].to(device, non_blocking=True)
-        head = B * DESC_BYTES
+        src, dev_desc = upload(hb["packed"], B, device)
         pix = torch.empty(B, 3, R, R, device=device)
-        _pdmk.image_prep(buf[head:], hb["image_desc"], buf[:head].view(torch.int64), pix)
+        _pdmk.image_prep(src, hb["image_desc"], dev_desc, pix)
         out["pixel_values"] = pix
     for k in ("input_ids", "empty_input_ids"):
         if k in out:

@@ -22,7 +22,7 @@ import numpy as np
 import torch
 
 from .clip_utils import IMAGE_EXTENSIONS, default_workers, load_image
-from .data import DESC_BYTES
+from . import data
 
 MODES = ("legacy_pytorch",)
 STATS_ENV = "PDM_FID_STATS"
@@ -102,34 +102,17 @@ def load_stats(path):
 
 # ---- batches
 def pack_images(arrays):
-    """One uint8 host buffer: B pdmk_image_desc then the HWC images, each on a 4-byte word (+ one spare word); and the
-    descriptors as an int64 [B, 8] tensor (offset, h, w, and the unused resize / crop fields as the identity)."""
-    desc, off = [], 0
-    for a in arrays:
-        h, w = a.shape[:2]
-        if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3:
-            raise ValueError(f"expected uint8 [H, W, 3] images, got {a.dtype} {a.shape}")
-        desc.append([off, h, w, h, w, 0, 0, 0])
-        off += (a.size + 3) & ~3
-    B = len(arrays)
-    head = B * DESC_BYTES
-    packed = torch.zeros(head + off + 4, dtype=torch.uint8)
-    buf = packed.numpy()
-    d = np.asarray(desc, np.int64).reshape(B, 8)
-    buf[:head] = d.reshape(-1).view(np.uint8)
-    for (o, *_), a in zip(desc, arrays):
-        buf[head + o:head + o + a.size] = np.ascontiguousarray(a).reshape(-1)
-    return packed, torch.from_numpy(d.copy())
+    """data.pack_images with the unused resize / crop fields as the identity: descriptors [offset, h, w, h, w, 0, 0, 0]."""
+    return data.pack_images(arrays, lambda h, w: (h, w, 0, 0, 0))
 
 
 def prep_images(packed, desc, device, size=299):
     """Packed host batch -> the network's input fp32 NHWC [B, size, size, 3] in [-1, 1] (one H2D copy, one kernel)."""
     from .. import _pdmk
     B = desc.shape[0]
-    buf = packed.to(device, non_blocking=True)
-    head = B * DESC_BYTES
+    src, dev_desc = data.upload(packed, B, device)
     x = torch.empty(B, size, size, 3, device=device)
-    _pdmk.resize_bilinear_u8(buf[head:], desc, buf[:head].view(torch.int64), x)
+    _pdmk.resize_bilinear_u8(src, desc, dev_desc, x)
     return x
 
 

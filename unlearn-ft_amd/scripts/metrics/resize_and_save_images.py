@@ -44,14 +44,13 @@ class _Batches(torch.utils.data.Dataset):
 def resize_batch(packed, desc, size, device):
     """Packed host batch -> uint8 [B, H, W, 3] on the device, each image resized to size = (W, H)."""
     from pdm import _pdmk
-    from pdm.utils.data import DESC_BYTES
+    from pdm.utils.data import upload
     B = desc.shape[0]
     desc = desc.clone()
     desc[:, 3], desc[:, 4] = size[1], size[0]
-    head = B * DESC_BYTES
-    buf = packed.to(device, non_blocking=True)
+    src, _ = upload(packed, B, device)                  # the descriptors in the buffer carry no target size
     out = torch.empty(B, size[1], size[0], 3, device=device, dtype=torch.uint8)
-    _pdmk.image_resize_u8(buf[head:], desc, desc.to(device), out)
+    _pdmk.image_resize_u8(src, desc, desc.to(device), out)
     return out
 
 
