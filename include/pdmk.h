@@ -600,6 +600,41 @@ int pdmk_sld_ddim_step(const void* pred, int ld, float guidance_scale, const pdm
                        const pdmk_ddim_row* table, int nsteps, int32_t* state, int64_t* t_out, void* x_next, int cpad, int B,
                        int C, int HW, int dtype, pdmk_stream stream);
 
+/* Concept algebra (Wang et al. 2023; baselines/unified-concept-editing/eval-scripts/concept_algebra.py): five U-Net branches
+ * per step - u (uncond), t (text) and three concept prompts p0, p1, p2 - and, over the WHOLE [B, C, H, W] tensor, batch
+ * included,
+ *     w = t - p2;  d = p1 - p0;  d /= sqrt(sum d^2);  t -= sum(w d) d;  pred = u + g (t - u)
+ * Here that is two launches between two U-Net calls, both capturable, neither waits on the host, the library allocates nothing.
+ * pdmk_calg_dots: pred NHWC rows [5B * HW, ld] in dtype (f32 / bf16), fifths in the order u, t, p0, p1, p2.  Per element
+ *   d = p1 - p0 and w = t - p2 are fp32 subtractions; sum d d and sum w d are accumulated in fp64 in one fixed order (no
+ *   atomics): the grid is calg_parts = min(256, ceil(B C HW / 256)) workgroups, a function of B C HW only; elements are taken in
+ *   the latent's NCHW order, so fp32 NCHW fifths passed as (ld = 1, C = 1, HW = C H W) give the same bits as the NHWC rows
+ *   they were converted from.  Workgroup g writes its pair to ws[2g], ws[2g + 1].  ws: pdmk_calg_workspace_elems(B, C, HW) =
+ *   2 calg_parts fp64 elements.
+ * The guidance (pdmk_calg_guidance and the two step launches): each workgroup adds the pairs in index order in one thread
+ *   and takes S_dd, S_wd from LDS - every workgroup holds the same bits - and forms nrm = (float)sqrt(S_dd),
+ *   dot = (float)(S_wd / sqrt(S_dd)).  Then per element, separate fp32 operations each rounded once (no fma):
+ *     d = p1 - p0;  e = d / nrm;  pw = dot * e;  t2 = t - pw;  ng = t2 - u;  gn = g * ng;  pred = u + gn
+ *   Deviation: where S_dd is zero or not finite (or nrm is zero in fp32) the reference divides by zero and samples NaN; here
+ *   nrm = dot = 0 and pw = 0, the plain two-branch guidance.  scalars (fp32 [2] on the device, may be NULL) receives nrm, dot
+ *   from workgroup 0.
+ * pdmk_calg_guidance: the eager loop's form, pred fp32 NCHW [5B, C, HW] -> out fp32 [B, C, HW]; 16-byte accesses when
+ *   B * C * HW % 4 == 0 and both pointers are 16-byte aligned.
+ * pdmk_calg_plms_step / pdmk_calg_ddim_step: pdmk_plms_step / pdmk_ddim_step with this guidance on 5B rows; x_next
+ *   ([5B * HW, cpad]) receives the new sample for all five fifths (padding channels 0), t_out (int64 [5B]) table[step + 1].t;
+ *   sample, cur, ets, table, state and "past the end does nothing" as in the two-branch launches.  ws must hold the pairs of a
+ *   pdmk_calg_dots launch on the same pred, B, C, HW. */
+int64_t pdmk_calg_workspace_elems(int B, int C, int HW);
+int pdmk_calg_dots(const void* pred, int ld, int B, int C, int HW, int dtype, double* ws, int64_t ws_elems, pdmk_stream stream);
+int pdmk_calg_guidance(const float* pred, float* out, int B, int C, int HW, float guidance_scale, const double* ws,
+                       int64_t ws_elems, float* scalars, pdmk_stream stream);
+int pdmk_calg_plms_step(const void* pred, int ld, float guidance_scale, const double* ws, int64_t ws_elems, float* scalars,
+                        float* sample, float* cur, float* ets, const pdmk_plms_row* table, int nsteps, int32_t* state,
+                        int64_t* t_out, void* x_next, int cpad, int B, int C, int HW, int dtype, pdmk_stream stream);
+int pdmk_calg_ddim_step(const void* pred, int ld, float guidance_scale, const double* ws, int64_t ws_elems, float* scalars,
+                        float* sample, const pdmk_ddim_row* table, int nsteps, int32_t* state, int64_t* t_out, void* x_next,
+                        int cpad, int B, int C, int HW, int dtype, pdmk_stream stream);
+
 /* Image epilogue of generate_fid_images.py:141-151 (`(image / 2 + 0.5).clamp(0, 1)` of the diffusers image processor, then
  * `.permute(0, 2, 3, 1).cpu().numpy()`, `img * 255`, `img.astype(np.uint8)`): fp32 NCHW [B, C, HW] in, uint8 NHWC out,
  * truncated (not rounded); NaN gives 0. */
@@ -736,6 +771,12 @@ int pdmk_wanda_apply(void* w, int dtype, int O, int F, int ldw, const int32_t* c
  * pdmk_spd_system_f64: A[i][j] = fma(s_b, sym(g_b)[i][j], fma(s_a, sym(g_a)[i][j], i == j ? lam : 0)) (g_b NULL: the inner fma
  *   alone), A [n, n] fp64 with row stride lda.  g_a / g_b: [n, n] fp64 contiguous as pdmk_fid_accumulate leaves `outer` (only
  *   the 64 x 64 tiles that touch the upper triangle are valid); sym takes each element from the tile that holds it.
+ * pdmk_pair_gram_f64 (debias-VL, baselines/unified-concept-editing/eval-scripts/debiasing_vl.py get_M; pdm/utils/debias_vl.py):
+ *   z fp32 [2 npairs, d] (row stride ldz), rows 2p / 2p + 1 the two members of pair p.  A[i][j] = fma(scale, S[i][j], i == j ?
+ *   lam : 0) with S[i][j] = sum_p delta_p[i] delta_p[j], delta_p = (double)z[2p] - (double)z[2p + 1], the sum a chain of fp64
+ *   FMAs over p ascending.  All d x d elements are written (so the lower triangle the factor reads is valid) and A is
+ *   symmetric bit for bit; 64 x 64 tiles, delta staged in LDS.  1 <= d <= PDMK_SPD_MAX_N, npairs >= 1.  The reference's
+ *   P = inv(500 M + I) with M the mean of the outer products is scale = 500 / npairs, lam = 1, then factor and solve.
  * pdmk_spd_factor_f64: Cholesky A = L L^T in place, 1 <= n <= PDMK_SPD_MAX_N (any n), lda >= n: the lower triangle of A is read
  *   and receives L; the strict upper triangle is not read and is unspecified afterwards; columns >= n of a row are neither read
  *   nor written.  Right-looking, 64-wide panels, per panel: the diagonal block in LDS by one workgroup, the rows below it by
@@ -770,6 +811,8 @@ int pdmk_wanda_apply(void* w, int dtype, int O, int F, int ldw, const int32_t* c
 int64_t pdmk_spd_workspace_elems(int n, int m);
 int pdmk_spd_system_f64(const double* g_a, double s_a, const double* g_b, double s_b, double lam, double* A, int n, int lda,
                         pdmk_stream stream);
+int pdmk_pair_gram_f64(const float* z, int ldz, int npairs, int d, double scale, double lam, double* A, int lda,
+                       pdmk_stream stream);
 int pdmk_spd_factor_f64(double* A, int n, int lda, int32_t* info, pdmk_stream stream);
 int pdmk_spd_solve_f64(const double* L, int n, int ldl, const float* B, int m, int ldb, float* X, int ldx, double* X64, int ldx64,
                        double* ws, int64_t ws_elems, pdmk_stream stream);

@@ -12,7 +12,10 @@
 // in nchw2nhwc_kernel.
 // pdmk_sld_plms_step / pdmk_sld_ddim_step are the same two launches with Safe Latent Diffusion's three-branch guidance
 // (sld_chain below: plain fp32 operations, no fma) in place of the axpby; pdmk_sld_guidance is that chain alone, for the
-// eager loop.  All four step entry points are instances of one kernel (step_kernel<T, Guide, Sched>).
+// eager loop.  pdmk_calg_plms_step / pdmk_calg_ddim_step are the same two launches with concept algebra's score projection on
+// five branches (calg_chain below); its two scalars come from the fp64 partial sums that pdmk_calg_dots leaves, summed again
+// by every workgroup in one fixed order.  pdmk_calg_guidance is that chain alone.  All six step entry points are instances of
+// one kernel (step_kernel<T, Guide, Sched>).
 #include "common.h"
 
 #pragma clang fp contract(off)
@@ -30,6 +33,7 @@ struct CfgGuide {
     float g_u, g_t;
     int cfg;
     __device__ int copies() const { return cfg ? 2 : 1; }
+    __device__ void prepare() {}
     template <typename T>
     __device__ float operator()(const T* __restrict__ pred, int ld, long p, long npix, int c, long, int) const {
         float g = to_f32(pred[p * ld + c]);                           // unconditional half (or the only one)
@@ -62,10 +66,63 @@ struct SldGuide {
     pdmk_sld_params q;
     float* mom;
     __device__ int copies() const { return 3; }
+    __device__ void prepare() {}
     template <typename T>
     __device__ float operator()(const T* __restrict__ pred, int ld, long p, long npix, int c, long i, int step) const {
         return sld_chain(to_f32(pred[p * ld + c]), to_f32(pred[(p + npix) * ld + c]), to_f32(pred[(p + 2 * npix) * ld + c]),
                          mom[i], g, q, step >= q.warmup_steps);
+    }
+};
+
+// Concept algebra (include/pdmk.h "Concept algebra"): the partial pairs of pdmk_calg_dots -> the two fp32 scalars.  One thread
+// adds the pairs in index order and the workgroup takes the result from LDS, so every workgroup of every launch that reads the
+// same workspace holds the same bits.  A sum of squares that is not finite, or whose root is zero in fp32, gives (0, 0): the
+// chain then leaves the projection out.  Every thread of the workgroup must call this.
+struct CalgScalars {
+    float nrm, dot;
+};
+__device__ __forceinline__ CalgScalars calg_scalars(const double* __restrict__ ws, int nparts, float* scalars) {
+    __shared__ float sc[2];
+    if (threadIdx.x == 0) {
+        double sdd = 0.0, swd = 0.0;
+        for (int k = 0; k < nparts; ++k) sdd += ws[2 * k], swd += ws[2 * k + 1];
+        const double root = sqrt(sdd);
+        float nrm = (float)root, dot = (float)(swd / root);
+        if (!(sdd - sdd == 0.0) || !(nrm > 0.f)) nrm = 0.f, dot = 0.f;
+        sc[0] = nrm, sc[1] = dot;
+        if (scalars && blockIdx.x == 0) scalars[0] = nrm, scalars[1] = dot;
+    }
+    __syncthreads();
+    return CalgScalars{sc[0], sc[1]};
+}
+
+// Separate fp32 operations, each rounded once (no fma: this file is compiled without contraction).
+__device__ __forceinline__ float calg_chain(float u, float t, float p0, float p1, float g, CalgScalars q) {
+    float pw = 0.f;
+    if (q.nrm > 0.f) {
+        const float d = p1 - p0;
+        const float e = d / q.nrm;
+        pw = q.dot * e;
+    }
+    const float t2 = t - pw;
+    const float ng = t2 - u;
+    const float gn = g * ng;
+    return u + gn;
+}
+
+// Five branches, fifths in the order uncond, text, p0, p1, p2 (p2 enters through the dot product only).
+struct CalgGuide {
+    float g;
+    const double* ws;
+    int nparts;
+    float* scalars;
+    CalgScalars q;
+    __device__ int copies() const { return 5; }
+    __device__ void prepare() { q = calg_scalars(ws, nparts, scalars); }
+    template <typename T>
+    __device__ float operator()(const T* __restrict__ pred, int ld, long p, long npix, int c, long, int) const {
+        return calg_chain(to_f32(pred[p * ld + c]), to_f32(pred[(p + npix) * ld + c]), to_f32(pred[(p + 2 * npix) * ld + c]),
+                          to_f32(pred[(p + 3 * npix) * ld + c]), g, q);
     }
 };
 
@@ -111,7 +168,7 @@ struct DdimSched {
 };
 
 // One launch between two U-Net calls: guidance, scheduler step, the next call's input (one copy per branch) and timesteps,
-// and the step counter.  pdmk_plms_step, pdmk_ddim_step and their SLD forms are its four instances per dtype.
+// and the step counter.  pdmk_plms_step, pdmk_ddim_step and their SLD and concept-algebra forms are its six instances per dtype.
 template <typename T, typename Guide, typename Sched>
 __global__ void step_kernel(const T* __restrict__ pred, int ld, Guide guide, Sched sched, int nsteps, int32_t* state,
                             int64_t* __restrict__ t_out, T* __restrict__ x_next, int cpad, int B, int C, int HW) {
@@ -121,6 +178,7 @@ __global__ void step_kernel(const T* __restrict__ pred, int ld, Guide guide, Sch
     const long npix = (long)B * HW;
     const long part = npix * cpad;                   // elements of one branch's rows in x_next
     const int copies = guide.copies();
+    guide.prepare();                                 // (nothing for the guides without launch-wide scalars)
     for (long p = blockIdx.x * (long)NT + threadIdx.x; p < npix; p += (long)gridDim.x * NT) {
         const int b = (int)(p / HW);
         const int px = (int)(p - (long)b * HW);
@@ -190,6 +248,63 @@ __global__ void sld_guidance_kernel(const float* __restrict__ pred, float* __res
         } else {
             out[j] = o[0], mom[j] = m[0];
         }
+    }
+}
+
+// pdmk_calg_dots: workgroup g's share of sum d d and sum w d, d = p1 - p0 and w = t - p2 in fp32, the sums in fp64.  Elements
+// are taken in the latent's NCHW order i (thread j of workgroup g: i = g NT + j, then steps of gridDim NT), a thread's sum runs
+// over its elements ascending, and the workgroup's 256 sums are added pairwise in LDS - one fixed order, no atomics.
+constexpr int CALG_PARTS = 256;
+inline int calg_parts(long n) { return grid_for(n, CALG_PARTS); }
+
+template <typename T>
+__global__ void __launch_bounds__(NT) calg_dots_kernel(const T* __restrict__ pred, int ld, int C, int HW, long n, long npix,
+                                                       double* __restrict__ ws) {
+    __shared__ double sdd[NT], swd[NT];
+    double add = 0.0, awd = 0.0;
+    const long chw = (long)C * HW;
+    for (long i = blockIdx.x * (long)NT + threadIdx.x; i < n; i += (long)gridDim.x * NT) {
+        const long b = i / chw, r = i - b * chw;
+        const int c = (int)(r / HW);
+        const long p = b * HW + (r - (long)c * HW);
+        const T* at = pred + p * ld + c;
+        const long fifth = npix * ld;
+        const float t = to_f32(at[fifth]), p0 = to_f32(at[2 * fifth]), p1 = to_f32(at[3 * fifth]), p2 = to_f32(at[4 * fifth]);
+        const float d = p1 - p0, w = t - p2;
+        add += (double)d * (double)d;
+        awd += (double)w * (double)d;
+    }
+    sdd[threadIdx.x] = add, swd[threadIdx.x] = awd;
+    __syncthreads();
+    for (int h = NT / 2; h > 0; h >>= 1) {
+        if ((int)threadIdx.x < h) sdd[threadIdx.x] += sdd[threadIdx.x + h], swd[threadIdx.x] += swd[threadIdx.x + h];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) ws[2 * blockIdx.x] = sdd[0], ws[2 * blockIdx.x + 1] = swd[0];
+}
+
+// The eager loop's concept-algebra guidance on fp32 NCHW fifths: 16-byte loads and stores when n and the pointers allow.
+template <int V>
+__global__ void calg_guidance_kernel(const float* __restrict__ pred, float* __restrict__ out, long n, float g,
+                                     const double* __restrict__ ws, int nparts, float* scalars) {
+    const CalgScalars q = calg_scalars(ws, nparts, scalars);
+    const long nv = n / V;
+    for (long j = blockIdx.x * (long)NT + threadIdx.x; j < nv; j += (long)gridDim.x * NT) {
+        float u[V], t[V], p0[V], p1[V], o[V];
+        if (V == 4) {
+            *reinterpret_cast<float4*>(u) = reinterpret_cast<const float4*>(pred)[j];
+            *reinterpret_cast<float4*>(t) = reinterpret_cast<const float4*>(pred + n)[j];
+            *reinterpret_cast<float4*>(p0) = reinterpret_cast<const float4*>(pred + 2 * n)[j];
+            *reinterpret_cast<float4*>(p1) = reinterpret_cast<const float4*>(pred + 3 * n)[j];
+        } else {
+            u[0] = pred[j], t[0] = pred[n + j], p0[0] = pred[2 * n + j], p1[0] = pred[3 * n + j];
+        }
+#pragma unroll
+        for (int e = 0; e < V; ++e) o[e] = calg_chain(u[e], t[e], p0[e], p1[e], g, q);
+        if (V == 4)
+            reinterpret_cast<float4*>(out)[j] = *reinterpret_cast<const float4*>(o);
+        else
+            out[j] = o[0];
     }
 }
 
@@ -266,6 +381,66 @@ extern "C" int pdmk_sld_ddim_step(const void* pred, int ld, float guidance_scale
         return -1;
     return launch_step(pred, ld, SldGuide{guidance_scale, *params, mom}, DdimSched{sample, table}, nsteps, state, t_out, x_next,
                        cpad, B, C, HW, dtype, s);
+}
+
+extern "C" int64_t pdmk_calg_workspace_elems(int B, int C, int HW) {
+    if (B <= 0 || C <= 0 || HW <= 0) return 0;
+    return 2 * (int64_t)calg_parts((long)B * C * HW);
+}
+
+extern "C" int pdmk_calg_dots(const void* pred, int ld, int B, int C, int HW, int dtype, double* ws, int64_t ws_elems,
+                              pdmk_stream s) {
+    if (!pred || !ws || B <= 0 || C <= 0 || HW <= 0 || ld < C || ((uintptr_t)ws & 7) ||
+        ws_elems < pdmk_calg_workspace_elems(B, C, HW))
+        return -1;
+    const long n = (long)B * C * HW, npix = (long)B * HW;
+    const dim3 grid(calg_parts(n));
+    if (dtype == PDMK_BF16)
+        hipLaunchKernelGGL(calg_dots_kernel<bf16>, grid, dim3(NT), 0, (hipStream_t)s, (const bf16*)pred, ld, C, HW, n, npix, ws);
+    else if (dtype == PDMK_F32)
+        hipLaunchKernelGGL(calg_dots_kernel<float>, grid, dim3(NT), 0, (hipStream_t)s, (const float*)pred, ld, C, HW, n, npix, ws);
+    else return -2;
+    PDMK_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int pdmk_calg_guidance(const float* pred, float* out, int B, int C, int HW, float guidance_scale, const double* ws,
+                                  int64_t ws_elems, float* scalars, pdmk_stream s) {
+    if (!pred || !out || !ws || B <= 0 || C <= 0 || HW <= 0 || ((uintptr_t)ws & 7) ||
+        ws_elems < pdmk_calg_workspace_elems(B, C, HW))
+        return -1;
+    const long n = (long)B * C * HW;
+    const int nparts = calg_parts(n);
+    const bool wide = n % 4 == 0 && ((uintptr_t)pred | (uintptr_t)out) % 16 == 0;
+    if (wide)
+        hipLaunchKernelGGL(calg_guidance_kernel<4>, dim3(grid_for(n / 4)), dim3(NT), 0, (hipStream_t)s, pred, out, n,
+                           guidance_scale, ws, nparts, scalars);
+    else
+        hipLaunchKernelGGL(calg_guidance_kernel<1>, dim3(grid_for(n)), dim3(NT), 0, (hipStream_t)s, pred, out, n,
+                           guidance_scale, ws, nparts, scalars);
+    PDMK_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int pdmk_calg_plms_step(const void* pred, int ld, float guidance_scale, const double* ws, int64_t ws_elems,
+                                   float* scalars, float* sample, float* cur, float* ets, const pdmk_plms_row* table, int nsteps,
+                                   int32_t* state, int64_t* t_out, void* x_next, int cpad, int B, int C, int HW, int dtype,
+                                   pdmk_stream s) {
+    if (!pred || !ws || !sample || !cur || !ets || !table || !state || !t_out || !x_next || nsteps <= 0 || B <= 0 || C <= 0 ||
+        HW <= 0 || ld < C || cpad < C || ((uintptr_t)ws & 7) || ws_elems < pdmk_calg_workspace_elems(B, C, HW))
+        return -1;
+    return launch_step(pred, ld, CalgGuide{guidance_scale, ws, calg_parts((long)B * C * HW), scalars, {0.f, 0.f}},
+                       PlmsSched{sample, cur, ets, table}, nsteps, state, t_out, x_next, cpad, B, C, HW, dtype, s);
+}
+
+extern "C" int pdmk_calg_ddim_step(const void* pred, int ld, float guidance_scale, const double* ws, int64_t ws_elems,
+                                   float* scalars, float* sample, const pdmk_ddim_row* table, int nsteps, int32_t* state,
+                                   int64_t* t_out, void* x_next, int cpad, int B, int C, int HW, int dtype, pdmk_stream s) {
+    if (!pred || !ws || !sample || !table || !state || !t_out || !x_next || nsteps <= 0 || B <= 0 || C <= 0 || HW <= 0 ||
+        ld < C || cpad < C || ((uintptr_t)ws & 7) || ws_elems < pdmk_calg_workspace_elems(B, C, HW))
+        return -1;
+    return launch_step(pred, ld, CalgGuide{guidance_scale, ws, calg_parts((long)B * C * HW), scalars, {0.f, 0.f}},
+                       DdimSched{sample, table}, nsteps, state, t_out, x_next, cpad, B, C, HW, dtype, s);
 }
 
 extern "C" int pdmk_image_to_u8_ex(const float* src, uint8_t* dst, int B, int C, int HW, int rounding, pdmk_stream s) {

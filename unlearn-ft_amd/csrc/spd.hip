@@ -1,6 +1,7 @@
 // Dense symmetric-positive-definite solve in fp64 and the target differences of the closed-form cross-attention edit
 // (include/pdmk.h "UCE"; pdm/utils/uce.py):
 //   pdmk_spd_system_f64 : A = lam I + s_a sym(g_a) + s_b sym(g_b) from the Gram matrices pdmk_fid_accumulate leaves
+//   pdmk_pair_gram_f64  : A = lam I + scale sum_p delta_p delta_p^T from pairs of fp32 rows (debias-VL's calibration matrix)
 //   pdmk_spd_factor_f64 : blocked right-looking Cholesky A = L L^T in place, 64-wide panels, three launches per panel
 //   pdmk_spd_solve_f64  : X = B (L L^T)^-1 for the rows of B, forward then backward block substitution per block of 16 rows
 //   pdmk_uce_delta      : D = N - O (replace) or N - (1 + <O, N> / <O, O>) O per (pair, projection) block (tensor)
@@ -40,6 +41,47 @@ __global__ void __launch_bounds__(NT) spd_system_kernel(const double* __restrict
         if (gb) v = fma(sb, gb[src], v);
         A[(long)i * lda + j] = v;
     }
+}
+
+// Debias-VL's calibration matrix (include/pdmk.h pdmk_pair_gram_f64): one workgroup per 64 x 64 tile of A, the differences
+// delta_p of PG pairs at a time staged in LDS for the tile's rows and columns (zeros past npairs and past d, which add nothing),
+// a 4 x 4 block of sums per thread (rows ty + 16 a, columns tx + 16 b: the column reads of a wave are consecutive, the row reads a
+// broadcast).  Each sum is one chain of fp64 FMAs over p ascending.
+constexpr int PG = 16;
+__global__ void __launch_bounds__(NT) pair_gram_kernel(const float* __restrict__ z, int ldz, int npairs, int d, double scale,
+                                                       double lam, double* __restrict__ A, int lda) {
+    __shared__ double di[PG][NB], dj[PG][NB];
+    const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
+    const int i0 = blockIdx.y * NB, j0 = blockIdx.x * NB;
+    double acc[4][4] = {};
+    for (int p0 = 0; p0 < npairs; p0 += PG) {
+        for (int idx = tid; idx < PG * NB; idx += NT) {
+            const int pp = idx / NB, col = idx - pp * NB, p = p0 + pp;
+            const float* male = z + (long)(2 * p) * ldz;
+            const float* female = male + ldz;
+            const bool in = p < npairs;
+            di[pp][col] = in && i0 + col < d ? (double)male[i0 + col] - (double)female[i0 + col] : 0.0;
+            dj[pp][col] = in && j0 + col < d ? (double)male[j0 + col] - (double)female[j0 + col] : 0.0;
+        }
+        __syncthreads();
+        for (int pp = 0; pp < PG; ++pp) {
+            double r[4], c[4];
+#pragma unroll
+            for (int a = 0; a < 4; ++a) r[a] = di[pp][ty + 16 * a], c[a] = dj[pp][tx + 16 * a];
+#pragma unroll
+            for (int a = 0; a < 4; ++a)
+#pragma unroll
+                for (int b = 0; b < 4; ++b) acc[a][b] = fma(r[a], c[b], acc[a][b]);
+        }
+        __syncthreads();
+    }
+#pragma unroll
+    for (int a = 0; a < 4; ++a)
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+            const int i = i0 + ty + 16 * a, j = j0 + tx + 16 * b;
+            if (i < d && j < d) A[(long)i * lda + j] = fma(scale, acc[a][b], i == j ? lam : 0.0);
+        }
 }
 
 // ---------------------------------------------------------------------------------------------------- factor
@@ -447,6 +489,16 @@ extern "C" int pdmk_spd_system_f64(const double* g_a, double s_a, const double* 
     const long total = (long)n * n;
     const int grid = (int)min(4096L, (total + NT - 1) / NT);
     hipLaunchKernelGGL(spd_system_kernel, dim3(grid), dim3(NT), 0, (hipStream_t)s, g_a, s_a, g_b, s_b, lam, A, n, lda);
+    PDMK_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int pdmk_pair_gram_f64(const float* z, int ldz, int npairs, int d, double scale, double lam, double* A, int lda,
+                                  pdmk_stream s) {
+    if (!z || !A || npairs < 1 || d < 1 || d > PDMK_SPD_MAX_N || ldz < d || lda < d || ((uintptr_t)z & 3) || ((uintptr_t)A & 7))
+        return -1;
+    const int nt = (d + NB - 1) / NB;
+    hipLaunchKernelGGL(pair_gram_kernel, dim3(nt, nt), dim3(NT), 0, (hipStream_t)s, z, ldz, npairs, d, scale, lam, A, lda);
     PDMK_CHECK_LAUNCH();
     return 0;
 }

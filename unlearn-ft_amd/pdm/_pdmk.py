@@ -139,6 +139,11 @@ _SIGS = {
     "pdmk_sld_plms_step": ([vp, i32, f32, C.POINTER(SldParams), vp, vp, vp, vp, vp, i32, vp, vp, vp, i32, i32, i32, i32, i32,
                             vp], i32),
     "pdmk_sld_ddim_step": ([vp, i32, f32, C.POINTER(SldParams), vp, vp, vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, vp], i32),
+    "pdmk_calg_workspace_elems": ([i32, i32, i32], i64),
+    "pdmk_calg_dots": ([vp, i32, i32, i32, i32, i32, vp, i64, vp], i32),
+    "pdmk_calg_guidance": ([vp, vp, i32, i32, i32, f32, vp, i64, vp, vp], i32),
+    "pdmk_calg_plms_step": ([vp, i32, f32, vp, i64, vp, vp, vp, vp, vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, vp], i32),
+    "pdmk_calg_ddim_step": ([vp, i32, f32, vp, i64, vp, vp, vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, vp], i32),
     "pdmk_image_to_u8": ([vp, vp, i32, i32, i32, vp], i32),
     "pdmk_image_to_u8_ex": ([vp, vp, i32, i32, i32, i32, vp], i32),
     "pdmk_resize_bilinear_u8": ([vp, i64, vp, vp, i32, i32, vp, vp], i32),
@@ -160,6 +165,7 @@ _SIGS = {
     "pdmk_wanda_apply": ([vp, i32, i32, i32, i32, vp, f32, vp], i32),
     "pdmk_spd_workspace_elems": ([i32, i32], i64),
     "pdmk_spd_system_f64": ([vp, f64, vp, f64, f64, vp, i32, i32, vp], i32),
+    "pdmk_pair_gram_f64": ([vp, i32, i32, i32, f64, f64, vp, i32, vp], i32),
     "pdmk_spd_factor_f64": ([vp, i32, i32, vp, vp], i32),
     "pdmk_spd_solve_f64": ([vp, i32, i32, vp, i32, i32, vp, i32, vp, i32, vp, i64, vp], i32),
     "pdmk_uce_delta": ([vp, vp, vp, i32, i32, vp, i32, vp, i32, i32, vp, vp], i32),
@@ -1029,6 +1035,68 @@ def sld_ddim_step(pred, ld, guidance_scale, params, mom, sample, table, nsteps, 
                                  _p(state), _p(t_out), _p(x_next), cpad, B, Cc, HW, dt(pred), _st()), "pdmk_sld_ddim_step")
 
 
+def calg_workspace_elems(B, Cc, HW):
+    """fp64 elements of concept algebra's partial-sum workspace for a [B, Cc, HW] latent (pdmk_calg_workspace_elems)."""
+    return int(_lib.pdmk_calg_workspace_elems(B, Cc, HW))
+
+
+def _calg_ws_ok(ws, scalars, B, Cc, HW):
+    return (ws.dtype == torch.float64 and ws.is_contiguous() and ws.numel() >= calg_workspace_elems(B, Cc, HW) > 0
+            and (scalars is None or (scalars.dtype == torch.float32 and scalars.is_contiguous() and scalars.numel() >= 2)))
+
+
+def calg_dots(pred, ld, B, Cc, HW, ws):
+    """Concept algebra's two sums as per-workgroup fp64 pairs in ws (include/pdmk.h pdmk_calg_dots): pred rows of 5B * HW
+    pixels (uncond, text, p0, p1, p2), f32 or bf16.  fp32 NCHW fifths go in as (ld = 1, Cc = 1, HW = C * H * W): same bits."""
+    if not _calg_ws_ok(ws, None, B, Cc, HW) or ld < Cc or _avail(pred) < (5 * B * HW - 1) * ld + Cc:
+        raise PdmkError("calg_dots: inconsistent buffers")
+    _chk(_lib.pdmk_calg_dots(_p(pred), ld, B, Cc, HW, dt(pred), _p(ws), ws.numel(), _st()), "pdmk_calg_dots")
+
+
+def calg_guidance(pred, out, guidance_scale, ws, scalars=None):
+    """Concept-algebra guidance of the eager loop (include/pdmk.h pdmk_calg_guidance): pred fp32 [5B, C, H, W] contiguous ->
+    out fp32 [B, C, H, W]; ws as calg_dots left it; scalars (fp32 [2], optional) receives nrm, dot."""
+    if (not _f32c(pred, out) or pred.dim() != 4 or pred.shape[0] % 5
+            or tuple(out.shape) != (pred.shape[0] // 5,) + tuple(pred.shape[1:])
+            or not _calg_ws_ok(ws, scalars, out.shape[0], out.shape[1], out.shape[2] * out.shape[3])):
+        raise PdmkError("calg_guidance: pred fp32 [5B, C, H, W], out fp32 [B, C, H, W], contiguous; ws fp64 of "
+                        "calg_workspace_elems, scalars fp32 [2]")
+    B, Cc, H, W = out.shape
+    _chk(_lib.pdmk_calg_guidance(_p(pred), _p(out), B, Cc, H * W, float(guidance_scale), _p(ws), ws.numel(), _p(scalars),
+                                 _st()), "pdmk_calg_guidance")
+
+
+def _calg_step_ok(pred, ld, ws, scalars, sample, table, row, nsteps, state, t_out, x_next, cpad, B, Cc, HW):
+    n, rows = B * Cc * HW, 5 * B * HW
+    return (_calg_ws_ok(ws, scalars, B, Cc, HW) and pred.dtype == x_next.dtype and ld >= Cc and cpad >= Cc
+            and _avail(pred) >= (rows - 1) * ld + Cc and x_next.numel() >= rows * cpad and x_next.is_contiguous()
+            and _f32c(sample) and sample.numel() == n and table.dtype == torch.uint8
+            and table.numel() == nsteps * C.sizeof(row) and state.dtype == torch.int32 and state.numel() == 2
+            and t_out.dtype == torch.int64 and t_out.numel() >= 5 * B)
+
+
+def calg_plms_step(pred, ld, guidance_scale, ws, scalars, sample, cur, ets, table, nsteps, state, t_out, x_next, cpad, B, Cc,
+                   HW):
+    """plms_step with concept-algebra guidance (include/pdmk.h pdmk_calg_plms_step): pred / x_next rows of 5B * HW pixels;
+    ws holds the pairs of calg_dots on the same pred."""
+    n = B * Cc * HW
+    if (not _calg_step_ok(pred, ld, ws, scalars, sample, table, PlmsRow, nsteps, state, t_out, x_next, cpad, B, Cc, HW)
+            or not _f32c(cur, ets) or cur.numel() != n or ets.numel() != 4 * n):
+        raise PdmkError("calg_plms_step: inconsistent buffers")
+    _chk(_lib.pdmk_calg_plms_step(_p(pred), ld, float(guidance_scale), _p(ws), ws.numel(), _p(scalars), _p(sample), _p(cur),
+                                  _p(ets), _p(table), nsteps, _p(state), _p(t_out), _p(x_next), cpad, B, Cc, HW, dt(pred),
+                                  _st()), "pdmk_calg_plms_step")
+
+
+def calg_ddim_step(pred, ld, guidance_scale, ws, scalars, sample, table, nsteps, state, t_out, x_next, cpad, B, Cc, HW):
+    """ddim_step with concept-algebra guidance (include/pdmk.h pdmk_calg_ddim_step); buffers as calg_plms_step, no history."""
+    if not _calg_step_ok(pred, ld, ws, scalars, sample, table, DdimRow, nsteps, state, t_out, x_next, cpad, B, Cc, HW):
+        raise PdmkError("calg_ddim_step: inconsistent buffers")
+    _chk(_lib.pdmk_calg_ddim_step(_p(pred), ld, float(guidance_scale), _p(ws), ws.numel(), _p(scalars), _p(sample), _p(table),
+                                  nsteps, _p(state), _p(t_out), _p(x_next), cpad, B, Cc, HW, dt(pred), _st()),
+         "pdmk_calg_ddim_step")
+
+
 def _u8_shape(src, dst, name):
     B, Cc, H, W = src.shape
     if (src.dtype != torch.float32 or not src.is_contiguous() or dst.dtype != torch.uint8 or not dst.is_contiguous()
@@ -1377,6 +1445,19 @@ def spd_system(g_a, s_a, g_b, s_b, lam, A):
     lda = _f64_matrix(A, n, "spd_system", "A")
     _chk(_lib.pdmk_spd_system_f64(_p(g_a), float(s_a), _p(g_b), float(s_b), float(lam), _p(A), n, lda, _st()),
          "pdmk_spd_system_f64")
+
+
+def pair_gram(z, scale, lam, A):
+    """A = lam I + scale sum_p (z[2p] - z[2p+1]) (z[2p] - z[2p+1])^T in fp64 (include/pdmk.h pdmk_pair_gram_f64): z fp32
+    [2 * npairs, d] and A fp64 [d, d], views with contiguous rows."""
+    if z.dtype != torch.float32 or z.dim() != 2 or z.shape[0] < 2 or z.shape[0] % 2 or z.stride(1) != 1 or z.stride(0) < z.shape[1]:
+        raise PdmkError("pair_gram: z must be an fp32 [2 * npairs, d] view with contiguous rows")
+    d = z.shape[1]
+    if not 1 <= d <= SPD_MAX_N:
+        raise PdmkError(f"pair_gram: d = {d} outside 1 .. {SPD_MAX_N}")
+    lda = _f64_matrix(A, d, "pair_gram", "A")
+    _chk(_lib.pdmk_pair_gram_f64(_p(z), z.stride(0), z.shape[0] // 2, d, float(scale), float(lam), _p(A), lda, _st()),
+         "pdmk_pair_gram_f64")
 
 
 def spd_factor(A, info):

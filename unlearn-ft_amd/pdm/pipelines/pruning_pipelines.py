@@ -18,6 +18,11 @@ does a DDIMScheduler unless the caller passes graph=True (pdmk_ddim_step is then
 Safe Latent Diffusion (`safety_concept=` and the `sld_*` keywords) adds a third row block conditioned on a safety
 concept: the eager loop calls pdmk_sld_guidance before scheduler.step, the captured loop's step kernel is pdmk_sld_plms_step /
 pdmk_sld_ddim_step on 3B rows.  With SLD off nothing of it runs: the same loops, launches and bits as without the keywords.
+
+Concept algebra (`algebra_concepts=` / `algebra_ids=` / `algebra_embeds=`) runs five row blocks - uncond, text
+and three concept prompts - and projects the text score off the direction between the first two concepts: pdmk_calg_dots
+leaves the two sums over the whole batch as fp64 partials, then pdmk_calg_guidance (eager) or pdmk_calg_plms_step /
+pdmk_calg_ddim_step (captured, 5B rows) applies them.  Without the keyword nothing of it runs.
 """
 import ctypes
 import gc
@@ -30,6 +35,7 @@ import torch
 from .. import _pdmk as k
 from ..models.unet.spec import padc
 from ..utils.sld import is_active as sld_is_active
+from ..utils.concept_algebra import check_sampling as check_algebra
 
 
 # Adams-Bashforth weights of the linear multistep update by history length, newest model output first (PLMS)
@@ -222,7 +228,7 @@ class _CapturedLoop:
     steps, N for N DDIM steps), or fewer when the caller stops early.  The graph reads the U-Net's weight arenas in place: it
     stays valid while an optimiser rewrites them."""
 
-    def __init__(self, unet, B, h, w, cfg_on, guidance_scale, nsteps, T, ctx, kind="plms", sld=None):
+    def __init__(self, unet, B, h, w, cfg_on, guidance_scale, nsteps, T, ctx, kind="plms", sld=None, algebra=False):
         dev, dt = unet.device, unet.dtype
         if kind not in ("plms", "ddim"):
             raise ValueError(f"_CapturedLoop: step kind {kind!r}")
@@ -233,7 +239,10 @@ class _CapturedLoop:
         self.sld = sld                  # k.SldParams: the 3B form (uncond, text, safety rows; Safe Latent Diffusion guidance)
         if sld is not None and not cfg_on:
             raise ValueError("_CapturedLoop: SLD needs classifier-free guidance")
-        self.R, self.cp = (3 * B if sld is not None else 2 * B if cfg_on else B), padc(self.C)
+        self.algebra = bool(algebra)    # the 5B form (uncond, text, three concept rows; concept-algebra guidance)
+        if self.algebra and (sld is not None or not cfg_on):
+            raise ValueError("_CapturedLoop: concept algebra needs classifier-free guidance and excludes SLD")
+        self.R, self.cp = (5 * B if self.algebra else 3 * B if sld is not None else 2 * B if cfg_on else B), padc(self.C)
         n = B * self.C * h * w
         self.x = torch.zeros((self.R * h * w, self.cp), device=dev, dtype=dt)
         self.t = torch.zeros(self.R, device=dev, dtype=torch.int64)
@@ -244,6 +253,9 @@ class _CapturedLoop:
             self.ets = torch.zeros(4, n, device=dev)
         if sld is not None:
             self.mom = torch.zeros(n, device=dev)
+        if self.algebra:
+            self.ws = torch.zeros(k.calg_workspace_elems(B, self.C, h * w), device=dev, dtype=torch.float64)
+            self.scalars = torch.zeros(2, device=dev)
         self.state = torch.zeros(2, device=dev, dtype=torch.int32)
         self.table = torch.zeros(nsteps * ctypes.sizeof(self.Row), device=dev, dtype=torch.uint8)
         self.graph, self.keep = None, []
@@ -251,7 +263,15 @@ class _CapturedLoop:
 
     def _body(self):
         pred, _ = self.unet.forward_nhwc(self.x, self.t, self.ehs, self.R, self.h, self.w, train=False)
-        if self.sld is not None:
+        if self.algebra:
+            k.calg_dots(pred.t, pred.t.stride(0), self.B, self.C, self.h * self.w, self.ws)
+            if self.kind == "plms":
+                k.calg_plms_step(pred.t, pred.t.stride(0), self.g[1], self.ws, self.scalars, self.sample, self.cur, self.ets,
+                                 self.table, self.nsteps, self.state, self.t, self.x, self.cp, self.B, self.C, self.h * self.w)
+            else:
+                k.calg_ddim_step(pred.t, pred.t.stride(0), self.g[1], self.ws, self.scalars, self.sample, self.table,
+                                 self.nsteps, self.state, self.t, self.x, self.cp, self.B, self.C, self.h * self.w)
+        elif self.sld is not None:
             if self.kind == "plms":
                 k.sld_plms_step(pred.t, pred.t.stride(0), self.g[1], self.sld, self.mom, self.sample, self.cur, self.ets,
                                 self.table, self.nsteps, self.state, self.t, self.x, self.cp, self.B, self.C, self.h * self.w)
@@ -304,7 +324,7 @@ class _CapturedLoop:
 
     def run(self, latents, ehs, rows, n_calls=None):
         """latents: fp32 [B, C, h, w] (contiguous, on the device); ehs: [R, T, ctx] text embeddings (unconditional half
-        first, with SLD the safety third last); rows: the scheduler's plms_rows() / ddim_rows(); n_calls: U-Net calls to
+        first, with SLD the safety third last, with concept algebra the three concepts last); rows: the scheduler's plms_rows() / ddim_rows(); n_calls: U-Net calls to
         replay (None: all of them).  Returns the latents after them (a new tensor)."""
         B, C, HW = self.B, self.C, self.h * self.w
         n_calls = self.nsteps if n_calls is None else int(n_calls)
@@ -319,6 +339,9 @@ class _CapturedLoop:
         if self.sld is not None:
             k.nchw_to_nhwc(latents, self.x[2 * B * HW:], B, C, HW, self.cp)
             self.mom.zero_()
+        if self.algebra:
+            for j in range(2, 5):
+                k.nchw_to_nhwc(latents, self.x[j * B * HW:], B, C, HW, self.cp)
         self.t.fill_(rows[0].t)
         self.state.zero_()
         for _ in range(n_calls):
@@ -375,16 +398,19 @@ class StableDiffusionPruningPipeline:
             return False
         return graph is True or os.environ.get("PDMK_SAMPLER_GRAPH", "1") != "0"
 
-    def _loop(self, B, h, w, cfg_on, guidance_scale, nsteps, T, ctx, sld=None):
+    def _loop(self, B, h, w, cfg_on, guidance_scale, nsteps, T, ctx, sld=None, algebra=False):
         key = (B, h, w, self.unet.dtype, cfg_on, nsteps, T, ctx, float(guidance_scale), type(self.scheduler))
         if sld is not None:
             key += ("sld",) + sld.key()
+        if algebra:
+            key += ("algebra",)
         loop = self._loops.pop(key, None)
         if loop is None:
             while len(self._loops) >= self.GRAPH_SHAPES:
                 self._loops.pop(next(iter(self._loops))).close()
             loop = _CapturedLoop(self.unet, B, h, w, cfg_on, guidance_scale, nsteps, T, ctx,
-                                 kind="ddim" if type(self.scheduler) is DDIMScheduler else "plms", sld=sld)
+                                 kind="ddim" if type(self.scheduler) is DDIMScheduler else "plms", sld=sld,
+                                 algebra=algebra)
             self.captures += 1
         self._loops[key] = loop                                       # most recently used last
         return loop
@@ -395,7 +421,8 @@ class StableDiffusionPruningPipeline:
                          negative_prompt_embeds=None, output_type="np", return_dict=True, callback=None, callback_steps=1,
                          prompt=None, negative_prompt=None, graph=None, end_iteration=None, safety_concept=None,
                          safety_concept_ids=None, safety_concept_embeds=None, sld_guidance_scale=1000.0, sld_warmup_steps=10,
-                         sld_threshold=0.01, sld_momentum_scale=0.3, sld_mom_beta=0.4):
+                         sld_threshold=0.01, sld_momentum_scale=0.3, sld_mom_beta=0.4, algebra_concepts=None,
+                         algebra_ids=None, algebra_embeds=None):
         """prompt / negative_prompt: strings or lists of strings (needs the tokenizer; with guidance and no negative prompt
         the empty prompt).  output_type "latent", "pt", "np" (float32 NHWC in [0, 1]), "u8" (uint8 NHWC numpy, the FID
         script's `(img * 255).astype(np.uint8)`, formed on the device) or "u8_round" (the same with diffusers' numpy_to_pil
@@ -408,8 +435,19 @@ class StableDiffusionPruningPipeline:
         from the guidance where the text prediction leans towards it (include/pdmk.h pdmk_sld_params; the five sld_* keywords
         default to diffusers' StableDiffusionPipelineSafe's, the Medium preset of configs/baselines/sld.yaml).  Active only
         with a concept, sld_guidance_scale > 1 and guidance_scale > 1; otherwise the keywords change nothing.  The concept is
-        encoded once per call and repeated over the batch; the warm-up counts U-Net calls (PNDM's repeated call included)."""
+        encoded once per call and repeated over the batch; the warm-up counts U-Net calls (PNDM's repeated call included).
+        algebra_concepts (three strings, needs the tokenizer) / algebra_ids ([3, T] token ids) / algebra_embeds
+        ([3, T, ctx]): concept algebra - three further U-Net branches p0, p1, p2; the text score loses its component along
+        p1 - p0, measured against p2, over the whole batch (include/pdmk.h "Concept algebra").  Exactly three concepts, each
+        encoded once per call and repeated over the batch; ValueError together with a safety concept or when
+        guidance_scale <= 1."""
         cfg_on = guidance_scale > 1.0
+        algebra = algebra_concepts is not None or algebra_ids is not None or algebra_embeds is not None
+        if algebra:
+            check_algebra(guidance_scale, safety_concept is not None or safety_concept_ids is not None
+                          or safety_concept_embeds is not None,
+                          algebra_embeds if algebra_embeds is not None else algebra_ids if algebra_ids is not None
+                          else algebra_concepts)
         has_concept = safety_concept is not None or safety_concept_ids is not None or safety_concept_embeds is not None
         sld = None
         if sld_is_active(guidance_scale, sld_guidance_scale, has_concept):
@@ -439,6 +477,8 @@ class StableDiffusionPruningPipeline:
         ehs = torch.cat([negative_prompt_embeds.to(dev), prompt_embeds.to(dev)]) if cfg_on else prompt_embeds.to(dev)
         if sld is not None:
             ehs = torch.cat([ehs, self._safety_embeds(safety_concept, safety_concept_ids, safety_concept_embeds, B, ehs)])
+        if algebra:
+            ehs = torch.cat([ehs, self._algebra_embeds(algebra_concepts, algebra_ids, algebra_embeds, B, ehs)])
         sch = self.scheduler
         sch.set_timesteps(num_inference_steps, device=dev)
         C = self.unet.cfg.in_channels
@@ -450,12 +490,12 @@ class StableDiffusionPruningPipeline:
             raise ValueError(f"end_iteration={end_iteration} outside 0 ... {len(sch.timesteps)}")
         if self._use_graph(graph, callback):
             loop = self._loop(B, shape[2], shape[3], cfg_on, guidance_scale, len(sch.timesteps), ehs.shape[1], ehs.shape[2],
-                              sld=sld)
+                              sld=sld, algebra=algebra)
             rows = sch.ddim_rows() if loop.kind == "ddim" else sch.plms_rows()
             latents = loop.run(latents, ehs, rows, n_calls=end_iteration)
         else:
             latents = self._eager_loop(latents, ehs, B, shape, cfg_on, guidance_scale, callback, callback_steps, end_iteration,
-                                       sld=sld)
+                                       sld=sld, algebra=algebra)
         if output_type == "latent":
             image = latents
         else:
@@ -488,14 +528,28 @@ class StableDiffusionPruningPipeline:
                              f"{(1,) + tuple(ehs.shape[1:])}")
         return embeds.to(ehs.dtype).expand(B, -1, -1)
 
+    def _algebra_embeds(self, concepts, ids, embeds, B, ehs):
+        """The three concepts' text embeddings [3B, T, ctx], concept-major: each encoded once, repeated over the batch."""
+        if embeds is None:
+            if ids is None:
+                ids = self._tokenize(list(concepts))
+            embeds = self.text_encoder(ids.to(self.device))[0]
+        embeds = embeds.to(self.device)
+        if embeds.dim() != 3 or embeds.shape[0] != 3 or tuple(embeds.shape[1:]) != tuple(ehs.shape[1:]):
+            raise ValueError(f"concept-algebra embeddings {tuple(embeds.shape)}: expected three concepts of shape "
+                             f"{(3,) + tuple(ehs.shape[1:])}")
+        return embeds.to(ehs.dtype)[:, None].expand(3, B, -1, -1).reshape((3 * B,) + tuple(ehs.shape[1:]))
+
     def _eager_loop(self, latents, ehs, B, shape, cfg_on, guidance_scale, callback, callback_steps, end_iteration=None,
-                    sld=None):
+                    sld=None, algebra=False):
         dev, sch = self.device, self.scheduler
         was_training = self.unet.training
         self.unet.eval()
         try:
-            x2 = torch.empty((3 * B if sld is not None else 2 * B if cfg_on else B,) + shape[1:], device=dev,
-                             dtype=torch.float32)
+            x2 = torch.empty((5 * B if algebra else 3 * B if sld is not None else 2 * B if cfg_on else B,) + shape[1:],
+                             device=dev, dtype=torch.float32)
+            if algebra:
+                ws = torch.zeros(k.calg_workspace_elems(*shape[:2], shape[2] * shape[3]), device=dev, dtype=torch.float64)
             if sld is not None:
                 mom = torch.zeros(shape, device=dev, dtype=torch.float32)
             for i, t in enumerate(sch.timesteps.tolist()[:end_iteration]):
@@ -504,9 +558,17 @@ class StableDiffusionPruningPipeline:
                     x2[B:2 * B].copy_(latents)
                 if sld is not None:
                     x2[2 * B:].copy_(latents)
+                if algebra:
+                    for j in range(2, 5):
+                        x2[j * B:(j + 1) * B].copy_(latents)
                 tt = torch.full((x2.shape[0],), t, device=dev, dtype=torch.int64)
                 out = self.unet(sch.scale_model_input(x2, t), tt, ehs, return_dict=False)[0]
-                if sld is not None:
+                if algebra:       # the two sums over the whole batch, then the projection and the guidance
+                    out = out.contiguous()
+                    noise = torch.empty(shape, device=dev, dtype=torch.float32)
+                    k.calg_dots(out, 1, B, 1, shape[1] * shape[2] * shape[3], ws)
+                    k.calg_guidance(out, noise, guidance_scale, ws)
+                elif sld is not None:
                     noise = torch.empty(shape, device=dev, dtype=torch.float32)
                     k.sld_guidance(out.contiguous(), noise, mom, guidance_scale, sld, i >= sld.warmup_steps)
                 elif cfg_on:      # uncond + g (text - uncond) = (1 - g) uncond + g text, in place on the text half

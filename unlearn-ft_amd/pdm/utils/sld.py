@@ -66,18 +66,20 @@ def with_suffix(name, sld_type):
     return name if sld_type is None else f"{name}_SLD_{sld_type}"
 
 
-def sample_cases(pipe, prompts_path, folder, from_case=0, till_case=None, num_samples=1, **sampling):
+def sample_cases(pipe, prompts_path, folder, from_case=0, till_case=None, num_samples=1, prompt_kwargs=None, **sampling):
     """The row loop of the reference's sld-generate-images.py and generate-images.py: per row of the prompt CSV
     `torch.Generator(device).manual_seed(evaluation_seed)`, `num_samples` images of the prompt as one batch (`sampling`: the
     keywords of the pipeline call), uint8 as diffusers' numpy_to_pil (rounded), written to <folder>/<case_number>_<n>.png.
-    Returns the paths written, in order."""
+    prompt_kwargs: callable(prompt, num_samples) -> the pipeline keywords that stand for the prompt (debias-VL passes
+    transformed embeddings); None: `prompt=[prompt] * num_samples`.  Returns the paths written, in order."""
     import torch
     from PIL import Image
     os.makedirs(folder, exist_ok=True)
     written = []
     for case_number, prompt, seed in read_cases(prompts_path, from_case, till_case):
         gen = torch.Generator(device=pipe.device).manual_seed(seed)
-        images = pipe(prompt=[prompt] * num_samples, generator=gen, output_type="u8_round", **sampling).images
+        text = dict(prompt=[prompt] * num_samples) if prompt_kwargs is None else prompt_kwargs(prompt, num_samples)
+        images = pipe(generator=gen, output_type="u8_round", **text, **sampling).images
         for num, im in enumerate(images):
             written.append(os.path.join(folder, image_name(case_number, num)))
             Image.fromarray(im).save(written[-1])
