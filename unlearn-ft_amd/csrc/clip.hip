@@ -5,6 +5,8 @@
 //   pdmk_quick_gelu_fwd : x * sigmoid(1.702 x) (transformers' QuickGELUActivation, OpenAI CLIP's MLP activation).
 //   pdmk_gather_rows    : one row per sequence: row 0 (CLS) or the row at the first argmax of the token ids (EOT).
 //   pdmk_clip_score_head: row L2 normalisation in fp32 and the sum of the per-row cosines into an fp64 accumulator.
+// tests/test_encoder_forms_gpu.py restates grid_for's cap (8192) and test_restated_constants_are_the_sources matches it against
+// this text: change the two together.
 #include "vec.h"
 
 namespace {

@@ -5,6 +5,8 @@
 //                        pass (the U-Net's flash kernels are specialised for head dim 64).
 //   pdmk_latent_sample : DiagonalGaussianDistribution.sample() * scaling_factor on NHWC moments -> NCHW fp32 latents.
 //   pdmk_embed_tokens  : CLIP text embeddings, token row + position row.
+// tests/test_encoder_forms_gpu.py restates the softmax form thresholds and the grid caps (4096 / 8192) below, and
+// test_restated_constants_are_the_sources matches them against this text: change the two together.
 #include "vec.h"
 
 namespace {

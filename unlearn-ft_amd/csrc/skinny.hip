@@ -5,6 +5,8 @@
 //   pdmk_skinny_wgrad: dw[n][k] += sum_m dy[m][n] x[m][k],  dbias[n] += sum_m dy[m][n]
 // The skinny operand lives in LDS (<= 64 KiB), every weight byte is read exactly once with 16-byte loads: HBM/L2
 // streaming bound (a 1280x1280 bf16 weight = 3.3 MB).
+// tests/test_skinny_forms_gpu.py restates the launch rule below (MMAX, NPW, MR, the 1024-block cap, the loop strides, the LDS
+// limits) and test_restated_constants_are_the_sources matches it against this text: change the two together.
 #include "vec.h"
 
 namespace {
