@@ -351,8 +351,10 @@ template <typename T> int pool(const void* src, void* dst, int B, int H, int W, 
 }
 
 // ------------------------------------------------------------------------------------------------ timestep embedding
-template <typename T>
-__global__ void temb_kernel(const int64_t* __restrict__ t, const float* __restrict__ freqs, T* __restrict__ out, int B,
+// TS: the timestep type, int64 (training, PNDM / DDIM sampling) or float (K-LMS's fractional timesteps); an integral float
+// below 2^24 converts to the same fp32 value as the int64, so both give the same bits there
+template <typename T, typename TS>
+__global__ void temb_kernel(const TS* __restrict__ t, const float* __restrict__ freqs, T* __restrict__ out, int B,
                             int dim) {
     const int half = dim / 2;
     const int total = B * half;
@@ -362,6 +364,11 @@ __global__ void temb_kernel(const int64_t* __restrict__ t, const float* __restri
         out[(long)b * dim + j] = from_f32<T>(cosf(arg));
         out[(long)b * dim + half + j] = from_f32<T>(sinf(arg));
     }
+}
+
+// y = x / div: one correctly rounded fp32 division per element (a true division, not a multiplication by 1 / div)
+__global__ void scale_div_kernel(const float* __restrict__ x, float* __restrict__ y, long n, float div) {
+    for (long i = blockIdx.x * (long)NT + threadIdx.x; i < n; i += (long)gridDim.x * NT) y[i] = x[i] / div;
 }
 
 // ------------------------------------------------------------------------------------------------ forward diffusion
@@ -924,13 +931,27 @@ extern "C" int pdmk_pool2x2_sum(const void* src, void* dst, int B, int H, int W,
     if (!src || !dst || B <= 0 || H <= 0 || W <= 0 || C <= 0) return -1;
     PDMK_DISPATCH(dtype, pool, src, dst, B, H, W, C, (hipStream_t)s);
 }
-extern "C" int pdmk_timestep_embed(const int64_t* t, const float* freqs, void* out, int B, int dim, int dtype,
-                                   pdmk_stream s) {
+template <typename TS>
+static int timestep_embed(const TS* t, const float* freqs, void* out, int B, int dim, int dtype, pdmk_stream s) {
     if (!t || !freqs || !out || B <= 0 || dim <= 0 || (dim & 1)) return -1;
     dim3 grid(grid_for((long)B * dim / 2));
-    if (dtype == PDMK_BF16) hipLaunchKernelGGL(temb_kernel<bf16>, grid, dim3(NT), 0, (hipStream_t)s, t, freqs, (bf16*)out, B, dim);
-    else if (dtype == PDMK_F32) hipLaunchKernelGGL(temb_kernel<float>, grid, dim3(NT), 0, (hipStream_t)s, t, freqs, (float*)out, B, dim);
+    if (dtype == PDMK_BF16) hipLaunchKernelGGL((temb_kernel<bf16, TS>), grid, dim3(NT), 0, (hipStream_t)s, t, freqs, (bf16*)out, B, dim);
+    else if (dtype == PDMK_F32) hipLaunchKernelGGL((temb_kernel<float, TS>), grid, dim3(NT), 0, (hipStream_t)s, t, freqs, (float*)out, B, dim);
     else return -2;
+    PDMK_CHECK_LAUNCH();
+    return 0;
+}
+extern "C" int pdmk_timestep_embed(const int64_t* t, const float* freqs, void* out, int B, int dim, int dtype,
+                                   pdmk_stream s) {
+    return timestep_embed(t, freqs, out, B, dim, dtype, s);
+}
+extern "C" int pdmk_timestep_embed_f32(const float* t, const float* freqs, void* out, int B, int dim, int dtype,
+                                       pdmk_stream s) {
+    return timestep_embed(t, freqs, out, B, dim, dtype, s);
+}
+extern "C" int pdmk_scale_div(const float* x, float* y, float div, int64_t n, pdmk_stream s) {
+    if (!x || !y || n <= 0) return -1;
+    hipLaunchKernelGGL(scale_div_kernel, dim3(grid_for(n)), dim3(NT), 0, (hipStream_t)s, x, y, (long)n, div);
     PDMK_CHECK_LAUNCH();
     return 0;
 }

@@ -14,8 +14,10 @@
 // (sld_chain below: plain fp32 operations, no fma) in place of the axpby; pdmk_sld_guidance is that chain alone, for the
 // eager loop.  pdmk_calg_plms_step / pdmk_calg_ddim_step are the same two launches with concept algebra's score projection on
 // five branches (calg_chain below); its two scalars come from the fp64 partial sums that pdmk_calg_dots leaves, summed again
-// by every workgroup in one fixed order.  pdmk_calg_guidance is that chain alone.  All six step entry points are instances of
-// one kernel (step_kernel<T, Guide, Sched>).
+// by every workgroup in one fixed order.  pdmk_calg_guidance is that chain alone.  pdmk_lms_step / pdmk_sld_lms_step /
+// pdmk_calg_lms_step are the launches for LMSDiscreteScheduler.step (K-LMS): the derivative and the update are axpby forms, and
+// the next U-Net input is divided by sqrt(sigma^2 + 1) in the same launch (scale_model_input).  All nine step entry points are
+// instances of one kernel (step_kernel<T, Guide, Sched>).
 #include "common.h"
 
 #pragma clang fp contract(off)
@@ -132,7 +134,9 @@ struct PlmsSched {
     float* cur;
     float* ets;
     const pdmk_plms_row* table;
+    using time_type = int64_t;
     __device__ int64_t t(int step) const { return table[step].t; }
+    __device__ float next_input(int, float prev) const { return prev; }
     __device__ float operator()(int step, float g, long i, long N) const {
         const pdmk_plms_row& r = table[step];
         float eps, base = sample[i];
@@ -159,7 +163,9 @@ struct PlmsSched {
 struct DdimSched {
     float* sample;
     const pdmk_ddim_row* table;
+    using time_type = int64_t;
     __device__ int64_t t(int step) const { return table[step].t; }
+    __device__ float next_input(int, float prev) const { return prev; }
     __device__ float operator()(int step, float g, long i, long) const {
         const float prev = form(table[step].c_m, g, table[step].c_x, sample[i]);      // axpby(model_output, prev, c_m, c_x)
         sample[i] = prev;
@@ -167,11 +173,37 @@ struct DdimSched {
     }
 };
 
+// K-LMS (LMSDiscreteScheduler.step): the derivative d of this step goes into the 4-slot history, the update is the chain
+// prev = sample + sum_j coef[j] d_{i-j}, newest first, each term one axpby.  An element's history is read and written by the
+// thread that owns the element only.  The next U-Net input is scale_model_input of the NEXT step: prev / sqrt(sigma^2 + 1),
+// one fp32 division.
+struct LmsSched {
+    float* sample;
+    float* hist;
+    const pdmk_lms_row* table;
+    using time_type = float;
+    __device__ float t(int step) const { return table[step].t; }
+    __device__ float next_input(int step, float prev) const { return prev / table[step].in_div; }
+    __device__ float operator()(int step, float g, long i, long N) const {
+        const pdmk_lms_row& r = table[step];
+        const float base = sample[i];
+        const float d = r.dmode ? form(r.d_x, base, r.d_m, g) : g;     // v_prediction: sigma / (sigma^2 + 1) x + v / sqrt(sigma^2 + 1)
+        hist[(r.wslot & 3) * N + i] = d;                                // (slots masked: a bad table cannot leave hist)
+        float prev = form(r.coef[0], d, 1.f, base);
+        const int nterms = min(r.nterms, 4);
+        for (int j = 1; j < nterms; ++j) prev = form(r.coef[j], hist[(r.rslot[j - 1] & 3) * N + i], 1.f, prev);
+        sample[i] = prev;
+        return prev;
+    }
+};
+
 // One launch between two U-Net calls: guidance, scheduler step, the next call's input (one copy per branch) and timesteps,
-// and the step counter.  pdmk_plms_step, pdmk_ddim_step and their SLD and concept-algebra forms are its six instances per dtype.
+// and the step counter.  pdmk_plms_step, pdmk_ddim_step, pdmk_lms_step and their SLD and concept-algebra forms are its nine
+// instances per dtype.  The scheduler types the timesteps (time_type) and maps the new sample to the next input (next_input).
 template <typename T, typename Guide, typename Sched>
 __global__ void step_kernel(const T* __restrict__ pred, int ld, Guide guide, Sched sched, int nsteps, int32_t* state,
-                            int64_t* __restrict__ t_out, T* __restrict__ x_next, int cpad, int B, int C, int HW) {
+                            typename Sched::time_type* __restrict__ t_out, T* __restrict__ x_next, int cpad, int B, int C,
+                            int HW) {
     const int step = state[0];
     if (step < 0 || step >= nsteps) return;          // every workgroup reads the same counter: all of them return
     const long N = (long)B * C * HW;                 // one history slot
@@ -186,7 +218,7 @@ __global__ void step_kernel(const T* __restrict__ pred, int ld, Guide guide, Sch
         for (int c = 0; c < C; ++c) {
             const long i = ((long)b * C + c) * HW + px;               // NCHW index of the latent element
             const float prev = sched(step, guide(pred, ld, p, npix, c, i, step), i, N);
-            const T o = from_f32<T>(prev);
+            const T o = from_f32<T>(sched.next_input(step, prev));    // (the identity but for K-LMS's input scaling)
             for (int k = 0; k < copies; ++k) xo[k * part + c] = o;
         }
         for (int c = C; c < cpad; ++c)                                // padding channels, as nchw2nhwc_kernel leaves them
@@ -211,8 +243,8 @@ __global__ void step_kernel(const T* __restrict__ pred, int ld, Guide guide, Sch
 }
 
 template <typename Guide, typename Sched>
-int launch_step(const void* pred, int ld, const Guide& guide, const Sched& sched, int nsteps, int32_t* state, int64_t* t_out,
-                void* x_next, int cpad, int B, int C, int HW, int dtype, pdmk_stream s) {
+int launch_step(const void* pred, int ld, const Guide& guide, const Sched& sched, int nsteps, int32_t* state,
+                typename Sched::time_type* t_out, void* x_next, int cpad, int B, int C, int HW, int dtype, pdmk_stream s) {
     const dim3 grid(grid_for((long)B * HW));
     if (dtype == PDMK_BF16)
         hipLaunchKernelGGL((step_kernel<bf16, Guide, Sched>), grid, dim3(NT), 0, (hipStream_t)s, (const bf16*)pred, ld, guide,
@@ -441,6 +473,37 @@ extern "C" int pdmk_calg_ddim_step(const void* pred, int ld, float guidance_scal
         return -1;
     return launch_step(pred, ld, CalgGuide{guidance_scale, ws, calg_parts((long)B * C * HW), scalars, {0.f, 0.f}},
                        DdimSched{sample, table}, nsteps, state, t_out, x_next, cpad, B, C, HW, dtype, s);
+}
+
+extern "C" int pdmk_lms_step(const void* pred, int ld, float g_u, float g_t, int cfg, float* sample, float* hist,
+                             const pdmk_lms_row* table, int nsteps, int32_t* state, float* t_out, void* x_next, int cpad, int B,
+                             int C, int HW, int dtype, pdmk_stream s) {
+    if (!pred || !sample || !hist || !table || !state || !t_out || !x_next || nsteps <= 0 || B <= 0 || C <= 0 || HW <= 0 ||
+        ld < C || cpad < C)
+        return -1;
+    return launch_step(pred, ld, CfgGuide{g_u, g_t, cfg}, LmsSched{sample, hist, table}, nsteps, state, t_out, x_next, cpad, B,
+                       C, HW, dtype, s);
+}
+
+extern "C" int pdmk_sld_lms_step(const void* pred, int ld, float guidance_scale, const pdmk_sld_params* params, float* mom,
+                                 float* sample, float* hist, const pdmk_lms_row* table, int nsteps, int32_t* state, float* t_out,
+                                 void* x_next, int cpad, int B, int C, int HW, int dtype, pdmk_stream s) {
+    if (!pred || !params || !mom || !sample || !hist || !table || !state || !t_out || !x_next || nsteps <= 0 || B <= 0 ||
+        C <= 0 || HW <= 0 || ld < C || cpad < C)
+        return -1;
+    return launch_step(pred, ld, SldGuide{guidance_scale, *params, mom}, LmsSched{sample, hist, table}, nsteps, state, t_out,
+                       x_next, cpad, B, C, HW, dtype, s);
+}
+
+extern "C" int pdmk_calg_lms_step(const void* pred, int ld, float guidance_scale, const double* ws, int64_t ws_elems,
+                                  float* scalars, float* sample, float* hist, const pdmk_lms_row* table, int nsteps,
+                                  int32_t* state, float* t_out, void* x_next, int cpad, int B, int C, int HW, int dtype,
+                                  pdmk_stream s) {
+    if (!pred || !ws || !sample || !hist || !table || !state || !t_out || !x_next || nsteps <= 0 || B <= 0 || C <= 0 ||
+        HW <= 0 || ld < C || cpad < C || ((uintptr_t)ws & 7) || ws_elems < pdmk_calg_workspace_elems(B, C, HW))
+        return -1;
+    return launch_step(pred, ld, CalgGuide{guidance_scale, ws, calg_parts((long)B * C * HW), scalars, {0.f, 0.f}},
+                       LmsSched{sample, hist, table}, nsteps, state, t_out, x_next, cpad, B, C, HW, dtype, s);
 }
 
 extern "C" int pdmk_image_to_u8_ex(const float* src, uint8_t* dst, int B, int C, int HW, int rounding, pdmk_stream s) {

@@ -58,6 +58,12 @@ class DdimRow(C.Structure):
     _fields_ = [("t", i64), ("c_x", f32), ("c_m", f32), ("pad_", i64)]
 
 
+class LmsRow(C.Structure):
+    """pdmk_lms_row (include/pdmk.h): one step of the fused guidance + K-LMS update."""
+    _fields_ = [("t", f32), ("nterms", i32), ("wslot", i32), ("rslot", i32 * 3), ("coef", f32 * 4), ("d_x", f32), ("d_m", f32),
+                ("dmode", i32), ("in_div", f32), ("pad_", i32 * 2)]
+
+
 class SldParams(C.Structure):
     """pdmk_sld_params (include/pdmk.h): Safe Latent Diffusion's scalars as the kernels take them.  Build it with
     sld_params(): the fp32 fields are rounded from doubles, one_minus_beta from the double 1 - mom_beta."""
@@ -105,6 +111,8 @@ _SIGS = {
     "pdmk_colsum": ([vp, vp, i64, i32, i32, i32, i32, i32, i32, vp], i32),
     "pdmk_pool2x2_sum": ([vp, vp, i32, i32, i32, i32, i32, vp], i32),
     "pdmk_timestep_embed": ([vp, vp, vp, i32, i32, i32, vp], i32),
+    "pdmk_timestep_embed_f32": ([vp, vp, vp, i32, i32, i32, vp], i32),
+    "pdmk_scale_div": ([vp, vp, f32, i64, vp], i32),
     "pdmk_add_noise_velocity": ([vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp], i32),
     "pdmk_nchw_to_nhwc": ([vp, vp, i32, i32, i32, i32, i32, vp], i32),
     "pdmk_nhwc_to_nchw": ([vp, vp, i32, i32, i32, i32, i32, vp], i32),
@@ -144,6 +152,10 @@ _SIGS = {
     "pdmk_calg_guidance": ([vp, vp, i32, i32, i32, f32, vp, i64, vp, vp], i32),
     "pdmk_calg_plms_step": ([vp, i32, f32, vp, i64, vp, vp, vp, vp, vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, vp], i32),
     "pdmk_calg_ddim_step": ([vp, i32, f32, vp, i64, vp, vp, vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, vp], i32),
+    "pdmk_lms_step": ([vp, i32, f32, f32, i32, vp, vp, vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, vp], i32),
+    "pdmk_sld_lms_step": ([vp, i32, f32, C.POINTER(SldParams), vp, vp, vp, vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, vp],
+                          i32),
+    "pdmk_calg_lms_step": ([vp, i32, f32, vp, i64, vp, vp, vp, vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, vp], i32),
     "pdmk_image_to_u8": ([vp, vp, i32, i32, i32, vp], i32),
     "pdmk_image_to_u8_ex": ([vp, vp, i32, i32, i32, i32, vp], i32),
     "pdmk_resize_bilinear_u8": ([vp, i64, vp, vp, i32, i32, vp, vp], i32),
@@ -842,7 +854,20 @@ def pool2x2_sum(src, dst, B, H, W, Cc):
 
 
 def timestep_embed(t, freqs, out, B, dim):
-    _chk(_lib.pdmk_timestep_embed(_p(t), _p(freqs), _p(out), B, dim, dt(out), _st()), "pdmk_timestep_embed")
+    """t int64 [B] (pdmk_timestep_embed) or float32 [B] (pdmk_timestep_embed_f32: K-LMS's fractional timesteps)."""
+    if t.dtype == torch.int64:
+        _chk(_lib.pdmk_timestep_embed(_p(t), _p(freqs), _p(out), B, dim, dt(out), _st()), "pdmk_timestep_embed")
+    elif t.dtype == torch.float32:
+        _chk(_lib.pdmk_timestep_embed_f32(_p(t), _p(freqs), _p(out), B, dim, dt(out), _st()), "pdmk_timestep_embed_f32")
+    else:
+        raise PdmkError(f"timestep_embed: timesteps are int64 or float32, not {t.dtype}")
+
+
+def scale_div(x, y, div):
+    """y = x / div on contiguous fp32 tensors of one size: one fp32 division per element (pdmk_scale_div)."""
+    if not _f32c(x, y) or x.numel() != y.numel() or x.numel() == 0:
+        raise PdmkError("scale_div: x, y fp32 contiguous of one size")
+    _chk(_lib.pdmk_scale_div(_p(x), _p(y), float(div), x.numel(), _st()), "pdmk_scale_div")
 
 
 def add_noise_velocity(x0, noise, t, sa, sb, noisy, target, B, Cc, HW, cpad):
@@ -982,6 +1007,27 @@ def ddim_step(pred, ld, g_u, g_t, cfg, sample, table, nsteps, state, t_out, x_ne
                              _p(t_out), _p(x_next), cpad, B, Cc, HW, dt(pred), _st()), "pdmk_ddim_step")
 
 
+def lms_table(rows, device):
+    """A list of LmsRow -> the uint8 device tensor pdmk_lms_step reads (one host-to-device copy)."""
+    arr = (LmsRow * len(rows))(*rows)
+    return torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(device)
+
+
+def lms_step(pred, ld, g_u, g_t, cfg, sample, hist, table, nsteps, state, t_out, x_next, cpad, B, Cc, HW):
+    """One fused guidance + K-LMS step (include/pdmk.h pdmk_lms_step).  pred / x_next in the engine dtype; sample fp32
+    [B*Cc*HW]; hist fp32 [4, B*Cc*HW]; table from lms_table() with nsteps rows; state int32 [2]; t_out FLOAT32."""
+    n = B * Cc * HW
+    rows = (2 * B if cfg else B) * HW
+    if (pred.dtype != x_next.dtype or ld < Cc or cpad < Cc or _avail(pred) < (rows - 1) * ld + Cc
+            or x_next.numel() < rows * cpad or not x_next.is_contiguous() or not _f32c(sample, hist) or sample.numel() != n
+            or hist.numel() != 4 * n or table.dtype != torch.uint8 or table.numel() != nsteps * C.sizeof(LmsRow)
+            or state.dtype != torch.int32 or state.numel() != 2 or t_out.dtype != torch.float32
+            or t_out.numel() < (2 * B if cfg else B)):
+        raise PdmkError("lms_step: inconsistent buffers")
+    _chk(_lib.pdmk_lms_step(_p(pred), ld, float(g_u), float(g_t), int(bool(cfg)), _p(sample), _p(hist), _p(table), nsteps,
+                            _p(state), _p(t_out), _p(x_next), cpad, B, Cc, HW, dt(pred), _st()), "pdmk_lms_step")
+
+
 def sld_params(sld_guidance_scale, warmup_steps, threshold, momentum_scale, mom_beta):
     """The five SLD scalars (Python numbers, i.e. doubles) -> SldParams: each rounded once to fp32, `1 - mom_beta` formed in
     double first - what torch does with a Python scalar operand of an fp32 tensor."""
@@ -1005,13 +1051,13 @@ def sld_guidance(pred, out, mom, guidance_scale, params, apply):
                                 int(bool(apply)), _st()), "pdmk_sld_guidance")
 
 
-def _sld_step_ok(pred, ld, params, mom, sample, table, row, nsteps, state, t_out, x_next, cpad, B, Cc, HW):
+def _sld_step_ok(pred, ld, params, mom, sample, table, row, nsteps, state, t_out, x_next, cpad, B, Cc, HW, tdtype=torch.int64):
     n, rows = B * Cc * HW, 3 * B * HW
     return (isinstance(params, SldParams) and pred.dtype == x_next.dtype and ld >= Cc and cpad >= Cc
             and _avail(pred) >= (rows - 1) * ld + Cc and x_next.numel() >= rows * cpad and x_next.is_contiguous()
             and _f32c(mom, sample) and mom.numel() == n and sample.numel() == n and table.dtype == torch.uint8
             and table.numel() == nsteps * C.sizeof(row) and state.dtype == torch.int32 and state.numel() == 2
-            and t_out.dtype == torch.int64 and t_out.numel() >= 3 * B)
+            and t_out.dtype == tdtype and t_out.numel() >= 3 * B)
 
 
 def sld_plms_step(pred, ld, guidance_scale, params, mom, sample, cur, ets, table, nsteps, state, t_out, x_next, cpad, B, Cc,
@@ -1033,6 +1079,17 @@ def sld_ddim_step(pred, ld, guidance_scale, params, mom, sample, table, nsteps, 
         raise PdmkError("sld_ddim_step: inconsistent buffers")
     _chk(_lib.pdmk_sld_ddim_step(_p(pred), ld, float(guidance_scale), C.byref(params), _p(mom), _p(sample), _p(table), nsteps,
                                  _p(state), _p(t_out), _p(x_next), cpad, B, Cc, HW, dt(pred), _st()), "pdmk_sld_ddim_step")
+
+
+def sld_lms_step(pred, ld, guidance_scale, params, mom, sample, hist, table, nsteps, state, t_out, x_next, cpad, B, Cc, HW):
+    """lms_step with SLD guidance (include/pdmk.h pdmk_sld_lms_step); buffers as sld_plms_step, hist fp32 [4, B*Cc*HW],
+    t_out float32."""
+    if (not _sld_step_ok(pred, ld, params, mom, sample, table, LmsRow, nsteps, state, t_out, x_next, cpad, B, Cc, HW,
+                         tdtype=torch.float32) or not _f32c(hist) or hist.numel() != 4 * B * Cc * HW):
+        raise PdmkError("sld_lms_step: inconsistent buffers")
+    _chk(_lib.pdmk_sld_lms_step(_p(pred), ld, float(guidance_scale), C.byref(params), _p(mom), _p(sample), _p(hist), _p(table),
+                                nsteps, _p(state), _p(t_out), _p(x_next), cpad, B, Cc, HW, dt(pred), _st()),
+         "pdmk_sld_lms_step")
 
 
 def calg_workspace_elems(B, Cc, HW):
@@ -1066,13 +1123,13 @@ def calg_guidance(pred, out, guidance_scale, ws, scalars=None):
                                  _st()), "pdmk_calg_guidance")
 
 
-def _calg_step_ok(pred, ld, ws, scalars, sample, table, row, nsteps, state, t_out, x_next, cpad, B, Cc, HW):
+def _calg_step_ok(pred, ld, ws, scalars, sample, table, row, nsteps, state, t_out, x_next, cpad, B, Cc, HW, tdtype=torch.int64):
     n, rows = B * Cc * HW, 5 * B * HW
     return (_calg_ws_ok(ws, scalars, B, Cc, HW) and pred.dtype == x_next.dtype and ld >= Cc and cpad >= Cc
             and _avail(pred) >= (rows - 1) * ld + Cc and x_next.numel() >= rows * cpad and x_next.is_contiguous()
             and _f32c(sample) and sample.numel() == n and table.dtype == torch.uint8
             and table.numel() == nsteps * C.sizeof(row) and state.dtype == torch.int32 and state.numel() == 2
-            and t_out.dtype == torch.int64 and t_out.numel() >= 5 * B)
+            and t_out.dtype == tdtype and t_out.numel() >= 5 * B)
 
 
 def calg_plms_step(pred, ld, guidance_scale, ws, scalars, sample, cur, ets, table, nsteps, state, t_out, x_next, cpad, B, Cc,
@@ -1095,6 +1152,17 @@ def calg_ddim_step(pred, ld, guidance_scale, ws, scalars, sample, table, nsteps,
     _chk(_lib.pdmk_calg_ddim_step(_p(pred), ld, float(guidance_scale), _p(ws), ws.numel(), _p(scalars), _p(sample), _p(table),
                                   nsteps, _p(state), _p(t_out), _p(x_next), cpad, B, Cc, HW, dt(pred), _st()),
          "pdmk_calg_ddim_step")
+
+
+def calg_lms_step(pred, ld, guidance_scale, ws, scalars, sample, hist, table, nsteps, state, t_out, x_next, cpad, B, Cc, HW):
+    """lms_step with concept-algebra guidance (include/pdmk.h pdmk_calg_lms_step); buffers as calg_plms_step, hist fp32
+    [4, B*Cc*HW], t_out float32."""
+    if (not _calg_step_ok(pred, ld, ws, scalars, sample, table, LmsRow, nsteps, state, t_out, x_next, cpad, B, Cc, HW,
+                          tdtype=torch.float32) or not _f32c(hist) or hist.numel() != 4 * B * Cc * HW):
+        raise PdmkError("calg_lms_step: inconsistent buffers")
+    _chk(_lib.pdmk_calg_lms_step(_p(pred), ld, float(guidance_scale), _p(ws), ws.numel(), _p(scalars), _p(sample), _p(hist),
+                                 _p(table), nsteps, _p(state), _p(t_out), _p(x_next), cpad, B, Cc, HW, dt(pred), _st()),
+         "pdmk_calg_lms_step")
 
 
 def _u8_shape(src, dst, name):

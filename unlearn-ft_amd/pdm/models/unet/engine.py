@@ -147,7 +147,8 @@ class UNetEngine(Ops):
 
     # ------------------------------------------------------------------ whole model
     def forward(self, x, timesteps, ehs, B, H, W, train):
-        """x: [B*H*W, padc(in_channels)] NHWC rows in self.dtype; timesteps int64 [B]; ehs: [B*T, ctx] in self.dtype.
+        """x: [B*H*W, padc(in_channels)] NHWC rows in self.dtype; timesteps int64 [B], or float32 [B] for fractional ones
+        (k.timestep_embed dispatches on the dtype); ehs: [B*T, ctx] in self.dtype.
         Returns (pred Act [B*H*W, padc(out_channels)], acts {d0..,m,u0..: Act})."""
         cfg = self.cfg
         self.train = train

@@ -223,8 +223,9 @@ class UNet2DConditionModelPruned:
         B, C, H, W = sample.shape
         dev = self.device
         if not torch.is_tensor(timestep):
-            timestep = torch.tensor([timestep], dtype=torch.int64)
-        timestep = timestep.to(dev).to(torch.int64).reshape(-1)
+            timestep = torch.tensor([timestep], dtype=torch.float32 if isinstance(timestep, float) else torch.int64)
+        # a floating timestep stays fractional (K-LMS: 988.9091); ints go through the int64 embedding as ever
+        timestep = timestep.to(dev).to(torch.float32 if timestep.is_floating_point() else torch.int64).reshape(-1)
         if timestep.numel() == 1 and B > 1:
             timestep = timestep.expand(B).contiguous()
         cp = padc(C)

@@ -23,6 +23,10 @@ Concept algebra (`algebra_concepts=` / `algebra_ids=` / `algebra_embeds=`; DESIG
 and three concept prompts - and projects the text score off the direction between the first two concepts: pdmk_calg_dots
 leaves the two sums over the whole batch as fp64 partials, then pdmk_calg_guidance (eager) or pdmk_calg_plms_step /
 pdmk_calg_ddim_step (captured, 5B rows) applies them.  Without the keyword nothing of it runs.
+
+K-LMS (`LMSDiscreteScheduler`, what the reference's UCE evaluation scripts sample with) calls the U-Net at
+fractional float32 timesteps on inputs divided by sqrt(sigma^2 + 1).  Its loop is captured by default like PNDM's, with
+pdmk_lms_step / pdmk_sld_lms_step / pdmk_calg_lms_step as the step kernel (the next input's division included), one replay per step.
 """
 import ctypes
 import gc
@@ -30,6 +34,7 @@ import json
 import os
 from types import SimpleNamespace
 
+import numpy as np
 import torch
 
 from .. import _pdmk as k
@@ -43,8 +48,8 @@ _PLMS_COEF = {2: (3 / 2, -1 / 2), 3: (23 / 12, -16 / 12, 5 / 12), 4: (55 / 24, -
 
 
 class _Scheduler:
-    """What the two schedulers share: SD-2.1's scaled_linear betas, the `config` namespace, the strict `from_config` and the
-    identity `scale_model_input`.  A subclass sets the key tables and has `set_timesteps` and `step`."""
+    """What the schedulers share: SD-2.1's scaled_linear betas, the `config` namespace, the strict `from_config` and the
+    identity `scale_model_input` (LMS overrides it).  A subclass sets the key tables and has `set_timesteps` and `step`."""
     order = 1
     init_noise_sigma = 1.0
     _FIXED = {}          # config keys whose value the class does not implement otherwise: the value it implements
@@ -220,20 +225,124 @@ class DDIMScheduler(_Scheduler):
         return rows
 
 
+class LMSDiscreteScheduler(_Scheduler):
+    """diffusers LMSDiscreteScheduler (K-LMS, Katherine Crowson's linear multistep sampler) as the UCE evaluation scripts
+    configure it: scaled_linear betas 0.00085 ... 0.012, 1000 train steps, linspace timestep spacing, no Karras sigmas, order
+    4.  A restatement from the published algorithm, unpinned like PNDMScheduler and DDIMScheduler above (diffusers absent,
+    no vendored twin).  `from_config` is as strict as theirs; `steps_offset` is read by no linspace-spaced schedule.
+
+    sigma_t = sqrt((1 - a_t) / a_t) from the fp32 alphas_cumprod.  set_timesteps(n): timesteps = linspace(0, T - 1, n) in
+    fp32, reversed and kept FRACTIONAL (the U-Net is called at 988.9091); sigmas = interp(timesteps, arange(T), sigma_t), a
+    0 appended, fp32.  init_noise_sigma = max sigma.  scale_model_input divides by sqrt(sigma_i^2 + 1) (one fp32 scalar, one
+    fp32 division per element: pdmk_scale_div).  step i, with order_i = min(i + 1, 4):
+        d_i  = model_output                                                           (epsilon)
+        d_i  = sigma / (sigma^2 + 1) sample + 1 / sqrt(sigma^2 + 1) model_output      (v_prediction)
+        c_j  = integral over [sigma_i, sigma_{i+1}] of prod_{k != j, k < order_i} (tau - sigma_{i-k}) / (sigma_{i-j} - sigma_{i-k})
+        prev = sample + sum_j c_j d_{i-j}
+    The coefficients are float64 host scalars and every latent operation is one pdmk_axpby, the newest derivative first.
+    Two deviations from diffusers: c_j is the exact integral of the polynomial (degree <= 3; diffusers calls
+    scipy.integrate.quad with epsrel 1e-4), and the derivative is formed with the fused coefficients above instead of
+    diffusers' fp32 chain (sample - pred_original_sample) / sigma."""
+    _FIXED = {"beta_schedule": "scaled_linear", "trained_betas": None, "use_karras_sigmas": False,
+              "timestep_spacing": "linspace"}
+    _IGNORED = ("steps_offset",)
+    ORDER = 4            # step()'s default, the 4-slot history of pdmk_lms_step
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        acp = self.alphas_cumprod.float()                                  # (the fp32 cumprod itself)
+        self.sigmas_all = ((1 - acp) / acp).sqrt().numpy()
+        self.sigmas, self.derivatives = None, []
+
+    def set_timesteps(self, num_inference_steps, device=None):
+        self.num_inference_steps = num_inference_steps
+        T = self.config.num_train_timesteps
+        timesteps = np.linspace(0, T - 1, num_inference_steps, dtype=np.float32)[::-1].copy()
+        sigmas = np.interp(timesteps, np.arange(0, T), self.sigmas_all)
+        self.sigmas = np.concatenate([sigmas, [0.0]]).astype(np.float32)
+        self.timesteps = torch.from_numpy(timesteps)
+        self.init_noise_sigma = float(self.sigmas.max())
+        self.derivatives = []
+        self._index = {float(t): i for i, t in enumerate(timesteps)}
+
+    def _in_div(self, i):
+        """sqrt(sigma_i^2 + 1), every operation in fp32 (a Python float holding an fp32 value)."""
+        s = self.sigmas[i]
+        return float(np.sqrt(s * s + np.float32(1)))
+
+    def scale_model_input(self, sample, t=None):
+        """sample (contiguous fp32 device tensor) / sqrt(sigma^2 + 1) at the step index of timestep t; a new tensor."""
+        out = torch.empty_like(sample)
+        k.scale_div(sample, out, self._in_div(self._index[float(t)]))
+        return out
+
+    def lms_coefficients(self, i, order):
+        """c_0 .. c_{order-1} of step i (float64): the Lagrange basis polynomials through sigma_i, sigma_{i-1}, ... integrated
+        exactly over [sigma_i, sigma_{i+1}], in the variable u = tau - sigma_i (roots and bounds of the size of a step)."""
+        s = self.sigmas.astype(np.float64)
+        h = s[i + 1] - s[i]
+        out = []
+        for j in range(order):
+            roots = [s[i - m] - s[i] for m in range(order) if m != j]
+            denom = 1.0
+            for m in range(order):
+                if m != j:
+                    denom *= s[i - j] - s[i - m]
+            integral = np.polynomial.polynomial.polyint(np.polynomial.polynomial.polyfromroots(roots) if roots else [1.0])
+            out.append(float(np.polynomial.polynomial.polyval(h, integral) / denom))
+        return out
+
+    def derivative_coefficients(self, i):
+        """(d_x, d_m) with d = d_x * sample + d_m * model_output for v_prediction (float64); None for epsilon (d = model_output)."""
+        if self.config.prediction_type != "v_prediction":
+            return None
+        s = float(self.sigmas[i])
+        return s / (s * s + 1.0), 1.0 / (s * s + 1.0) ** 0.5
+
+    def step(self, model_output, timestep, sample, order=ORDER, return_dict=True):
+        """model_output / sample: contiguous fp32 device tensors of one shape; returns the previous sample (new tensor)."""
+        i = self._index[float(timestep)]
+        d, dc = model_output, self.derivative_coefficients(i)
+        if dc is not None:
+            d = model_output.clone()
+            k.axpby(sample, d, dc[0], dc[1])
+        self.derivatives = (self.derivatives + [d])[-order:]
+        prev = sample.clone()
+        for c, dj in zip(self.lms_coefficients(i, min(i + 1, order)), reversed(self.derivatives)):
+            k.axpby(dj, prev, c, 1.0)
+        return SimpleNamespace(prev_sample=prev) if return_dict else (prev,)
+
+    def lms_rows(self):
+        """The schedule of set_timesteps() as pdmk_lms_row entries: step()'s coefficients at each index, the derivative of
+        step i in ring slot i % 4, and the divisor of the next call's scale_model_input (sigma 0 after the last: 1)."""
+        rows = []
+        for i, t in enumerate(self.timesteps.tolist()):
+            r = k.LmsRow(t=t, nterms=min(i + 1, self.ORDER), wslot=i % 4, in_div=self._in_div(i + 1))
+            for j in range(3):
+                r.rslot[j] = (i - 1 - j) % 4
+            for j, c in enumerate(self.lms_coefficients(i, r.nterms)):
+                r.coef[j] = c
+            dc = self.derivative_coefficients(i)
+            if dc is not None:
+                r.dmode, r.d_x, r.d_m = 1, dc[0], dc[1]
+            rows.append(r)
+        return rows
+
+
 class _CapturedLoop:
     """The denoising loop of one (batch, H, W, dtype, CFG, steps, text shape, guidance) as replays of ONE single-stream
     captured graph (GraphedBilevel's docstring: graphs with parallel branches are not used): the U-Net forward over static
-    buffers, then pdmk_plms_step (kind "plms") or pdmk_ddim_step (kind "ddim"), which writes the next U-Net input and
-    timesteps itself and advances the step counter.  The same graph is replayed once per U-Net call (N + 1 calls for N PLMS
-    steps, N for N DDIM steps), or fewer when the caller stops early.  The graph reads the U-Net's weight arenas in place: it
-    stays valid while an optimiser rewrites them."""
+    buffers, then pdmk_plms_step (kind "plms"), pdmk_ddim_step (kind "ddim") or pdmk_lms_step (kind "lms"), which writes the
+    next U-Net input and timesteps itself and advances the step counter.  The same graph is replayed once per U-Net call
+    (N + 1 calls for N PLMS steps, N for N DDIM or LMS steps), or fewer when the caller stops early.  The graph reads the
+    U-Net's weight arenas in place: it stays valid while an optimiser rewrites them."""
 
     def __init__(self, unet, B, h, w, cfg_on, guidance_scale, nsteps, T, ctx, kind="plms", sld=None, algebra=False):
         dev, dt = unet.device, unet.dtype
-        if kind not in ("plms", "ddim"):
+        if kind not in ("plms", "ddim", "lms"):
             raise ValueError(f"_CapturedLoop: step kind {kind!r}")
         self.kind = kind
-        self.Row = k.PlmsRow if kind == "plms" else k.DdimRow
+        self.Row = {"plms": k.PlmsRow, "ddim": k.DdimRow, "lms": k.LmsRow}[kind]
         self.unet, self.B, self.C, self.h, self.w, self.cfg_on, self.nsteps = unet, B, unet.cfg.in_channels, h, w, cfg_on, nsteps
         self.g = (float(1.0 - guidance_scale), float(guidance_scale))       # axpby(out[:B], out[B:], 1 - g, g)
         self.sld = sld                  # k.SldParams: the 3B form (uncond, text, safety rows; Safe Latent Diffusion guidance)
@@ -245,12 +354,13 @@ class _CapturedLoop:
         self.R, self.cp = (5 * B if self.algebra else 3 * B if sld is not None else 2 * B if cfg_on else B), padc(self.C)
         n = B * self.C * h * w
         self.x = torch.zeros((self.R * h * w, self.cp), device=dev, dtype=dt)
-        self.t = torch.zeros(self.R, device=dev, dtype=torch.int64)
+        self.t = torch.zeros(self.R, device=dev, dtype=torch.float32 if kind == "lms" else torch.int64)   # LMS: fractional
         self.ehs = torch.zeros((self.R * T, ctx), device=dev, dtype=dt)
         self.sample = torch.zeros(n, device=dev)
         if kind == "plms":
             self.cur = torch.zeros(n, device=dev)
-            self.ets = torch.zeros(4, n, device=dev)
+        if kind in ("plms", "lms"):
+            self.ets = torch.zeros(4, n, device=dev)    # PLMS: model outputs; LMS: derivatives
         if sld is not None:
             self.mom = torch.zeros(n, device=dev)
         if self.algebra:
@@ -268,6 +378,9 @@ class _CapturedLoop:
             if self.kind == "plms":
                 k.calg_plms_step(pred.t, pred.t.stride(0), self.g[1], self.ws, self.scalars, self.sample, self.cur, self.ets,
                                  self.table, self.nsteps, self.state, self.t, self.x, self.cp, self.B, self.C, self.h * self.w)
+            elif self.kind == "lms":
+                k.calg_lms_step(pred.t, pred.t.stride(0), self.g[1], self.ws, self.scalars, self.sample, self.ets, self.table,
+                                self.nsteps, self.state, self.t, self.x, self.cp, self.B, self.C, self.h * self.w)
             else:
                 k.calg_ddim_step(pred.t, pred.t.stride(0), self.g[1], self.ws, self.scalars, self.sample, self.table,
                                  self.nsteps, self.state, self.t, self.x, self.cp, self.B, self.C, self.h * self.w)
@@ -275,12 +388,18 @@ class _CapturedLoop:
             if self.kind == "plms":
                 k.sld_plms_step(pred.t, pred.t.stride(0), self.g[1], self.sld, self.mom, self.sample, self.cur, self.ets,
                                 self.table, self.nsteps, self.state, self.t, self.x, self.cp, self.B, self.C, self.h * self.w)
+            elif self.kind == "lms":
+                k.sld_lms_step(pred.t, pred.t.stride(0), self.g[1], self.sld, self.mom, self.sample, self.ets, self.table,
+                               self.nsteps, self.state, self.t, self.x, self.cp, self.B, self.C, self.h * self.w)
             else:
                 k.sld_ddim_step(pred.t, pred.t.stride(0), self.g[1], self.sld, self.mom, self.sample, self.table, self.nsteps,
                                 self.state, self.t, self.x, self.cp, self.B, self.C, self.h * self.w)
         elif self.kind == "plms":
             k.plms_step(pred.t, pred.t.stride(0), *self.g, self.cfg_on, self.sample, self.cur, self.ets, self.table,
                         self.nsteps, self.state, self.t, self.x, self.cp, self.B, self.C, self.h * self.w)
+        elif self.kind == "lms":
+            k.lms_step(pred.t, pred.t.stride(0), *self.g, self.cfg_on, self.sample, self.ets, self.table, self.nsteps,
+                       self.state, self.t, self.x, self.cp, self.B, self.C, self.h * self.w)
         else:
             k.ddim_step(pred.t, pred.t.stride(0), *self.g, self.cfg_on, self.sample, self.table, self.nsteps, self.state,
                         self.t, self.x, self.cp, self.B, self.C, self.h * self.w)
@@ -322,10 +441,12 @@ class _CapturedLoop:
         eng = self.unet.engine          # what the graph reads or writes beyond its own pool stays allocated
         self.keep = [pred, eng.ws, eng._cs_arena]
 
-    def run(self, latents, ehs, rows, n_calls=None):
+    def run(self, latents, ehs, rows, n_calls=None, x0=None):
         """latents: fp32 [B, C, h, w] (contiguous, on the device); ehs: [R, T, ctx] text embeddings (unconditional half
-        first, with SLD the safety third last, with concept algebra the three concepts last); rows: the scheduler's plms_rows() / ddim_rows(); n_calls: U-Net calls to
-        replay (None: all of them).  Returns the latents after them (a new tensor)."""
+        first, with SLD the safety third last, with concept algebra the three concepts last); rows: the scheduler's plms_rows() / ddim_rows() / lms_rows(); n_calls: U-Net calls to
+        replay (None: all of them); x0: the first U-Net input where it is not the latents themselves (LMS: the scheduler's
+        scale_model_input of them - later inputs are scaled by the step kernel).  Returns the latents after them (a new
+        tensor)."""
         B, C, HW = self.B, self.C, self.h * self.w
         n_calls = self.nsteps if n_calls is None else int(n_calls)
         if len(rows) != self.nsteps or not 0 <= n_calls <= self.nsteps:
@@ -333,15 +454,16 @@ class _CapturedLoop:
         self.ehs.copy_(ehs.reshape(self.ehs.shape))                       # the batch's one cast of the text embeddings
         self.table.copy_(torch.frombuffer(bytearray(bytes((self.Row * len(rows))(*rows))), dtype=torch.uint8))
         self.sample.copy_(latents.reshape(-1))
-        k.nchw_to_nhwc(latents, self.x, B, C, HW, self.cp)
+        x0 = latents if x0 is None else x0
+        k.nchw_to_nhwc(x0, self.x, B, C, HW, self.cp)
         if self.cfg_on:
-            k.nchw_to_nhwc(latents, self.x[B * HW:], B, C, HW, self.cp)
+            k.nchw_to_nhwc(x0, self.x[B * HW:], B, C, HW, self.cp)
         if self.sld is not None:
-            k.nchw_to_nhwc(latents, self.x[2 * B * HW:], B, C, HW, self.cp)
+            k.nchw_to_nhwc(x0, self.x[2 * B * HW:], B, C, HW, self.cp)
             self.mom.zero_()
         if self.algebra:
             for j in range(2, 5):
-                k.nchw_to_nhwc(latents, self.x[j * B * HW:], B, C, HW, self.cp)
+                k.nchw_to_nhwc(x0, self.x[j * B * HW:], B, C, HW, self.cp)
         self.t.fill_(rows[0].t)
         self.state.zero_()
         for _ in range(n_calls):
@@ -386,7 +508,7 @@ class StableDiffusionPruningPipeline:
 
     def _use_graph(self, graph, callback):
         kind = type(self.scheduler)
-        if graph is False or callback is not None or kind not in (PNDMScheduler, DDIMScheduler):
+        if graph is False or callback is not None or kind not in (PNDMScheduler, DDIMScheduler, LMSDiscreteScheduler):
             return False
         if kind is DDIMScheduler and graph is not True:      # DDIM is captured only on request
             return False
@@ -409,8 +531,8 @@ class StableDiffusionPruningPipeline:
             while len(self._loops) >= self.GRAPH_SHAPES:
                 self._loops.pop(next(iter(self._loops))).close()
             loop = _CapturedLoop(self.unet, B, h, w, cfg_on, guidance_scale, nsteps, T, ctx,
-                                 kind="ddim" if type(self.scheduler) is DDIMScheduler else "plms", sld=sld,
-                                 algebra=algebra)
+                                 kind={DDIMScheduler: "ddim", LMSDiscreteScheduler: "lms"}.get(type(self.scheduler), "plms"),
+                                 sld=sld, algebra=algebra)
             self.captures += 1
         self._loops[key] = loop                                       # most recently used last
         return loop
@@ -491,8 +613,9 @@ class StableDiffusionPruningPipeline:
         if self._use_graph(graph, callback):
             loop = self._loop(B, shape[2], shape[3], cfg_on, guidance_scale, len(sch.timesteps), ehs.shape[1], ehs.shape[2],
                               sld=sld, algebra=algebra)
-            rows = sch.ddim_rows() if loop.kind == "ddim" else sch.plms_rows()
-            latents = loop.run(latents, ehs, rows, n_calls=end_iteration)
+            rows = getattr(sch, loop.kind + "_rows")()
+            x0 = sch.scale_model_input(latents, sch.timesteps[0].item()) if loop.kind == "lms" else None
+            latents = loop.run(latents, ehs, rows, n_calls=end_iteration, x0=x0)
         else:
             latents = self._eager_loop(latents, ehs, B, shape, cfg_on, guidance_scale, callback, callback_steps, end_iteration,
                                        sld=sld, algebra=algebra)
@@ -561,7 +684,8 @@ class StableDiffusionPruningPipeline:
                 if algebra:
                     for j in range(2, 5):
                         x2[j * B:(j + 1) * B].copy_(latents)
-                tt = torch.full((x2.shape[0],), t, device=dev, dtype=torch.int64)
+                tt = torch.full((x2.shape[0],), t, device=dev,
+                                dtype=torch.float32 if sch.timesteps.is_floating_point() else torch.int64)
                 out = self.unet(sch.scale_model_input(x2, t), tt, ehs, return_dict=False)[0]
                 if algebra:       # the two sums over the whole batch, then the projection and the guidance
                     out = out.contiguous()

@@ -72,6 +72,8 @@ def add_common_arguments(parser):
     parser.add_argument('--ckpt_path', type=str, default=None, help="the pruned checkpoint directory: arch_vector.pt + unet/")
     parser.add_argument('--mixed_precision', type=str, default=None, choices=["no", "bf16"])
     parser.add_argument('--tiny', action="store_true", help="tiny U-Net topology (tests)")
+    parser.add_argument('--scheduler', type=str, default='pndm', choices=["pndm", "lms"],
+                        help="sampler: the project's PNDM (default) or the reference's K-LMS (LMSDiscreteScheduler)")
     return parser
 
 
@@ -92,4 +94,4 @@ def load_pipeline(args):
     if erasure is not None:
         from .erasure_utils import load_erasure_checkpoint
         load_erasure_checkpoint(unet, erasure)
-    return models, models.pipeline(unet)
+    return models, models.pipeline(unet, kind=getattr(args, "scheduler", "pndm"))

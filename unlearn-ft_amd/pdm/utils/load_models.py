@@ -6,6 +6,7 @@ directory, the sampling scheduler and the pipeline over them.
 one (`Trainer.models`), a script builds its own from `inference_config(...)`.  Nothing here trains, and nothing here touches the
 GPU before a model is asked for.
 """
+import json
 import os
 
 import torch
@@ -47,12 +48,19 @@ def unet_kwargs(config):
 
 def load_scheduler(config, kind="pndm"):
     """`kind` "pndm" / "ddim" from <snapshot>/scheduler/scheduler_config.json when present (values the class does not
-    implement raise), else the SD-2.1 defaults with `model.prediction_model.prediction_type`."""
-    from ..pipelines.pruning_pipelines import DDIMScheduler, PNDMScheduler
-    cls = {"pndm": PNDMScheduler, "ddim": DDIMScheduler}[kind]
+    implement raise), else the SD-2.1 defaults with `model.prediction_model.prediction_type`.  `kind` "lms" (the UCE
+    evaluation scripts build their LMSDiscreteScheduler by hand beside the snapshot's models): the snapshot's file names
+    another scheduler class, so only its prediction_type and beta keys are taken and the other class's keys are ignored."""
+    from ..pipelines.pruning_pipelines import DDIMScheduler, LMSDiscreteScheduler, PNDMScheduler
+    cls = {"pndm": PNDMScheduler, "ddim": DDIMScheduler, "lms": LMSDiscreteScheduler}[kind]
     root = cfg_get(config, "pretrained_model_name_or_path")
     path = os.path.join(str(root), "scheduler", "scheduler_config.json")
     if root and os.path.exists(path):
+        if kind == "lms":
+            with open(path) as f:
+                file = json.load(f)
+            return cls(**{key: file[key] for key in ("prediction_type", "beta_start", "beta_end", "num_train_timesteps")
+                          if key in file})
         return cls.from_config(path)
     return cls(prediction_type=cfg_get(config, "model.prediction_model.prediction_type", "v_prediction"))
 

@@ -13,8 +13,11 @@ p1 - p0, measured against p2, over the whole batch (include/pdmk.h "Concept alge
 * Rows, seeds, batch and output as generate_images.py: <save_path>/<model_name without "diffusers-" and ".pt">/
   <case_number>_<n>.png, which CLIP_classify.py reads.
 * --concepts_to_project: exactly three, comma separated; anything else raises.
-* Deviations from the reference: it samples with the project's captured PNDM sampler, not LMSDiscreteScheduler (not built;
-  diffusers is not available to pin it against), so --ddim_steps counts PNDM steps; the models are the pruned SD-2.1 student
+* --scheduler lms samples as the reference does, with K-LMS (LMSDiscreteScheduler): --ddim_steps then counts LMS
+  steps and the initial noise is scaled by the largest sigma.
+* Deviations from the reference: the default --scheduler pndm is the project's captured PNDM sampler, and --ddim_steps counts
+  PNDM steps there; the LMS scheduler is a restatement (diffusers is not available to pin it against, and no real SD-2.1
+  weights were sampled with it) with exact coefficient integrals; the models are the pruned SD-2.1 student
   loaded through FrozenModels, not SD-1.4 / CLIP-L from the hub, so --base is not offered; where the direction p1 - p0 is zero
   the projection is left out (the reference divides by zero and samples NaN).
 """

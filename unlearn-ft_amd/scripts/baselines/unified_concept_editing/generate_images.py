@@ -12,8 +12,11 @@
   Per row `torch.Generator(device).manual_seed(evaluation_seed)` and --num_samples images of the prompt as one batch.
 * Output: <save_path>/<model_name without "diffusers-" and ".pt">/<case_number>_<n>.png - the layout lpips_eval.py and
   styleloss.py read (run it once with `original` and once per edit, same prompts, same seeds).
-* Deviations from the reference: it samples with the project's captured PNDM sampler, not LMSDiscreteScheduler (not built;
-  diffusers is not available to pin it against), so --ddim_steps counts PNDM steps; the models are the pruned checkpoint loaded
+* --scheduler lms samples as the reference does, with K-LMS (LMSDiscreteScheduler, scaled_linear 0.00085 ... 0.012, 1000 train
+  steps): --ddim_steps then counts LMS steps and the initial noise is scaled by the largest sigma.
+* Deviations from the reference: the default --scheduler pndm is the project's captured PNDM sampler, and --ddim_steps counts
+  PNDM steps there; the LMS scheduler is a restatement (diffusers is not available to pin it against, and no real SD-2.1
+  weights were sampled with it) with exact coefficient integrals; the models are the pruned checkpoint loaded
   through FrozenModels, not SD-1.x from the hub, so --base is not offered; the row loop is the one of sld_generate_images.py
   (pdm/utils/sld.py sample_cases).
 """
@@ -49,6 +52,8 @@ def parse_args(argv=None):
     parser.add_argument('--ckpt_path', type=str, default=None, help="the pruned checkpoint directory: arch_vector.pt + unet/")
     parser.add_argument('--mixed_precision', type=str, default=None, choices=["no", "bf16"])
     parser.add_argument('--tiny', action="store_true", help="tiny U-Net topology (tests)")
+    parser.add_argument('--scheduler', type=str, default='pndm', choices=["pndm", "lms"],
+                        help="sampler: the project's PNDM (default) or the reference's K-LMS (LMSDiscreteScheduler)")
     return parser.parse_args(argv)
 
 
@@ -91,7 +96,7 @@ def main(argv=None):
     if erasure is not None:
         from pdm.utils.erasure_utils import load_erasure_checkpoint
         load_erasure_checkpoint(unet, erasure)
-    return generate_images(models.pipeline(unet), args.model_name, args.prompts_path, args.save_path,
+    return generate_images(models.pipeline(unet, kind=args.scheduler), args.model_name, args.prompts_path, args.save_path,
                            guidance_scale=args.guidance_scale, image_size=args.image_size, ddim_steps=args.ddim_steps,
                            num_samples=args.num_samples, from_case=args.from_case, till_case=args.till_case)
 

@@ -14,7 +14,10 @@ third "safety concept" branch in classifier-free guidance (pdm/pipelines/pruning
 * Output: <save_path>/SLD_<sld_type>_<sld_concept>/<case_number>_<n>.png, the reference's names.
 * Deviations from the reference: its leftover filter that keeps only the cases 0, 38 and 51 is not reproduced; the models are
   the pruned checkpoint --ckpt_path (optionally with an erasure checkpoint laid over it) loaded through FrozenModels, not
-  SD-1.4 from the hub; --ddim_steps reaches the sampler (the reference parses it and samples with the pipeline's default 50).
+  SD-1.4 from the hub; --ddim_steps reaches the sampler (the reference parses it and samples with the pipeline's default 50);
+  the default --scheduler pndm is the project's captured PNDM sampler.  --scheduler lms samples with K-LMS
+  (LMSDiscreteScheduler as the sibling evaluation scripts configure it): --ddim_steps then counts LMS steps, the
+  warm-up counts LMS's U-Net calls (one per step), and the scheduler is a restatement that diffusers was not available to pin.
 """
 import argparse
 import logging
@@ -48,6 +51,8 @@ def parse_args(argv=None):
     parser.add_argument('--erasure_ckpt_path', type=str, default=None, help="an ESD / UCE / ConceptPrune checkpoint laid over it")
     parser.add_argument('--mixed_precision', type=str, default=None, choices=["no", "bf16"])
     parser.add_argument('--tiny', action="store_true", help="tiny U-Net topology (tests)")
+    parser.add_argument('--scheduler', type=str, default='pndm', choices=["pndm", "lms"],
+                        help="sampler: the project's PNDM (default) or K-LMS (LMSDiscreteScheduler)")
     return parser.parse_args(argv)
 
 
@@ -76,7 +81,7 @@ def main(argv=None):
     if args.erasure_ckpt_path is not None:
         from pdm.utils.erasure_utils import load_erasure_checkpoint
         load_erasure_checkpoint(unet, args.erasure_ckpt_path)
-    return generate_SLD(models.pipeline(unet), args.sld_concept, args.sld_type, args.prompts_path, args.save_path,
+    return generate_SLD(models.pipeline(unet, kind=args.scheduler), args.sld_concept, args.sld_type, args.prompts_path, args.save_path,
                         guidance_scale=args.guidance_scale, image_size=args.image_size, ddim_steps=args.ddim_steps,
                         num_samples=args.num_samples, from_case=args.from_case)
 
