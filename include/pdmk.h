@@ -794,13 +794,43 @@ int pdmk_gram_pair(const float* f0, const float* f1, int ld, int B, int HW, int 
  *   w f32 / bf16 with row stride ldw >= F; n_base / n_target fp32 [T, F] contiguous, FINITE and >= 0 (NaN / inf have no defined
  *   order here); count int32 [O, F] contiguous, accumulated into.  One workgroup per row, all T in the one launch.
  *   F <= PDMK_WANDA_MAX_F (the dense SD-2.1 width), else -2.
- * pdmk_wanda_apply: W[o][f] = 0 where (float)count[o][f] > threshold; every other element is left as it is. */
+ * pdmk_wanda_apply: W[o][f] = 0 where (float)count[o][f] > threshold; every other element is left as it is.
+ *
+ * Neuron removal at sampling time (baselines/concept_prune/remove_neurons.py, neuron_receivers/neuron_remover.py): at U-Net
+ * call t layer l's ff.net.2 runs with W * (1 - mask[t][l]).  The masks are bits, one per (t, o, f):
+ * pdmk_wanda_select: pdmk_wanda_count's selection (the same device routine: the same keys, bisection and tie rule), written
+ *   instead of counted.  Bit (f & 31) of word bits[t * t_stride + o * row_words + (f >> 5)], row_words = (F + 31) / 32, is set
+ *   exactly when f is in S at t and mt[f] > mb[f].  The words of a row are OVERWRITTEN (not OR-ed), the bits at f >= F of its
+ *   last word are 0, words outside the O * row_words of a timestep are not touched (t_stride >= O * row_words, in words).
+ *   k == 0 writes all-zero rows (pdmk_wanda_count returns at once), k >= F the whole row gated by mt > mb.  Plain vector
+ *   stores of a wave's ballot, no atomics: the same arguments give the same bits.  F > PDMK_WANDA_MAX_F: -2.
+ * pdmk_masked_weights: ONE launch sets the compute-copy weights of every listed layer to src * (1 - mask[slot]):
+ *   dst[dst_off + o * ld + f] = bit ? 0 : src[src_off + o * ld + f] for o < O, f < F of every table row - a select in the
+ *   dtype, nothing is rounded; columns F .. ld and everything between the layers are not written.  The bit is bit (f & 31) of
+ *   bits[slot * t_stride + bits_off + o * row_words(F) + (f >> 5)].  dst: the weight arena the engine reads; src: a PRISTINE
+ *   copy of those layers (in fp32 the arena is the master itself, so the masked values are never the source of the next
+ *   mask); the two must not overlap.  A table row is some consecutive weight rows of one layer (one workgroup each; the
+ *   host cuts a layer into rows of about equal work).  slot: the host value, or with state != NULL the device-side U-Net call
+ *   number state[0] (the captured sampler's counter), of which repeat_first maps calls 0 and 1 to slot 0 and call c to c - 1
+ *   (PNDM's repeated first timestep).  A slot outside [0, T), or bits == NULL, writes the unmasked weights: the capture
+ *   warm-up, whose counter is past the end, and the restore.  dst / src 16-byte aligned; 16-byte loads and stores where F, ld
+ *   and both offsets are multiples of 16 bytes, element-wise otherwise. */
 #define PDMK_WANDA_MAX_F 5120
+typedef struct {
+    int64_t dst_off, src_off;   /* elements from dst / src to the first weight of the row block */
+    int64_t bits_off;           /* words from a timestep's first word to the row block's first word */
+    int32_t O, F, ld;           /* weight rows in the block, columns, row stride (elements) of dst and src alike */
+    int32_t pad_;
+} pdmk_mask_row;
 int64_t pdmk_rownorm_colsq_workspace_elems(int M, int F);
 int pdmk_rownorm_colsq(const void* x, int dtype, int M, int F, int ld, float* acc, float* ws, int64_t ws_elems, pdmk_stream stream);
 int pdmk_wanda_count(const void* w, int dtype, int O, int F, int ldw, const float* n_base, const float* n_target, int T, int k,
                      int32_t* count, pdmk_stream stream);
 int pdmk_wanda_apply(void* w, int dtype, int O, int F, int ldw, const int32_t* count, float threshold, pdmk_stream stream);
+int pdmk_wanda_select(const void* w, int dtype, int O, int F, int ldw, const float* n_base, const float* n_target, int T, int k,
+                      uint32_t* bits, int64_t t_stride, pdmk_stream stream);
+int pdmk_masked_weights(void* dst, const void* src, int dtype, const pdmk_mask_row* table, int nrows, const uint32_t* bits,
+                        int64_t t_stride, int T, int slot, const int32_t* state, int repeat_first, pdmk_stream stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * UCE (baselines/unified-concept-editing/train-scripts/train_erase.py; pdm/utils/uce.py): the closed-form edit of every

@@ -1,5 +1,6 @@
 // ConceptPrune / Wanda kernels (include/pdmk.h "ConceptPrune"): the observation step on the GEGLU output that feeds ff.net.2
-// (row-normalised squared column sums), the per-row top-k selection of |W| * norm scores over all timesteps, and the mask.
+// (row-normalised squared column sums), the per-row top-k selection of |W| * norm scores over all timesteps (as counts over time,
+// or as one bit per timestep and weight), the time-averaged mask, and the per-timestep masks applied to the compute weights.
 //
 // Everything here is reproducible bit for bit from launch to launch: masks are built on comparisons of these numbers, so no
 // float atomics anywhere - sums go through wave butterflies, LDS and partial slabs in a fixed order.
@@ -141,25 +142,59 @@ __device__ __forceinline__ int block_count(int v, int (*buf)[NT / 64], int& slot
     return b[0] + b[1] + b[2] + b[3];
 }
 
-// One workgroup per weight row o; thread tid owns the columns f = j * 256 + tid, j < NPT: |W[o, f]| and the row's counts stay
+// Where a row's selection goes.  wanda_select_row calls emit(t, j, sel) for every t and j from ALL threads of the workgroup (a
+// policy may use wave-wide operations), sel being the outcome for column f = j * 256 + tid (false at f >= F), and finish() once.
+// CountOut: count[o][f] += the number of t at which f is selected, kept in registers until the end (pdmk_wanda_count).
+template <int NPT>
+struct CountOut {
+    int32_t* cr;
+    int F;
+    int cnt[NPT];
+    __device__ __forceinline__ CountOut(int32_t* row, int F_) : cr(row), F(F_) {
+#pragma unroll
+        for (int j = 0; j < NPT; ++j) cnt[j] = 0;
+    }
+    __device__ __forceinline__ void emit(int, int j, bool sel) { cnt[j] += sel ? 1 : 0; }
+    __device__ __forceinline__ void finish() {
+#pragma unroll
+        for (int j = 0; j < NPT; ++j) {
+            const int f = j * NT + (int)threadIdx.x;
+            if (f < F) cr[f] += cnt[j];
+        }
+    }
+};
+// BitsOut: one bit per (t, f), overwritten (pdmk_wanda_select).  A wave's ballot at j covers the 64 columns from
+// j * 256 + wave * 64: exactly the words j * 8 + wave * 2 and the next one, stored by lanes 0 and 32 with plain vector stores.
+// Columns at f >= F carry sel = false, so the tail bits of the last word are 0; words past the row are not written.
+struct BitsOut {
+    uint32_t* row;             // word 0 of row o at t = 0
+    long t_stride;
+    int row_words;
+    __device__ __forceinline__ void emit(int t, int j, bool sel) {
+        const unsigned long long m = __ballot(sel);
+        const int lane = threadIdx.x & 63;
+        const int word = j * (NT / 32) + (int)(threadIdx.x >> 6) * 2 + (lane >> 5);
+        if ((lane & 31) == 0 && word < row_words) row[t * t_stride + word] = (uint32_t)(m >> (lane & 32));
+    }
+    __device__ __forceinline__ void finish() {}
+};
+
+// The selection of one weight row by one workgroup; thread tid owns the columns f = j * 256 + tid, j < NPT: |W[o, f]| stays
 // in registers across the T timesteps.  The k-th largest score is found by bisection on the 32 key bits (the largest threshold
 // that at least k keys reach), one workgroup-wide count per bit and no atomics; keys equal to it are taken in ascending f.
-template <typename T, int NPT>
-__global__ void __launch_bounds__(NT) wanda_count_kernel(const T* __restrict__ w, int F, int ldw, const float* __restrict__ n_base,
-                                                         const float* __restrict__ n_target, int nT, int k,
-                                                         int32_t* __restrict__ count) {
+// k <= 0 selects nothing, k >= F the whole row (both still gated by mt > mb and emitted).
+template <typename T, int NPT, typename Out>
+__device__ __forceinline__ void wanda_select_row(const T* __restrict__ wr, int F, const float* __restrict__ n_base,
+                                                 const float* __restrict__ n_target, int nT, int k, Out& out) {
     __shared__ int cbuf[2][NT / 64];
     __shared__ int wtie[NT / 64];
     int slot = 0;
     const int tid = threadIdx.x;
-    const T* wr = w + (long)blockIdx.x * ldw;
     float aw[NPT];
-    int cnt[NPT];
 #pragma unroll
     for (int j = 0; j < NPT; ++j) {
         const int f = j * NT + tid;
         aw[j] = f < F ? fabsf(to_f32(wr[f])) : 0.f;
-        cnt[j] = 0;
     }
     for (int t = 0; t < nT; ++t) {
         const float* nb = n_base + (long)t * F;
@@ -177,9 +212,9 @@ __global__ void __launch_bounds__(NT) wanda_count_kernel(const T* __restrict__ w
                 gt |= (mt > mb ? 1u : 0u) << j;
             }
         }
-        if (k >= F) {                                         // the whole row
+        if (k >= F || k <= 0) {                               // the whole row, or nothing
 #pragma unroll
-            for (int j = 0; j < NPT; ++j) cnt[j] += (gt >> j) & 1u;
+            for (int j = 0; j < NPT; ++j) out.emit(t, j, k > 0 && ((gt >> j) & 1u));
             continue;
         }
         unsigned thr = 0u;
@@ -200,7 +235,7 @@ __global__ void __launch_bounds__(NT) wanda_count_kernel(const T* __restrict__ w
         const int nties = block_count(c, cbuf, slot);
         if (nties <= need) {                                  // no tie across the k-th place
 #pragma unroll
-            for (int j = 0; j < NPT; ++j) cnt[j] += (key[j] >= thr ? 1 : 0) & ((gt >> j) & 1u);
+            for (int j = 0; j < NPT; ++j) out.emit(t, j, key[j] >= thr && ((gt >> j) & 1u));
         } else {                                              // the first `need` of them in ascending f = (j, tid)
 #pragma unroll
             for (int j = 0; j < NPT; ++j) {
@@ -218,29 +253,55 @@ __global__ void __launch_bounds__(NT) wanda_count_kernel(const T* __restrict__ w
                     tot += wtie[q];
                 }
                 const bool sel = key[j] > thr || (tie && base + before < need);
-                cnt[j] += (sel ? 1 : 0) & ((gt >> j) & 1u);
+                out.emit(t, j, sel && ((gt >> j) & 1u));
                 need -= tot;                                  // (may go negative: nothing more is taken)
             }
         }
     }
-    int32_t* cr = count + (long)blockIdx.x * F;
-#pragma unroll
-    for (int j = 0; j < NPT; ++j) {
-        const int f = j * NT + tid;
-        if (f < F) cr[f] += cnt[j];
-    }
+    out.finish();
 }
+
+// One workgroup per weight row o, all T timesteps in the launch.
+template <typename T, int NPT>
+__global__ void __launch_bounds__(NT) wanda_count_kernel(const T* __restrict__ w, int F, int ldw, const float* __restrict__ n_base,
+                                                         const float* __restrict__ n_target, int nT, int k,
+                                                         int32_t* __restrict__ count) {
+    CountOut<NPT> out(count + (long)blockIdx.x * F, F);
+    wanda_select_row<T, NPT>(w + (long)blockIdx.x * ldw, F, n_base, n_target, nT, k, out);
+}
+
+template <typename T, int NPT>
+__global__ void __launch_bounds__(NT) wanda_select_kernel(const T* __restrict__ w, int F, int ldw, const float* __restrict__ n_base,
+                                                          const float* __restrict__ n_target, int nT, int k,
+                                                          uint32_t* __restrict__ bits, long t_stride) {
+    const int row_words = (F + 31) >> 5;
+    BitsOut out{bits + (long)blockIdx.x * row_words, t_stride, row_words};
+    wanda_select_row<T, NPT>(w + (long)blockIdx.x * ldw, F, n_base, n_target, nT, k, out);
+}
+
+// NPT by width: 5, 10 or 20 columns per thread
+#define WANDA_BY_WIDTH(KERNEL, ...)                                                                        \
+    do {                                                                                                   \
+        if (F <= 5 * NT)                                                                                   \
+            hipLaunchKernelGGL((KERNEL<T, 5>), dim3(O), dim3(NT), 0, st, __VA_ARGS__);                     \
+        else if (F <= 10 * NT)                                                                             \
+            hipLaunchKernelGGL((KERNEL<T, 10>), dim3(O), dim3(NT), 0, st, __VA_ARGS__);                    \
+        else                                                                                               \
+            hipLaunchKernelGGL((KERNEL<T, 20>), dim3(O), dim3(NT), 0, st, __VA_ARGS__);                    \
+    } while (0)
 
 template <typename T>
 int wanda_count_t(const void* w, int O, int F, int ldw, const float* nb, const float* nt, int nT, int k, int32_t* count,
                   hipStream_t st) {
-    const T* wp = (const T*)w;
-    if (F <= 5 * NT)
-        hipLaunchKernelGGL((wanda_count_kernel<T, 5>), dim3(O), dim3(NT), 0, st, wp, F, ldw, nb, nt, nT, k, count);
-    else if (F <= 10 * NT)
-        hipLaunchKernelGGL((wanda_count_kernel<T, 10>), dim3(O), dim3(NT), 0, st, wp, F, ldw, nb, nt, nT, k, count);
-    else
-        hipLaunchKernelGGL((wanda_count_kernel<T, 20>), dim3(O), dim3(NT), 0, st, wp, F, ldw, nb, nt, nT, k, count);
+    WANDA_BY_WIDTH(wanda_count_kernel, (const T*)w, F, ldw, nb, nt, nT, k, count);
+    PDMK_CHECK_LAUNCH();
+    return 0;
+}
+
+template <typename T>
+int wanda_select_t(const void* w, int O, int F, int ldw, const float* nb, const float* nt, int nT, int k, uint32_t* bits,
+                   long t_stride, hipStream_t st) {
+    WANDA_BY_WIDTH(wanda_select_kernel, (const T*)w, F, ldw, nb, nt, nT, k, bits, t_stride);
     PDMK_CHECK_LAUNCH();
     return 0;
 }
@@ -261,6 +322,61 @@ int wanda_apply_t(void* w, int O, int F, int ldw, const int32_t* count, float th
     const long n = (long)O * F;
     const int grid = (int)max(1L, min(4096L, (n + NT - 1) / NT));
     hipLaunchKernelGGL(wanda_apply_kernel<T>, dim3(grid), dim3(NT), 0, st, (T*)w, O, F, ldw, count, threshold);
+    PDMK_CHECK_LAUNCH();
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------- per-timestep masks
+// One workgroup per table row (some rows of one layer): dst = bit ? 0 : src over the row's F columns, a select in T.  The slot
+// is resolved here, from the host value or from the sampler's device-side call counter, so one captured launch serves every
+// step; outside [0, nT), or without bits, the pristine weights are written.  16-byte chunks where F, ld and the two offsets are
+// multiples of the chunk (the pointers are 16-byte aligned, checked on the host), else element by element.
+template <typename T>
+__global__ void __launch_bounds__(NT) masked_weights_kernel(T* __restrict__ dst, const T* __restrict__ src,
+                                                            const pdmk_mask_row* __restrict__ table,
+                                                            const uint32_t* __restrict__ bits, long t_stride, int nT, int slot,
+                                                            const int32_t* __restrict__ state, int repeat_first) {
+    constexpr int N = Vec<T>::N;
+    const pdmk_mask_row r = table[blockIdx.x];
+    if (r.O <= 0 || r.F <= 0 || r.ld < r.F || r.dst_off < 0 || r.src_off < 0 || r.bits_off < 0) return;
+    int s = slot;
+    if (state) {
+        s = state[0];
+        if (repeat_first && s > 0) --s;                       // PNDM: calls 0 and 1 are the same timestep
+    }
+    const uint32_t* b = (bits && s >= 0 && s < nT) ? bits + (long)s * t_stride + r.bits_off : nullptr;
+    const int rw = (r.F + 31) >> 5;
+    T* d = dst + r.dst_off;
+    const T* p = src + r.src_off;
+    if (!((r.F | r.ld | r.dst_off | r.src_off) & (N - 1))) {
+        const int cpr = r.F / N;                              // chunks per row
+        const int n = r.O * cpr;
+        for (int i = threadIdx.x; i < n; i += NT) {
+            const int o = i / cpr, f0 = (i - o * cpr) * N;
+            typename Vec<T>::raw v = Vec<T>::load_raw(p + (long)o * r.ld + f0);
+            if (b) {
+                const uint32_t m = b[(long)o * rw + (f0 >> 5)] >> (f0 & 31);       // N divides 32: a chunk is inside one word
+#pragma unroll
+                for (int e = 0; e < N; ++e) v[e] = ((m >> e) & 1u) ? (T)0.f : v[e];
+            }
+            *reinterpret_cast<typename Vec<T>::raw*>(d + (long)o * r.ld + f0) = v;
+        }
+    } else {
+        const int n = r.O * r.F;
+        for (int i = threadIdx.x; i < n; i += NT) {
+            const int o = i / r.F, f = i - o * r.F;
+            T v = p[(long)o * r.ld + f];
+            if (b && ((b[(long)o * rw + (f >> 5)] >> (f & 31)) & 1u)) v = (T)0.f;
+            d[(long)o * r.ld + f] = v;
+        }
+    }
+}
+
+template <typename T>
+int masked_weights_t(void* dst, const void* src, const pdmk_mask_row* table, int nrows, const uint32_t* bits, long t_stride, int nT,
+                     int slot, const int32_t* state, int repeat_first, hipStream_t st) {
+    hipLaunchKernelGGL(masked_weights_kernel<T>, dim3(nrows), dim3(NT), 0, st, (T*)dst, (const T*)src, table, bits, t_stride, nT,
+                       slot, state, repeat_first);
     PDMK_CHECK_LAUNCH();
     return 0;
 }
@@ -288,6 +404,24 @@ extern "C" int pdmk_wanda_count(const void* w, int dtype, int O, int F, int ldw,
     if (F > PDMK_WANDA_MAX_F) return -2;
     if (k == 0) return 0;                                      // nothing is selected
     PDMK_DISPATCH(dtype, wanda_count_t, w, O, F, ldw, n_base, n_target, T, k, count, (hipStream_t)s);
+}
+
+extern "C" int pdmk_wanda_select(const void* w, int dtype, int O, int F, int ldw, const float* n_base, const float* n_target, int T,
+                                 int k, uint32_t* bits, int64_t t_stride, pdmk_stream s) {
+    if (!w || !n_base || !n_target || !bits || O < 1 || F < 1 || ldw < F || T < 1 || k < 0 || ((uintptr_t)bits & 3)) return -1;
+    if (F > PDMK_WANDA_MAX_F) return -2;
+    if (t_stride < (int64_t)O * ((F + 31) / 32)) return -1;
+    PDMK_DISPATCH(dtype, wanda_select_t, w, O, F, ldw, n_base, n_target, T, k, bits, (long)t_stride, (hipStream_t)s);
+}
+
+extern "C" int pdmk_masked_weights(void* dst, const void* src, int dtype, const pdmk_mask_row* table, int nrows,
+                                   const uint32_t* bits, int64_t t_stride, int T, int slot, const int32_t* state, int repeat_first,
+                                   pdmk_stream s) {
+    if (!dst || !src || !table || nrows < 1 || T < 0 || t_stride < 0 || (((uintptr_t)dst | (uintptr_t)src) & 15) ||
+        ((uintptr_t)table & 7) || ((uintptr_t)bits & 3) || ((uintptr_t)state & 3))
+        return -1;
+    PDMK_DISPATCH(dtype, masked_weights_t, dst, src, table, nrows, bits, (long)t_stride, T, slot, state, repeat_first,
+                  (hipStream_t)s);
 }
 
 extern "C" int pdmk_wanda_apply(void* w, int dtype, int O, int F, int ldw, const int32_t* count, float threshold, pdmk_stream s) {

@@ -175,6 +175,8 @@ _SIGS = {
     "pdmk_rownorm_colsq": ([vp, i32, i32, i32, i32, vp, vp, i64, vp], i32),
     "pdmk_wanda_count": ([vp, i32, i32, i32, i32, vp, vp, i32, i32, vp, vp], i32),
     "pdmk_wanda_apply": ([vp, i32, i32, i32, i32, vp, f32, vp], i32),
+    "pdmk_wanda_select": ([vp, i32, i32, i32, i32, vp, vp, i32, i32, vp, i64, vp], i32),
+    "pdmk_masked_weights": ([vp, vp, i32, vp, i32, vp, i64, i32, i32, vp, i32, vp], i32),
     "pdmk_spd_workspace_elems": ([i32, i32], i64),
     "pdmk_spd_system_f64": ([vp, f64, vp, f64, f64, vp, i32, i32, vp], i32),
     "pdmk_pair_gram_f64": ([vp, i32, i32, i32, f64, f64, vp, i32, vp], i32),
@@ -1489,6 +1491,85 @@ def wanda_apply(w, count, threshold, O=None, F=None, ldw=None):
     if count.dtype != torch.int32 or tuple(count.shape) != (O, F) or not count.is_contiguous():
         raise PdmkError(f"wanda_apply: count must be contiguous int32 [{O}, {F}]")
     _chk(_lib.pdmk_wanda_apply(_p(w), dt(w), O, F, ldw, _p(count), float(threshold), _st()), "pdmk_wanda_apply")
+
+
+def mask_row_words(F):
+    """32-bit words of one weight row's mask bits (bit f & 31 of word f >> 5)."""
+    return (int(F) + 31) // 32
+
+
+def wanda_select(w, n_base, n_target, k, bits, O=None, F=None, ldw=None):
+    """wanda_count's selection as bits: bits [T, >= O * row_words] (int32, unit word stride, any row stride) - bit f & 31 of
+    bits[t, o * row_words + (f >> 5)] is set where wanda_count would add one at timestep t.  The O * row_words words of every t
+    are overwritten, the others are not touched."""
+    O = w.shape[0] if O is None else O
+    F = w.shape[1] if F is None else F
+    ldw = w.stride(0) if ldw is None else ldw
+    if F > WANDA_MAX_F:
+        raise PdmkError(f"wanda_select: F = {F} is wider than the {WANDA_MAX_F} columns the selection kernel keeps on chip")
+    T = n_base.shape[0]
+    for n in (n_base, n_target):
+        if n.dtype != torch.float32 or tuple(n.shape) != (T, F) or not n.is_contiguous():
+            raise PdmkError(f"wanda_select: norms must be contiguous fp32 [T, {F}], got {tuple(n.shape)} {n.dtype}")
+    words = O * mask_row_words(F)
+    if (bits.dtype != torch.int32 or bits.dim() != 2 or bits.shape[0] != T or bits.shape[1] < words or bits.stride(1) != 1
+            or bits.stride(0) < words):
+        raise PdmkError(f"wanda_select: bits must be int32 [{T}, >= {words}] with unit word stride")
+    _chk(_lib.pdmk_wanda_select(_p(w), dt(w), O, F, ldw, _p(n_base), _p(n_target), T, int(k), _p(bits), bits.stride(0), _st()),
+         "pdmk_wanda_select")
+
+
+MASK_PIECE = 16384     # elements one workgroup of pdmk_masked_weights works through (a layer is cut into row blocks of about this)
+
+
+class MaskTable:
+    """Layers [(dst element offset, O, F, ld)] as the device table of pdmk_masked_weights.  The pristine copy `src` is compact:
+    layer after layer in the given order, each O * ld elements (rounded up to 8, so every layer starts 16-byte aligned); so are
+    the mask words of one timestep, each layer O * row_words.  `layers` keeps (dst_off, src_off, bits_off, O, F, ld) per layer;
+    `extent` (one past the last dst element a layer owns), `src_elems` and `words` are what masked_weights checks the buffers
+    against.  A layer is cut into blocks of whole weight rows of about `piece` elements, one workgroup each."""
+
+    def __init__(self, layers, device, piece=MASK_PIECE):
+        import numpy as np
+        rec = np.dtype([("dst", "<i8"), ("src", "<i8"), ("bits", "<i8"), ("O", "<i4"), ("F", "<i4"), ("ld", "<i4"), ("pad", "<i4")])
+        if not layers or piece <= 0:
+            raise PdmkError("masked_weights: no layers")
+        self.layers, rows, soff, boff, end = [], [], 0, 0, 0
+        for d, O, F, ld in layers:
+            d, O, F, ld = int(d), int(O), int(F), int(ld)
+            if d < 0 or O <= 0 or F <= 0 or ld < F:
+                raise PdmkError(f"masked_weights: layer ({d}, {O}, {F}, {ld})")
+            rw = mask_row_words(F)
+            self.layers.append((d, soff, boff, O, F, ld))
+            per = max(1, piece // F)
+            for o0 in range(0, O, per):
+                rows.append((d + o0 * ld, soff + o0 * ld, boff + o0 * rw, min(per, O - o0), F, ld, 0))
+            soff += (O * ld + 7) // 8 * 8
+            boff += O * rw
+            end = max(end, d + O * ld)
+        tab = np.array(rows, dtype=rec)
+        self.nrows, self.extent, self.src_elems, self.words = len(rows), end, soff, boff
+        self.dev = torch.frombuffer(bytearray(tab.tobytes()), dtype=torch.uint8).to(device)
+
+
+def masked_weights(dst, src, table, bits=None, slot=-1, state=None, repeat_first=False):
+    """dst = src * (1 - mask[slot]) on the layers a MaskTable names, one launch (include/pdmk.h pdmk_masked_weights).  bits: int32
+    [T, >= table.words] or None (the unmasked weights); slot: the host value, or with `state` (int32 device tensor) the U-Net
+    call number state[0], mapped through repeat_first.  A slot outside [0, T) writes the unmasked weights."""
+    if (not isinstance(table, MaskTable) or dst.dtype != src.dtype or not dst.is_contiguous() or not src.is_contiguous()
+            or dst.numel() < table.extent or src.numel() < table.src_elems or table.dev.device != dst.device
+            or src.device != dst.device):
+        raise PdmkError("masked_weights: inconsistent buffers")
+    T, stride = 0, 0
+    if bits is not None:
+        if (bits.dtype != torch.int32 or bits.dim() != 2 or bits.shape[1] < table.words or bits.stride(1) != 1
+                or bits.stride(0) < table.words or bits.device != dst.device):
+            raise PdmkError(f"masked_weights: bits must be int32 [T, >= {table.words}] with unit word stride on the weights' device")
+        T, stride = bits.shape[0], bits.stride(0)
+    if state is not None and (state.dtype != torch.int32 or state.numel() < 1 or state.device != dst.device):
+        raise PdmkError("masked_weights: state must be an int32 tensor on the weights' device")
+    _chk(_lib.pdmk_masked_weights(_p(dst), _p(src), dt(dst), _p(table.dev), table.nrows, _p(bits), stride, T, int(slot),
+                                  _p(state), int(bool(repeat_first)), _st()), "pdmk_masked_weights")
 
 
 # ---- UCE (pdmk.h "UCE")

@@ -27,6 +27,11 @@ pdmk_calg_ddim_step (captured, 5B rows) applies them.  Without the keyword nothi
 K-LMS (`LMSDiscreteScheduler`, what the reference's UCE evaluation scripts sample with) calls the U-Net at
 fractional float32 timesteps on inputs divided by sqrt(sigma^2 + 1).  Its loop is captured by default like PNDM's, with
 pdmk_lms_step / pdmk_sld_lms_step / pdmk_calg_lms_step as the step kernel (the next input's division included), one replay per step.
+
+ConceptPrune's neuron removal (`neuron_masks=`, a utils.concept_prune.TimestepMasks) sets the ff.net.2 compute
+weights to W * (1 - mask[t]) before every U-Net call: one pdmk_masked_weights launch, from the host slot in the eager loop and
+from the device-side call counter as the first node of the captured graph.  The weights are restored when the call ends.
+Without the keyword nothing of it runs.
 """
 import ctypes
 import gc
@@ -337,8 +342,12 @@ class _CapturedLoop:
     (N + 1 calls for N PLMS steps, N for N DDIM or LMS steps), or fewer when the caller stops early.  The graph reads the
     U-Net's weight arenas in place: it stays valid while an optimiser rewrites them."""
 
-    def __init__(self, unet, B, h, w, cfg_on, guidance_scale, nsteps, T, ctx, kind="plms", sld=None, algebra=False):
+    def __init__(self, unet, B, h, w, cfg_on, guidance_scale, nsteps, T, ctx, kind="plms", sld=None, algebra=False, masks=None):
         dev, dt = unet.device, unet.dtype
+        # utils.concept_prune.TimestepMasks: pdmk_masked_weights is the graph's FIRST node - it reads the call counter that the
+        # previous replay's step kernel advanced (one stream) and sets the ff.net.2 compute weights of this call; the graph
+        # holds the addresses of the masks' buffers, and the loop the object, so they live as long as it does
+        self.masks = masks
         if kind not in ("plms", "ddim", "lms"):
             raise ValueError(f"_CapturedLoop: step kind {kind!r}")
         self.kind = kind
@@ -372,6 +381,8 @@ class _CapturedLoop:
         self._capture()
 
     def _body(self):
+        if self.masks is not None:
+            self.masks.apply(state=self.state, repeat_first=self.kind == "plms")
         pred, _ = self.unet.forward_nhwc(self.x, self.t, self.ehs, self.R, self.h, self.w, train=False)
         if self.algebra:
             k.calg_dots(pred.t, pred.t.stride(0), self.B, self.C, self.h * self.w, self.ws)
@@ -520,19 +531,21 @@ class StableDiffusionPruningPipeline:
             return False
         return graph is True or os.environ.get("PDMK_SAMPLER_GRAPH", "1") != "0"
 
-    def _loop(self, B, h, w, cfg_on, guidance_scale, nsteps, T, ctx, sld=None, algebra=False):
+    def _loop(self, B, h, w, cfg_on, guidance_scale, nsteps, T, ctx, sld=None, algebra=False, masks=None):
         key = (B, h, w, self.unet.dtype, cfg_on, nsteps, T, ctx, float(guidance_scale), type(self.scheduler))
         if sld is not None:
             key += ("sld",) + sld.key()
         if algebra:
             key += ("algebra",)
+        if masks is not None:
+            key += ("masks", masks)                                   # the object: its buffers are what the graph reads
         loop = self._loops.pop(key, None)
         if loop is None:
             while len(self._loops) >= self.GRAPH_SHAPES:
                 self._loops.pop(next(iter(self._loops))).close()
             loop = _CapturedLoop(self.unet, B, h, w, cfg_on, guidance_scale, nsteps, T, ctx,
                                  kind={DDIMScheduler: "ddim", LMSDiscreteScheduler: "lms"}.get(type(self.scheduler), "plms"),
-                                 sld=sld, algebra=algebra)
+                                 sld=sld, algebra=algebra, masks=masks)
             self.captures += 1
         self._loops[key] = loop                                       # most recently used last
         return loop
@@ -544,7 +557,7 @@ class StableDiffusionPruningPipeline:
                          prompt=None, negative_prompt=None, graph=None, end_iteration=None, safety_concept=None,
                          safety_concept_ids=None, safety_concept_embeds=None, sld_guidance_scale=1000.0, sld_warmup_steps=10,
                          sld_threshold=0.01, sld_momentum_scale=0.3, sld_mom_beta=0.4, algebra_concepts=None,
-                         algebra_ids=None, algebra_embeds=None):
+                         algebra_ids=None, algebra_embeds=None, neuron_masks=None):
         """prompt / negative_prompt: strings or lists of strings (needs the tokenizer; with guidance and no negative prompt
         the empty prompt).  output_type "latent", "pt", "np" (float32 NHWC in [0, 1]), "u8" (uint8 NHWC numpy, the FID
         script's `(img * 255).astype(np.uint8)`, formed on the device) or "u8_round" (the same with diffusers' numpy_to_pil
@@ -562,7 +575,12 @@ class StableDiffusionPruningPipeline:
         ([3, T, ctx]): concept algebra - three further U-Net branches p0, p1, p2; the text score loses its component along
         p1 - p0, measured against p2, over the whole batch (include/pdmk.h "Concept algebra").  Exactly three concepts, each
         encoded once per call and repeated over the batch; ValueError together with a safety concept or when
-        guidance_scale <= 1."""
+        guidance_scale <= 1.
+        neuron_masks (utils.concept_prune.TimestepMasks of this U-Net): ConceptPrune's neuron removal - U-Net call
+        t runs with the ff.net.2 weights W * (1 - mask[slot(t)]), slot(t) = t, with PNDM 0, 0, 1, 2, ...  num_inference_steps
+        must be the masks' T.  DDIM (captured unless PDMK_SAMPLER_GRAPH=0, graph=False, a callback, hooks or an observer ask
+        for the eager loop) and PNDM; K-LMS raises NotImplementedError, SLD or concept algebra beside the masks ValueError.
+        The weights are restored when the call returns or raises.  None: nothing of it runs."""
         cfg_on = guidance_scale > 1.0
         algebra = algebra_concepts is not None or algebra_ids is not None or algebra_embeds is not None
         if algebra:
@@ -610,15 +628,22 @@ class StableDiffusionPruningPipeline:
         latents = (latents.to(dev, torch.float32) * sch.init_noise_sigma).contiguous()
         if end_iteration is not None and not 0 <= int(end_iteration) <= len(sch.timesteps):
             raise ValueError(f"end_iteration={end_iteration} outside 0 ... {len(sch.timesteps)}")
-        if self._use_graph(graph, callback):
-            loop = self._loop(B, shape[2], shape[3], cfg_on, guidance_scale, len(sch.timesteps), ehs.shape[1], ehs.shape[2],
-                              sld=sld, algebra=algebra)
-            rows = getattr(sch, loop.kind + "_rows")()
-            x0 = sch.scale_model_input(latents, sch.timesteps[0].item()) if loop.kind == "lms" else None
-            latents = loop.run(latents, ehs, rows, n_calls=end_iteration, x0=x0)
-        else:
-            latents = self._eager_loop(latents, ehs, B, shape, cfg_on, guidance_scale, callback, callback_steps, end_iteration,
-                                       sld=sld, algebra=algebra)
+        if neuron_masks is not None:
+            graph = self._check_masks(neuron_masks, num_inference_steps, graph, sld is not None or algebra)
+            neuron_masks.attach()
+        try:
+            if self._use_graph(graph, callback):
+                loop = self._loop(B, shape[2], shape[3], cfg_on, guidance_scale, len(sch.timesteps), ehs.shape[1], ehs.shape[2],
+                                  sld=sld, algebra=algebra, masks=neuron_masks)
+                rows = getattr(sch, loop.kind + "_rows")()
+                x0 = sch.scale_model_input(latents, sch.timesteps[0].item()) if loop.kind == "lms" else None
+                latents = loop.run(latents, ehs, rows, n_calls=end_iteration, x0=x0)
+            else:
+                latents = self._eager_loop(latents, ehs, B, shape, cfg_on, guidance_scale, callback, callback_steps,
+                                           end_iteration, sld=sld, algebra=algebra, masks=neuron_masks)
+        finally:
+            if neuron_masks is not None:
+                neuron_masks.detach()
         if output_type == "latent":
             image = latents
         else:
@@ -636,6 +661,22 @@ class StableDiffusionPruningPipeline:
                 if output_type == "np":
                     image = image.permute(0, 2, 3, 1).cpu().numpy()
         return SimpleNamespace(images=image, nsfw_content_detected=None) if return_dict else (image, None)
+
+    def _check_masks(self, masks, num_inference_steps, graph, other_guidance):
+        """What neuron_masks= asks of the call; returns `graph` (a DDIM loop with masks is captured unless something asks for
+        the eager one)."""
+        kind = type(self.scheduler)
+        if kind not in (PNDMScheduler, DDIMScheduler):                # K-LMS: nothing pins what its slots would be
+            raise NotImplementedError(f"neuron_masks with {kind.__name__}: the timestep slots are defined for DDIM and PNDM only")
+        if other_guidance:
+            raise ValueError("neuron_masks combines with plain classifier-free guidance only, not with SLD or concept algebra")
+        if getattr(masks, "unet", None) is not self.unet:
+            raise ValueError("neuron_masks were built for another U-Net")
+        if int(num_inference_steps) != masks.T:
+            raise ValueError(f"num_inference_steps={num_inference_steps}, but the neuron masks hold {masks.T} timesteps")
+        if kind is DDIMScheduler and graph is None and os.environ.get("PDMK_SAMPLER_GRAPH", "1") != "0":
+            graph = True
+        return graph
 
     def _safety_embeds(self, concept, ids, embeds, B, ehs):
         """The safety concept's text embeddings [B, T, ctx]: encoded once, repeated over the batch."""
@@ -664,7 +705,7 @@ class StableDiffusionPruningPipeline:
         return embeds.to(ehs.dtype)[:, None].expand(3, B, -1, -1).reshape((3 * B,) + tuple(ehs.shape[1:]))
 
     def _eager_loop(self, latents, ehs, B, shape, cfg_on, guidance_scale, callback, callback_steps, end_iteration=None,
-                    sld=None, algebra=False):
+                    sld=None, algebra=False, masks=None):
         dev, sch = self.device, self.scheduler
         was_training = self.unet.training
         self.unet.eval()
@@ -686,6 +727,8 @@ class StableDiffusionPruningPipeline:
                         x2[j * B:(j + 1) * B].copy_(latents)
                 tt = torch.full((x2.shape[0],), t, device=dev,
                                 dtype=torch.float32 if sch.timesteps.is_floating_point() else torch.int64)
+                if masks is not None:                                 # U-Net call i: timestep slot i (PNDM: 0, 0, 1, 2, ...)
+                    masks.apply(slot=max(i - 1, 0) if type(sch) is PNDMScheduler else i)
                 out = self.unet(sch.scale_model_input(x2, t), tt, ehs, return_dict=False)[0]
                 if algebra:       # the two sums over the whole batch, then the projection and the guidance
                     out = out.contiguous()

@@ -10,6 +10,11 @@ sampling), `union_counts` (pdmk_wanda_count, one launch per layer for all T) and
 
 Only hook_module `unet` is built.  The reference's per-timestep pickles of selected neurons (an intermediate that only its
 remove_neurons.py reads) are not written: the counts over time are formed on the device in one pass.
+
+Neuron removal at sampling time (the reference's remove_neurons.py with neuron_receivers/neuron_remover.py: at U-Net call t
+layer l runs with W * (1 - mask[t][l])) is `TimestepMasks`: the same selection as one bit per (t, o, f) on the device
+(pdmk_wanda_select), applied to the engine's compute weights by one launch per U-Net call (pdmk_masked_weights), in the eager
+sampler and as the first node of the captured one (`StableDiffusionPruningPipeline(..., neuron_masks=)`).
 """
 import os
 from types import SimpleNamespace
@@ -87,6 +92,7 @@ def result_paths(args):
     res = os.path.join(root, model_component(args.model_id), args.target)
     return SimpleNamespace(res_path=res, images=os.path.join(res, "images"),
                            skilled_neurons=os.path.join(res, "skilled_neurons", str(args.skill_ratio)),
+                           after_removal_results=os.path.join(res, "after_removal_results", str(args.skill_ratio)),
                            checkpoints=os.path.join(res, "checkpoints"))
 
 
@@ -281,6 +287,128 @@ def apply_counts(unet, counts, select_ratio, timesteps):
         density[key] = float((c.to(torch.float32) > thr).float().mean().item())
     unet.store.refresh()
     return density
+
+
+# ---- per-timestep masks: neuron removal while sampling (the reference's remove_neurons.py / NeuronRemover)
+def call_slot(call, repeat_first=False):
+    """The timestep slot of U-Net call `call` of a sampling run (WandaObserver.slot): the call number, or with repeat_first
+    (PNDM: the first timestep is called twice) 0, 0, 1, 2, ..."""
+    return max(int(call) - 1, 0) if repeat_first else int(call)
+
+
+def pack_bits(mask):
+    """bool [..., F] -> int32 [..., (F + 31) // 32]: bit f & 31 of word f >> 5 (include/pdmk.h pdmk_wanda_select); the bits
+    past F in the last word are 0."""
+    F = mask.shape[-1]
+    rw = (F + 31) // 32
+    m = torch.zeros(tuple(mask.shape[:-1]) + (rw * 32,), dtype=torch.int64, device=mask.device)
+    m[..., :F] = mask.to(torch.int64)
+    words = (m.view(tuple(mask.shape[:-1]) + (rw, 32)) << torch.arange(32, device=mask.device)).sum(-1)
+    return torch.where(words >= 2 ** 31, words - 2 ** 32, words).to(torch.int32)
+
+
+def unpack_bits(words, F):
+    """int32 [..., (F + 31) // 32] -> bool [..., F], the inverse of pack_bits."""
+    rw = (F + 31) // 32
+    if words.shape[-1] != rw:
+        raise ValueError(f"unpack_bits: {words.shape[-1]} words per row, F = {F} takes {rw}")
+    w = words.to(torch.int64) & 0xFFFFFFFF
+    bits = (w[..., None] >> torch.arange(32, device=words.device)) & 1
+    return bits.reshape(tuple(words.shape[:-1]) + (rw * 32,))[..., :F].to(torch.bool)
+
+
+class TimestepMasks:
+    """mask[t][l] of every `...ff.net.2` of `unet` as bits on the device - one arena int32 [T][sum_l O_l * row_words_l], layer
+    after layer in ffn_layers() order - and what applies them while sampling: at U-Net call t the engine's compute weights of
+    those layers are `pristine * (1 - mask[slot(t)])`, set by ONE pdmk_masked_weights launch from a pristine copy of the
+    layers' weights (in fp32 the compute arena IS the master arena: masking in place would lose the weights).
+
+        masks = TimestepMasks.from_norms(unet, base_norms, target_norms, skill_ratio)
+        with masks.attach():                      # the pristine copy is taken; restored on exit, on an error too
+            masks.apply(slot=3)                   # or apply(state=device call counter, repeat_first=...)
+
+    The pristine buffer, the bit arena and the table are allocated once and keep their addresses, so a captured graph that
+    holds the launch stays valid from one attach() to the next.  A new object starts with all-zero masks."""
+
+    def __init__(self, unet, timesteps):
+        from .. import _pdmk as k
+        self.unet, self.T = unet, int(timesteps)
+        if self.T < 1:
+            raise ValueError(f"TimestepMasks: {timesteps} timesteps")
+        self.layers = ffn_layers(unet)
+        st = unet.store
+        self.table = k.MaskTable([(st.by_key[key + ".weight"].off, O, F, fp) for key, O, F, fp in self.layers], unet.device)
+        self.bits = torch.zeros((self.T, self.table.words), device=unet.device, dtype=torch.int32)
+        self._src = torch.zeros(self.table.src_elems, device=unet.device, dtype=st.w.dtype)
+        self.attached = False
+
+    def layer_bits(self, l):
+        """int32 [T, O, row_words] view of layer l's words."""
+        _d, _s, boff, O, F, _ld = self.table.layers[l]
+        rw = (F + 31) // 32
+        return self.bits[:, boff:boff + O * rw].view(self.T, O, rw)
+
+    @classmethod
+    @torch.no_grad()
+    def from_norms(cls, unet, base_norms, target_norms, skill_ratio):
+        """The masks of pdmk_wanda_count's selection (on the fp32 master weights, as union_counts), one pdmk_wanda_select per
+        layer for all T; base_norms / target_norms: [fp32 [T, F_l]] as load_norms() / WandaObserver.norms() give them."""
+        from .. import _pdmk as k
+        layers = ffn_layers(unet)
+        if len(base_norms) != len(layers) or len(target_norms) != len(layers):
+            raise ValueError(f"norms of {len(base_norms)} / {len(target_norms)} layers, the model has {len(layers)}")
+        self = cls(unet, base_norms[0].shape[0])
+        for l, ((key, O, F, _fp), nb, nt) in enumerate(zip(layers, base_norms, target_norms)):
+            if tuple(nb.shape) != (self.T, F) or tuple(nt.shape) != (self.T, F):
+                raise ValueError(f"{key}: norms {tuple(nb.shape)} / {tuple(nt.shape)}, expected {(self.T, F)}")
+            w, e = _weight_view(unet, key)
+            boff = self.table.layers[l][2]
+            k.wanda_select(w, nb.to(unet.device, torch.float32).contiguous(), nt.to(unet.device, torch.float32).contiguous(),
+                           top_k(skill_ratio, F), self.bits[:, boff:boff + O * ((F + 31) // 32)], O=O, F=F, ldw=e.shape[1])
+        return self
+
+    def density(self):
+        """{layer key: [T floats]}: the share of masked weights of the layer at every timestep."""
+        out = {}
+        for l, (key, O, F, _fp) in enumerate(self.layers):
+            n = unpack_bits(self.layer_bits(l), F).sum((1, 2)).tolist()
+            out[key] = [c / (O * F) for c in n]
+        return out
+
+    @torch.no_grad()
+    def attach(self):
+        """Takes the pristine copy of the layers' compute weights (a second attach() without detach() keeps the first copy)."""
+        if not self.attached:
+            w = self.unet.store.w
+            for d, s, _b, O, _F, ld in self.table.layers:
+                self._src[s:s + O * ld].copy_(w[d:d + O * ld])
+            self.attached = True
+        return self
+
+    @torch.no_grad()
+    def detach(self):
+        """Writes the pristine weights back: the arena is then bit for bit what attach() found."""
+        if self.attached:
+            from .. import _pdmk as k
+            k.masked_weights(self.unet.store.w, self._src, self.table)
+            self.attached = False
+
+    def __enter__(self):
+        return self.attach()
+
+    def __exit__(self, *exc):
+        self.detach()
+
+    def apply(self, slot=None, state=None, repeat_first=False):
+        """The compute weights of timestep slot `slot` (a host int; outside [0, T): unmasked), or of the U-Net call number in
+        the int32 device tensor `state`[0], which repeat_first maps as call_slot() does."""
+        from .. import _pdmk as k
+        if not self.attached:
+            raise RuntimeError("TimestepMasks.apply: attach() first (the pristine copy is what the masked weights are made from)")
+        if (slot is None) == (state is None):
+            raise ValueError("TimestepMasks.apply: pass slot= or state=")
+        k.masked_weights(self.unet.store.w, self._src, self.table, self.bits, slot=-1 if slot is None else int(slot),
+                         state=state, repeat_first=repeat_first)
 
 
 def masked_state_dict(unet):
